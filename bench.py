@@ -22,8 +22,12 @@ Usage: python bench.py --gpus N --steps K --warmup W
   --single-process: no RCCL, ONE process drives N devices through tl_two_opt_multistart_devices (the path a Rust caller
         has); cross-check of the RCCL number.
   --dry-launch: rehearsal of the launch + collective plumbing on CPU (gloo, a stub step, no GPU, no oracle): NOT a measurement.
-Rank 0 prints the long material first (`EXTRAS {...}` lines, also written whole to ./bench_extras.json) and then, as the LAST
-stdout line, ONE compact JSON object of at most 4096 bytes (asserted) — the line the driver parses.
+  --full: everything beside the headline — the untimed work-count launch and the roofline, the strong-scaling loop where it is
+        a loop of its own, the extras (other kernels, sizes and flags), the CPU baselines and the bit-for-bit parity check of
+        the timed restarts against the oracle.  Without it a run sets up, warms up, times the K steps and prints the line.
+  --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed back as DIR/<name>.npy (dump_outputs).
+With --full, rank 0 prints the long material first (`EXTRAS {...}` lines, also written whole to ./bench_extras.json); the LAST
+stdout line is always ONE compact JSON object of at most 4096 bytes (asserted) — the line the driver parses.
 """
 import argparse
 import ctypes as C
@@ -72,7 +76,16 @@ def parse():
                          "the rehearsal of that path on a one-GPU box")
     ap.add_argument("--dry-launch", action="store_true",
                     help="CPU rehearsal of the N-rank launch and the collectives (gloo, stub step): prints a line with value null")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the work count + roofline, the strong-scaling loop, the extras, the CPU baselines and the oracle parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs (tours, costs, descent counters, the winner) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and (a.single_process or a.dry_launch):
+        ap.error("--dump-outputs writes the outputs of the device-resident batch path: not with --single-process or --dry-launch")
+    return a
 
 
 def free_port():
@@ -438,7 +451,7 @@ def emit(full, stream=None):
     side = _round_floats(full, 9)
     for d in (os.getcwd(), os.path.join(ROOT, "gpurun_out")):
         try:
-            if os.path.isdir(d) and os.access(d, os.W_OK):
+            if "extras" in side and os.path.isdir(d) and os.access(d, os.W_OK):
                 with open(os.path.join(d, SIDECAR), "w") as fh:
                     json.dump(side, fh, indent=1)
         except OSError:
@@ -452,6 +465,30 @@ def emit(full, stream=None):
     print(line, file=stream)
     stream.flush()
     return line
+
+
+DUMP_LIMIT = 64 << 20  # bytes of .npy data --dump-outputs may write in all
+
+
+def dump_outputs(d, seed, d_pos, d_cost, d_stats, best_tour, best_cost, best_restart):
+    """--dump-outputs DIR: what tl_two_opt_batch_dev and the collective handed back in the last timed step, on rank 0:
+    tours.npy (restarts x n city ids, f32: exact below 2^24), costs.npy (f32), descent_stats.npy (sweeps, moves, reversed, status
+    per descent, f64: the deterministic words; the rest are clocks and speculative-work counters), best_tour.npy (the winner's
+    tour every rank receives, f32) and best.npy (its cost and restart id, f64).  Past DUMP_LIMIT the tours are a fixed sample of
+    rows drawn with the restart seed, listed in tour_rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    R, n = d_pos.shape
+    assert n < (1 << 24)
+    rows = np.arange(R)
+    keep = (DUMP_LIMIT - (1 << 20)) // (4 * n)  # 1 MB left for the small arrays
+    if R > keep:
+        rows = np.sort(np.random.default_rng(seed).choice(R, keep, replace=False))
+        np.save(os.path.join(d, "tour_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(d, "tours.npy"), d_pos[torch.from_numpy(rows).to(d_pos.device)].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(d, "costs.npy"), d_cost.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(d, "descent_stats.npy"), d_stats[:, :4].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(d, "best_tour.npy"), best_tour.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(d, "best.npy"), np.array([best_cost, best_restart], dtype=np.float64))
 
 
 def gather_rank_ms(ms_local, device, dist):
@@ -678,7 +715,7 @@ def main():
     # The work the cascade really did: one more launch of the same batch, UNTIMED, with the counting instantiation of the
     # kernel (TL_FLAG_COUNT_WORK; the counters cost ~8 %, so the timed kernel does not carry them): st[5..8].
     work = {"l0_tile_bounds": 0, "l1_candidates": 0, "l2_candidates": 0, "l3_candidates": 0}
-    if not a.no_work_count:
+    if a.full and not a.no_work_count:
         with TA.Context(local, TA.TL_FLAG_COUNT_WORK) as cc:
             d_pos2, d_cost2, d_stats2 = torch.empty_like(d_pos), torch.empty_like(d_cost), torch.zeros_like(d_stats)
             with torch.cuda.stream(stream):
@@ -701,13 +738,13 @@ def main():
     per_rank_ms = gather_rank_ms(dt / a.steps * 1e3, dev, dist)
     best_cost, best_restart = TA.multistart.unpack_key(key.item())
     # The other reading of configs[3], in the same line: a FIXED total of restarts dealt over the ranks (strong scaling).  At one
-    # GPU with the default 256 per GPU it is the timed loop above, word for word; otherwise a second timed loop of the same K steps.
+    # GPU with the default 256 per GPU it is the timed loop above, word for word; otherwise (--full) a second timed loop of the same K steps.
     weak_obj = strong_obj = None
     if not strong:
         weak_obj = {"ms_per_step": dt_max / a.steps * 1e3, "value": total / dt_max, "restarts_per_rank": R}
         if world == 1 and R == STRONG_TOTAL:
             strong_obj = dict(weak_obj, note="one GPU: the same batch as the headline loop (not run twice)")
-        else:
+        elif a.full:
             sf, sR = TA.multistart.shard_total(rank, world, STRONG_TOTAL)
             S = timed_loop(sf, sR, a.steps, min(a.warmup, 1))
             s_total, s_dt_max = TA.multistart.aggregate_throughput(S["cands"], S["dt"], dev, dist)
@@ -717,12 +754,15 @@ def main():
     else:
         strong_obj = {"ms_per_step": dt_max / a.steps * 1e3, "value": total / dt_max, "restarts_per_rank": R}
 
-    strong_obj["cross_cu_round_us"] = list(XCU_ROUND_US)
+    if strong_obj is not None:
+        strong_obj["cross_cu_round_us"] = list(XCU_ROUND_US)
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
         return
 
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, a.seed, d_pos, d_cost, d_stats, best_tour[0], best_cost, best_restart)
     bt = best_tour[0].cpu().numpy()
     assert sorted(bt.tolist()) == list(range(n)), "the shared best tour is not a permutation"
     status_bad = int((d_stats[:, 3] != 0).sum().item())
@@ -754,20 +794,21 @@ def main():
         "device": info,
         "roofline": None,
     }
-    out["candidates_touched"] = {
-        **work,
-        "l1_candidates_per_s": work["l1_candidates"] / (k_ms * 1e-3),
-        "fraction_of_algorithmic": work["l1_candidates"] / max(cand_per_launch, 1.0),
-        "note": "per launch, counted by the kernel's counting instantiation in one untimed launch of the same batch (same tours, "
-                "asserted): tile bounds evaluated by L0 (64 tiles per wave pass), candidates whose "
-                "squared-distance test L1 ran, candidates that went on to the v_sqrt_f32 test L2, and to the exact L3; "
-                "`value` counts candidates as the reference's loop visits them (SURVEY.md §8(d)), L0 decides most of "
-                "them a tile at a time",
-    }
-    out["value_l1_evaluated"] = {"value": out["candidates_touched"]["l1_candidates_per_s"], "unit": "candidates/s",
-                                 "note": "candidates whose own squared-distance test (L1) ran, per second of kernel time — what is left after the tile bound L0"}
-    out["roofline"] = valu_roofline(n, R, a.seed, first, info, k_ms, clock_hz, work, cand_per_launch, a.steps)
-    if world == 1 and not a.no_extras:
+    if a.full:
+        out["candidates_touched"] = {
+            **work,
+            "l1_candidates_per_s": work["l1_candidates"] / (k_ms * 1e-3),
+            "fraction_of_algorithmic": work["l1_candidates"] / max(cand_per_launch, 1.0),
+            "note": "per launch, counted by the kernel's counting instantiation in one untimed launch of the same batch (same tours, "
+                    "asserted): tile bounds evaluated by L0 (64 tiles per wave pass), candidates whose "
+                    "squared-distance test L1 ran, candidates that went on to the v_sqrt_f32 test L2, and to the exact L3; "
+                    "`value` counts candidates as the reference's loop visits them (SURVEY.md §8(d)), L0 decides most of "
+                    "them a tile at a time",
+        }
+        out["value_l1_evaluated"] = {"value": out["candidates_touched"]["l1_candidates_per_s"], "unit": "candidates/s",
+                                     "note": "candidates whose own squared-distance test (L1) ran, per second of kernel time — what is left after the tile bound L0"}
+        out["roofline"] = valu_roofline(n, R, a.seed, first, info, k_ms, clock_hz, work, cand_per_launch, a.steps)
+    if world == 1 and a.full and not a.no_extras:
         extras = {}
         try:  # the extras must never cost the run its headline line
             # Two descents per CU: with more restarts than CUs the library keeps the tours as grid coordinates (7 B per city instead
@@ -1096,7 +1137,7 @@ def main():
         if "multistart_two_descents_per_cu" in extras:  # the same kernel with a batch of 2 x CUs restarts (two descents per CU), for the record
             out["value_with_two_descents_per_cu"] = {"value": extras["multistart_two_descents_per_cu"]["candidates_per_s"], "unit": "candidates/s",
                                                      "restarts_per_gpu": extras["multistart_two_descents_per_cu"]["restarts"]}
-    if world == 1 and not a.no_cpu_baseline:
+    if world == 1 and a.full and not a.no_cpu_baseline:
         res, out["cpu_baseline"] = cpu_baseline(n, a.seed, xy)
         # the oracle's descents of restarts 0..cores-1 are the same units the GPU just ran: cost bits and sweep / move
         # counters must agree, or the headline number counts something else than the reference's loop

@@ -159,14 +159,31 @@ def test_rust_binding_matches_the_header():
     assert m and f"#define TL_ABI_VERSION {m.group(1)}" in open(HEADER).read()
 
 
-def test_reference_patch_applies_cleanly():
-    """integration/patches/0001-gpu-feature.patch against the reference tree (present in the build container only)."""
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "src", "tsp")):
-        pytest.skip("reference tree not present")
-    patch = os.path.join(ROOT, "integration", "patches", "0001-gpu-feature.patch")
-    r = subprocess.run(["patch", "-p1", "--dry-run", "-d", ref, "-i", patch], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+def test_reference_patch_applies_cleanly(tmp_path):
+    """integration/patches/0001-gpu-feature.patch against the reference tree it was cut against, kept as SHA-256 digests in
+    tests/golden/reference_patch_targets.json (make_patch_fingerprint.py): every hunk replaces exactly the reference's lines at the
+    line numbers it names, and `patch` takes it without offset or fuzz on a tree rebuilt from those lines."""
+    import json
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_patch_fingerprint as F
+    want = json.load(open(F.OUT))
+    got = F.parse(open(F.PATCH).read())
+    assert sorted(got) == sorted(want)
+    for path, hunks in got.items():
+        if want[path] is None:
+            assert all(s == 0 and n == 0 for s, n, _ in hunks), f"{path}: not in the reference tree, but the patch edits it"
+            continue
+        assert [[s, n, F.sha(old)] for s, n, old in hunks] == want[path]["hunks"], f"{path}: a hunk does not fit the reference's lines"
+        text = [f"{path}: line {k + 1}\n" for k in range(want[path]["lines"])]
+        for s, n, old in hunks:
+            text[s - 1:s - 1 + n] = old
+        dst = tmp_path / path
+        dst.parent.mkdir(parents=True, exist_ok=True)
+        dst.write_text("".join(text))
+    patch = F.PATCH
+    r = subprocess.run(["patch", "-p1", "--dry-run", "-F0", "-d", str(tmp_path), "-i", patch], capture_output=True, text=True)
+    assert r.returncode == 0 and "offset" not in r.stdout and "fuzz" not in r.stdout, r.stdout + r.stderr
     # the three arms SURVEY.md §8(b) names are switched, and the module added by the patch is the file kept beside the crate
     text = open(patch).read()
     for arm in ("two_opt_impl::solve(problem, &h, tx, init_tour)", "three_opt_impl::solve(problem, &h, tx, init_tour)",
@@ -186,12 +203,12 @@ def test_reference_patch_carries_the_current_gpu_rs():
 
 
 def test_rust_side_compiles():
-    """scripts/check_rust.sh: `cargo check` of the FFI crate (and of the patched reference where a checkout is given).  Exit 3 = no
-    Rust toolchain on this box: the Rust side is UNCOMPILED — reported as an expected failure so that it shows in every summary
-    instead of passing silently."""
+    """scripts/check_rust.sh: `cargo check` of the FFI crate (and of the patched reference where $TEELINE_REFERENCE_DIR names a
+    checkout).  Exit 3 = no Rust toolchain on this box: the Rust side is UNCOMPILED — reported as an expected failure so that it
+    shows in every summary instead of passing silently."""
     import shutil
-    r = subprocess.run(["bash", os.path.join(ROOT, "scripts", "check_rust.sh")] + (["/root/reference"] if os.path.isdir("/root/reference/src/tsp") else []),
-                       capture_output=True, text=True)
+    ref = os.environ.get("TEELINE_REFERENCE_DIR")
+    r = subprocess.run(["bash", os.path.join(ROOT, "scripts", "check_rust.sh")] + ([ref] if ref else []), capture_output=True, text=True)
     if r.returncode == 3:
         assert shutil.which("cargo") is None
         pytest.xfail("no cargo / rustc in this image: integration/teeline-gpu (lib.rs, gpu.rs, the reference patch) has never been compiled")

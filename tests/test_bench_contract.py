@@ -77,6 +77,11 @@ def test_emit_prints_the_compact_line_last_and_refuses_an_oversized_one(tmp_path
     assert [ln[:10] for ln in lines[:-1]] == ["EXTRAS {\"a", "EXTRAS {\"b", "EXTRAS {\"h"]
     side = json.load(open(tmp_path / bench.SIDECAR))
     assert side["extras"]["a"]["note"] == "n" * 20000 and json.loads(last)["extras_keys"] == ["a", "b"]
+    plain = tmp_path / "plain"
+    plain.mkdir()
+    monkeypatch.chdir(plain)
+    bench.emit({k: v for k, v in full.items() if k != "extras"}, stream=io.StringIO())
+    assert not os.path.exists(plain / bench.SIDECAR)        # a plain run (no extras) leaves no sidecar behind
     full["scaling_note"] = "z" * 5000
     with pytest.raises(SystemExit):
         bench.emit(full, stream=io.StringIO())
@@ -98,8 +103,36 @@ def test_roofline_is_rederivable_from_the_committed_counters():
 def test_bench_flags_parse():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--restarts", "--restarts-total", "--single-process", "--dry-launch"):
+    for flag in ("--gpus", "--steps", "--warmup", "--restarts", "--restarts-total", "--single-process", "--dry-launch", "--full", "--dump-outputs"):
         assert flag in out.stdout
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and "--steps" in out.stderr
+
+
+def test_dump_outputs_writes_the_last_step_within_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    R, n = 12, 50
+    pos = torch.stack([torch.randperm(n, generator=torch.Generator().manual_seed(r)) for r in range(R)]).to(torch.int32)
+    cost = torch.arange(R, dtype=torch.float32) + 0.5
+    stats = torch.arange(R * 16, dtype=torch.int64).reshape(R, 16)
+    bench.dump_outputs(str(tmp_path / "all"), 7, pos, cost, stats, pos[3], 3.5, 3)
+    d = tmp_path / "all"
+    assert sorted(p.name for p in d.iterdir()) == ["best.npy", "best_tour.npy", "costs.npy", "descent_stats.npy", "tours.npy"]
+    for p in d.iterdir():
+        assert np.load(p).dtype in (np.float32, np.float64), p.name
+    assert np.array_equal(np.load(d / "tours.npy"), pos.numpy()) and np.array_equal(np.load(d / "costs.npy"), cost.numpy())
+    assert np.array_equal(np.load(d / "descent_stats.npy"), stats[:, :4].numpy()) and np.load(d / "best.npy").tolist() == [3.5, 3.0]
+    # past the limit: a fixed sample of tour rows, the same on every run, listed in tour_rows.npy
+    monkeypatch.setattr(bench, "DUMP_LIMIT", (1 << 20) + 5 * 4 * n)
+    for k in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / k), 7, pos, cost, stats, pos[3], 3.5, 3)
+    rows = np.load(tmp_path / "a" / "tour_rows.npy")
+    assert len(rows) == 5 and np.array_equal(rows, np.load(tmp_path / "b" / "tour_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "tours.npy"), pos.numpy()[rows.astype(int)])
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= bench.DUMP_LIMIT
 
 
 def _bare_env():
