@@ -313,6 +313,16 @@ int tl_build_candidates(tl_ctx *ctx, const float *xy, uint32_t n, uint32_t k, ui
 int tl_nearest_neighbor(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, uint32_t n_nearest,
                         uint32_t *out_pos, float *out_cost);
 
+/* ---- greedy-edge construction: replaces greedy_edge::solve (greedy_edge.rs:21-65, graph.rs:54-196) ---- */
+/* Every edge i < j in ascending f32::total_cmp order of its length (ties: (i, j) ascending — the reference's unstable sort leaves
+ * that order open), accepted unless an endpoint has degree 2 or it closes a cycle before n - 1 edges are in, until n edges are in;
+ * the cycle is walked from position 0 along its earlier-accepted edge.  *out_cost is tour_length of that path (the closing edge
+ * first, sequential f32).  n <= 2: the identity.  Argument convention of tl_nearest_neighbor (dm_packed NULL: EUC_2D from xy).
+ * n <= 65 535 (positions are 16-bit in the sort keys; TL_ERR_UNSUPPORTED beyond).  stats (optional): sweeps = bands of sorted edges,
+ * candidates = edges the selection examined, moves = n. */
+int tl_greedy_edge(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, uint32_t *out_pos, float *out_cost,
+                   tl_stats *stats);
+
 /* ---- multi-start 2-opt (north-star config 4; no counterpart in the reference) ---------------- */
 /* Runs restarts [first, first+count) — restart r starts from the Fisher–Yates permutation drawn
  * from splitmix64(seed + r) (specification: DESIGN.md / oracle tlo_restart_perm) — one descent per

@@ -4,7 +4,7 @@
 //!   `two_opt::solve`        (src/tsp/two_opt.rs:7-67)
 //!   `three_opt::solve`      (src/tsp/three_opt.rs:16-51)
 //!   `lin_kernighan::solve`  (src/tsp/lin_kernighan.rs:35-100)
-//!   `or_opt::solve`, `nearest_neighbor::solve`, `DistanceMatrix::build`
+//!   `or_opt::solve`, `nearest_neighbor::solve`, `greedy_edge::solve`, `DistanceMatrix::build`
 //! of the `teeline` crate.  This crate knows nothing about `teeline`'s types (no dependency cycle): tours are
 //! POSITIONS (indices into the city array), coordinates are `[x0, y0, x1, y1, ...]`, the optional matrix is the
 //! reference's packed strict lower triangle (`DistanceMatrix::distances()`, distance_matrix.rs:171-173).
@@ -87,6 +87,8 @@ unsafe extern "C" {
              out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats) -> c_int;
     fn tl_nearest_neighbor(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, n_nearest: u32,
                            out_pos: *mut u32, out_cost: *mut f32) -> c_int;
+    fn tl_greedy_edge(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
+                      stats: *mut Stats) -> c_int;
     fn tl_two_opt_multistart_devices(ctxs: *const *mut TlCtx, n_ctxs: c_int, xy: *const f32, n: u32, seed: u64, first: u32, count: u32,
                                      mode: c_int, out_best_pos: *mut u32, out_best_cost: *mut f32, out_best_restart: *mut u32,
                                      out_costs: *mut f32, stats: *mut Stats) -> c_int;
@@ -403,6 +405,16 @@ impl Context {
         let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
         // SAFETY: as in two_opt.
         let rc = unsafe { tl_nearest_neighbor(self.raw, xy.as_ptr(), opt_ptr(dm_packed), n, n_nearest, t.pos.as_mut_ptr(), &mut t.cost) };
+        self.check(rc).map(|_| t)
+    }
+
+    /// `greedy_edge::solve` (greedy_edge.rs:21-65): every edge in ascending length order (ties: (i, j) ascending), n <= 65 535.
+    pub fn greedy_edge(&self, xy: &[f32], dm_packed: Option<&[f32]>) -> Result<Tour, Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, None);
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        // SAFETY: as in two_opt.
+        let rc = unsafe { tl_greedy_edge(self.raw, xy.as_ptr(), opt_ptr(dm_packed), n, t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats) };
         self.check(rc).map(|_| t)
     }
 }

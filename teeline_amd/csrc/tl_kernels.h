@@ -330,4 +330,27 @@ hipError_t launch_selftest_sqrt(uint32_t first_bits, uint64_t count, unsigned lo
 hipError_t launch_tour_length(const float2 *xy, const float *dm, uint32_t n, const uint32_t *perm,
                               float *out_cost, hipStream_t s);
 
+// greedy_edge.hip — greedy-edge construction in bands of at most `cap` sorted keys
+struct GreedyWs {
+    uint64_t *keys;       // [cap] the band's keys
+    uint32_t *hist;       // [4096] digit histogram
+    uint32_t *state;      // accepted edges, edges examined (u64), keys in the band, free cities
+    uint16_t *end;        // [n] fragment-end table between bands
+    uint16_t *free;       // [n] the free cities (degree < 2), position order
+    uint32_t *slots;      // [n][2] both neighbours of a city in acceptance order
+    uint32_t *succ[2];    // [2n] list ranking of the directed arcs (double-buffered)
+    uint32_t *dte[2];
+    uint32_t cap;
+};
+uint32_t greedy_band_cap(int lds_bytes);  // keys per band: a power of two whose keys fit one workgroup's LDS (16 384 on 160 KB)
+size_t greedy_ws_bytes(uint32_t n, uint32_t cap);
+GreedyWs greedy_ws_layout(void *ws, uint32_t n, uint32_t cap);
+hipError_t launch_greedy_init(const GreedyWs &w, uint32_t n, hipStream_t s);
+hipError_t launch_greedy_hist(const GreedyWs &w, const float2 *xy, const float *dm, uint32_t f, uint64_t t_prev, uint64_t prefix,
+                              uint32_t shift, uint32_t width, int blocks, hipStream_t s);
+// compact the keys in (t_lo, t_hi], sort them, walk them
+hipError_t launch_greedy_band(const GreedyWs &w, const float2 *xy, const float *dm, uint32_t n, uint32_t f, uint64_t t_lo, uint64_t t_hi,
+                              int blocks, hipStream_t s);
+hipError_t launch_greedy_path(const GreedyWs &w, uint32_t n, uint32_t *out_pos, hipStream_t s);
+
 }  // namespace tl
