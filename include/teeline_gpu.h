@@ -134,6 +134,8 @@ typedef enum tl_mode {
 /* matrix layouts for tl_dm_build */
 #define TL_DM_PACKED_LOWER 0 /* reference layout, n(n-1)/2 floats (distance_matrix.rs:122-153) */
 #define TL_DM_FULL 1         /* n x n row-major, zero diagonal (coalesced row gathers)           */
+/* TL_DM_FULL entry (i, j) is bit for bit the packed entry at (max(i, j), min(i, j)), i.e. d(xy[max], xy[min]) — for GEO too —
+ * and the diagonal is +0.0 whatever the coordinates (a NaN point included). */
 
 /* distance function for tl_dm_build */
 #define TL_DIST_EUC2D 0 /* kdtree.rs:291-295            */
@@ -204,7 +206,9 @@ int tl_dm_build(tl_ctx *ctx, const float *xy, uint32_t n, int dist, int layout, 
 
 /* Does dm_packed hold exactly (bit for bit) the EUC_2D distances of xy?  The reference's DistanceMatrix does not keep its
  * DistanceType (distance_matrix.rs:86-93); a shim that only has `problem.distances.distances()` asks here once and then
- * passes dm_packed = NULL (coordinate kernels, same results) when *is_euc2d comes back 1.  Costs one upload of the matrix. */
+ * passes dm_packed = NULL (coordinate kernels, same results) when *is_euc2d comes back 1.  Costs one upload of the matrix.
+ * The comparison is on bit patterns, with one exception: a NaN entry matches a computed NaN whatever the payloads.  So -0.0 where
+ * the computed distance is +0.0 reads as not EUC_2D (the conservative answer: the matrix kernels then run on it). */
 int tl_dm_is_euc2d(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, int *is_euc2d);
 
 /* ---- tour cost: replaces DistanceMatrix::tour_length_by_pos (distance_matrix.rs:235-245) ---- */
