@@ -80,7 +80,9 @@ typedef enum tl_mode {
 #define TL_FLAG_NO_PRUNE 1u
 /* Alternative forms of a kernel, kept as cross-checks of each other (the parity tests run every form against the oracle):
  * results are identical, only speed changes.  The library never reads the environment. */
-#define TL_FLAG_2OPT_FORCE_HBM (1u << 1)   /* tl_two_opt: the HBM-resident REF_ORDER variant (n > LDS limit) at every n      */
+#define TL_FLAG_2OPT_FORCE_HBM (1u << 1)   /* tl_two_opt: the HBM-resident REF_ORDER variant (n > LDS limit) at every n; also sends
+                                              tl_two_opt_multistart, tl_two_opt_multistart_devices (the flag of ctxs[0] decides) and the
+                                              coordinate form of tl_two_opt_population through their beyond-the-LDS branch at every n >= 4 */
 #define TL_FLAG_LK_ONE_WORKGROUP (1u << 2) /* tl_lk: the whole ILS in one persistent workgroup instead of chip-wide scans  */
 #define TL_FLAG_KNN_BRUTE (1u << 10)       /* candidate lists: brute-force scan (sixteen lanes per city) in (distance, position)
                                               order instead of the kd-tree walk — the same lists unless two candidates of a city
@@ -332,15 +334,21 @@ int tl_greedy_edge(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_
  * from splitmix64(seed + r) (specification: DESIGN.md / oracle tlo_restart_perm) — one descent per
  * workgroup, all concurrently.  Returns the best tour of this shard; out_costs (count floats,
  * optional) gets every restart's final cost.  Ranks shard [0,R) between themselves and min-reduce
- * tl_pack_cost_key(best_cost, best_restart) with RCCL. */
+ * tl_pack_cost_key(best_cost, best_restart) with RCCL.
+ * Beyond tl_two_opt_lds_max_n (or with TL_FLAG_2OPT_FORCE_HBM) the restarts run ONE AFTER THE OTHER through the HBM form:
+ * the same tours, costs and counters; stats->kernel_ms is then the sum of the descents' device times. */
 int tl_two_opt_multistart(tl_ctx *ctx, const float *xy, uint32_t n, uint64_t seed, uint32_t first,
                           uint32_t count, int mode, uint32_t *out_best_pos, float *out_best_cost,
                           uint32_t *out_best_restart, float *out_costs, tl_stats *stats);
 /* The same job over several devices of one node from ONE process (the reference is single-process; SURVEY.md §8(b)
  * proposed tl_multistart_two_opt(..., n_gpus, ...)): ctxs holds one context per device, each from tl_create(device, ...).
  * Restarts [first, first+count) are dealt in contiguous blocks (the first count % n_ctxs contexts take one more), all
- * shards run concurrently, the winner is the minimum packed key over the shards — results do not depend on n_ctxs.
- * Errors are reported on ctxs[0].  stats->kernel_ms is the slowest shard's device time.
+ * shards run concurrently, the winner is the minimum packed key over the shards (equal costs: the lower restart) — results
+ * do not depend on n_ctxs.  Errors are reported on ctxs[0].  stats->kernel_ms is the slowest shard's device time.
+ * Beyond tl_two_opt_lds_max_n (or with TL_FLAG_2OPT_FORCE_HBM on ctxs[0]) the shards do NOT run concurrently: every descent goes
+ * through the HBM form and is polled on the calling thread, shard after shard, restart after restart.  Results are the same;
+ * stats->kernel_ms is still the slowest shard's — the largest of the shards' summed device times — while total_ms covers all
+ * of them, so several devices give no speed-up on this path.
  * tl_multistart_shard: that deal as a host-only query (no context) — block `part` of `parts`; the ranks of a multi-process job
  * (bench.py, teeline_amd/host/multistart.py shard_total) use the same map. */
 int tl_multistart_shard(uint32_t first, uint32_t count, int parts, int part, uint32_t *shard_first, uint32_t *shard_count);
@@ -353,7 +361,8 @@ uint64_t tl_pack_cost_key(float cost, uint32_t restart);
  * REF_ORDER descent, one workgroup per tour, all concurrently; tour r of out_pos / out_costs equals what
  * tl_two_opt returns for it alone (two_opt.rs:7-67 with init_tour = Some(tour r)).  The reference has no
  * batch form: its callers loop over two_opt::solve (the north-star's GA refinement would, too).
- * dm_packed as in tl_two_opt.  Beyond tl_two_opt_lds_max_n (coordinates) the tours run one after the other through the HBM form. */
+ * dm_packed as in tl_two_opt.  Beyond tl_two_opt_lds_max_n, or with TL_FLAG_2OPT_FORCE_HBM (coordinates only), the tours run one after
+ * the other through the HBM form; stats->kernel_ms is then the sum of the descents' device times. */
 int tl_two_opt_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed,
                           const uint32_t *init_pos, uint32_t count, uint32_t *out_pos, float *out_costs,
                           tl_stats *stats);
@@ -383,6 +392,9 @@ int tl_dm_build_dev(tl_ctx *ctx, const float *d_xy, uint32_t n, int dist, int la
 /* Diagnostics: the 16 kernel-side counters of descent 0 of the most recent tl_two_opt / tl_two_opt_trace / tl_two_opt_population /
  * tl_two_opt_multistart call of this context (host-buffer entries; words 0-4: sweeps, moves, reversed elements, status, steps; the
  * rest is per kernel — matrix form: 5 = steps of sweeps run on the lists, 6 = such sweeps, 7 = their rows that walked the matrix rows).
+ * TL_ERR_BADARG (with a message) whenever the context does not hold such counters: no 2-opt call yet; the most recent one ran the
+ * HBM form or TL_MODE_BEST_SWEEP (no kernel-side counters); or the buffer has been used since by tl_lk_trace / tl_lk_live (their
+ * snapshot distances) or tl_two_opt_batch_dev (asynchronous, possibly still writing).
  * Not part of the reference's interface; tests and timing scripts read which form ran from it. */
 int tl_two_opt_last_counters(tl_ctx *ctx, uint64_t out[16]);
 

@@ -16,7 +16,7 @@ TL_ERR_BADARG, TL_ERR_REF_PANICS, TL_ERR_NO_DEVICE, TL_ERR_HIP = -1, -2, -3, -4
 TL_ERR_NOMEM, TL_ERR_UNSUPPORTED, TL_ERR_NO_CONVERGE, TL_ERR_BUSY = -5, -6, -7, -8
 TL_MODE_REF_ORDER, TL_MODE_BEST_SWEEP = 0, 1
 TL_FLAG_NONE, TL_FLAG_NO_PRUNE = 0, 1
-# alternative kernel forms (identical results; cross-checks of each other)
+# alternative kernel forms (identical results; cross-checks of each other); _2OPT_FORCE_HBM also routes the multi-start / population entries
 TL_FLAG_2OPT_FORCE_HBM, TL_FLAG_LK_ONE_WORKGROUP, TL_FLAG_LK_NO_SPLIT, TL_FLAG_LK_SPLIT2 = 1 << 1, 1 << 2, 1 << 3, 1 << 4
 TL_FLAG_LK_NO_SUBCHAINS, TL_FLAG_KNN_4LANES, TL_FLAG_KNN_1LANE = 1 << 5, 1 << 6, 1 << 7
 TL_FLAG_KNN_BRUTE = 1 << 10  # candidate lists by brute-force scan instead of the kd-tree walk

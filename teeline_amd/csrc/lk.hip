@@ -953,8 +953,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
             }
         }
         return;
-    
-        return;
     }
     LkView V{G.xy, G.cand, G.next, G.k, G.max_depth};
     const bool got = G.split_levels == 3u ? lk_subsearch3<LkView>(V, chain, clen, p1, t2, p2, g0, q1, s1, s2)

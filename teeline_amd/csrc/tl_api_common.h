@@ -41,6 +41,9 @@ struct tl_ctx {
     hipStream_t ws_stream = nullptr;
     bool ws_pending = false;
     bool in_callback = false;  // a tl_lk_live callback of this context is running: any entry into this context from inside it is refused
+    // out_stats holds the counters of a finished host-buffer 2-opt call (tl_two_opt_last_counters).  The buffer is also the f32 snapshot
+    // ring of tl_lk_trace / tl_lk_live and is written behind the caller's back by tl_two_opt_batch_dev: every such user clears this.
+    bool stats_valid = false;
     int cus = 0, lds_bytes = 0;
     std::string arch;
     std::string err;
@@ -84,6 +87,14 @@ struct CtxUse {
     }
     CtxUse(const CtxUse &) = delete;
     CtxUse &operator=(const CtxUse &) = delete;
+};
+// Around a tl_lk_live callback: while it runs, CtxUse refuses every entry into this context from the owning thread.
+struct InCallback {
+    tl_ctx *c;
+    explicit InCallback(tl_ctx *c_) : c(c_) { c->in_callback = true; }
+    ~InCallback() { c->in_callback = false; }
+    InCallback(const InCallback &) = delete;
+    InCallback &operator=(const InCallback &) = delete;
 };
 #define TL_ENTER(c)      \
     CtxUse tl_use_((c)); \

@@ -309,6 +309,7 @@ static int lk_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed
         G.nx = (float4 *)(w + o_pk_n);
     }
     if (snap_dev) {
+        c->stats_valid = false;  // out_stats becomes the snapshots' f32 distances
         G.snap = (uint32_t *)c->out_pos.p;
         G.snap_dist = (float *)c->out_stats.p;
         G.snap_cap = snap_cap;
@@ -346,9 +347,8 @@ static int lk_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed
                 if (e == hipSuccess) e = hipMemcpyAsync(&bd, G.snap_dist + at, 4, hipMemcpyDeviceToHost, c->stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
                 if (e != hipSuccess) break;
-                c->in_callback = true;
+                InCallback guard(c);
                 live(live_user, live_tour.data(), n, bd);
-                c->in_callback = false;
             }
             return e;
         };
@@ -462,9 +462,8 @@ static int lk_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed
                     if (e == hipSuccess) e = hipMemcpyAsync(&bd, G.snap_dist + at, 4, hipMemcpyDeviceToHost, c->stream);
                     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
                     if (e != hipSuccess) break;
-                    c->in_callback = true;   // an entry into THIS context from inside the callback gets TL_ERR_BUSY (CtxUse): the search owns it
+                    InCallback guard(c);  // an entry into THIS context from inside the callback gets TL_ERR_BUSY (CtxUse): the search owns it
                     live(live_user, live_tour.data(), n, bd);
-                    c->in_callback = false;
                 }
                 if (e != hipSuccess) {
                     rc_loop = fail(c, TL_ERR_HIP, "tl_lk_live: %s", hipGetErrorString(e));
@@ -512,6 +511,7 @@ static int lk_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed
             bd += sqrtf(sq);
         }
         if (live) {
+            InCallback guard(c);
             live(live_user, out_pos, n, bd);
         } else {
             if (snap_len) *snap_len = 1;

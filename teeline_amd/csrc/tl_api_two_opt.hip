@@ -13,8 +13,9 @@ using namespace tlapi;
                                 // cost 3-20 % more than they save, n = 532: even, n = 1 002: -33 % from the NN tour; scripts/timing_dm_late.py)
 #endif
 #ifndef TL_DM_LONG_MAX
-#define TL_DM_LONG_MAX 1024u  // ... a sweep runs on them while at most this many cities have a tour edge beyond their 16th distance (the descent's list holds 1024)
+#define TL_DM_LONG_MAX TL_DM_LONG_CAP  // ... a sweep runs on them while at most this many cities have a tour edge beyond their 16th distance (all the descent's list holds)
 #endif
+static_assert((TL_DM_LONG_MAX) <= tl::kDmLongCap, "TL_DM_LONG_MAX exceeds TL_DM_LONG_CAP: a late sweep would read the descent's list of long cities past its end");
 #ifndef TL_DM_MOVES_DIV
 #define TL_DM_MOVES_DIV 4000u  // ... and the sweep before it applied at most n^2 / 4000 moves: on the lists a sweep costs ~n rows + a step per move, in the
 #endif                         // other block shapes ~n^2 candidates (measured best at n = 1002 / 2000 / 3000: n / 4, n, n; scripts/timing_dm_late_knobs.py)
@@ -60,6 +61,7 @@ static int two_opt_enqueue(tl_ctx *c, const float2 *d_xy, const float *d_dm, uin
         return fail(c, TL_ERR_UNSUPPORTED, "two_opt (on-the-fly form): n=%u exceeds the LDS-resident limit %u", n, lds_max_n(c->lds_bytes));
     }
     c->ev_valid = false;
+    c->stats_valid = false;  // out_stats is about to be written (by the caller's own buffer or ours): the host-buffer entries set it after their synchronise
     {   // nl / fx / dmfull may still be read by an asynchronous batch this context enqueued on another stream
         int rco;
         if ((rco = ws_order(c, s))) return rco;
@@ -82,10 +84,10 @@ static int two_opt_enqueue(tl_ctx *c, const float2 *d_xy, const float *d_dm, uin
             if ((rc2 = ensure(c, c->dmx, two_opt_ref_dm_late_work_bytes(n, count)))) return rc2;  // (not c->work: tl_two_opt_trace keeps the move log there)
             A.work = (uint32_t *)c->dmx.p;
             HIPCHK(c, launch_dm_lists_build(A.dm_full, n, (unsigned char *)c->dmfull.p + full_bytes, &A.dml, s));
-            A.dml.long_max = (c->flags & TL_FLAG_2OPT_NL_ALWAYS) ? 1024u : (uint32_t)TL_DM_LONG_MAX;
+            A.dml.long_max = (c->flags & TL_FLAG_2OPT_NL_ALWAYS) ? kDmLongCap : (uint32_t)(TL_DM_LONG_MAX);
             A.dml.moves_max = (c->flags & TL_FLAG_2OPT_NL_ALWAYS) ? 0xFFFFFFFFu : (uint32_t)((uint64_t)n * n / TL_DM_MOVES_DIV > 8u ? (uint64_t)n * n / TL_DM_MOVES_DIV : 8u);
 #ifdef TL_TUNE  // tuning builds only: the product library never reads the environment
-            if (const char *e = getenv("TL_DM_LONG_MAX")) A.dml.long_max = (uint32_t)atoi(e);
+            if (const char *e = getenv("TL_DM_LONG_MAX")) A.dml.long_max = (uint32_t)atoi(e);  // (beyond kDmLongCap the kernel clamps it)
             if (const char *e = getenv("TL_DM_MOVES_MAX")) A.dml.moves_max = (uint32_t)atoi(e);
 #endif
         }
@@ -141,7 +143,9 @@ extern "C" int tl_two_opt_last_counters(tl_ctx *c, uint64_t out[16])
     TL_ENTER(c);
     if (!c || !out) return fail(c, TL_ERR_BADARG, "tl_two_opt_last_counters: NULL argument");
     static_assert(TL_STATS_STRIDE == 16, "the header documents 16 words");
-    if (!c->out_stats.p || c->out_stats.cap < (size_t)TL_STATS_STRIDE * 8) return fail(c, TL_ERR_BADARG, "tl_two_opt_last_counters: no 2-opt call on this context yet");
+    if (!c->stats_valid || !c->out_stats.p || c->out_stats.cap < (size_t)TL_STATS_STRIDE * 8)
+        return fail(c, TL_ERR_BADARG, "tl_two_opt_last_counters: the context holds no counters of a finished host-buffer 2-opt call (none yet, the last one ran a "
+                                      "form without kernel-side counters, or tl_lk_trace / tl_lk_live / tl_two_opt_batch_dev have used the buffer since)");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpyAsync(out, c->out_stats.p, (size_t)TL_STATS_STRIDE * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -216,11 +220,13 @@ static int two_opt_best_sweep(tl_ctx *c, const float *xy, uint32_t n, const floa
                               uint32_t *out_pos, float *out_cost, tl_stats *stats);
 
 // REF_ORDER for n beyond the LDS-resident kernel: tour state in HBM, scan spread over the chip (two_opt_large.hip)
+// xy == NULL: the instance already lies in c->xy (hbm_upload_xy: the batch entries upload it once, not once per descent)
 static int two_opt_ref_large(tl_ctx *c, const float *xy, uint32_t n, const uint32_t *init_pos, uint32_t *out_pos, float *out_cost,
                              tl_stats *stats)
 {
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(c, hipSetDevice(c->device));
+    c->stats_valid = false;  // (this form keeps its counters in the workspace: nothing for tl_two_opt_last_counters)
     int rc;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const uint32_t n_pad = ((n + 64u + 63u) / 64u) * 64u, ntile_cap = (((n_pad >> 6) + 63u) / 64u) * 64u;
@@ -234,7 +240,7 @@ static int two_opt_ref_large(tl_ctx *c, const float *xy, uint32_t n, const uint3
         for (uint32_t i = 0; i < n; ++i) ident[i] = i;
         init_pos = ident.data();
     }
-    HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    if (xy) HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(w + o_perm, init_pos, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     LargeTwoOptArgs A{};
@@ -279,6 +285,20 @@ static int two_opt_ref_large(tl_ctx *c, const float *xy, uint32_t n, const uint3
     }
     return TL_OK;
 }
+
+// the instance into c->xy, once, for the two_opt_ref_large calls of a batch (the first of them waits for the copy)
+static int hbm_upload_xy(tl_ctx *c, const float *xy, uint32_t n)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->xy, (size_t)n * 8))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    return TL_OK;
+}
+
+// the batch entries' branch through the HBM form: beyond the LDS-resident descent, or wherever TL_FLAG_2OPT_FORCE_HBM asks for it
+// (n == 3 has no candidate: the LDS kernel's empty descent serves it)
+static bool batch_runs_hbm_form(const tl_ctx *c, uint32_t n) { return n > lds_max_n(c->lds_bytes) || ((c->flags & TL_FLAG_2OPT_FORCE_HBM) && n >= 4u); }
 
 extern "C" int tl_two_opt(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, int mode,
                           uint32_t *out_pos, float *out_cost, tl_stats *stats)
@@ -329,6 +349,7 @@ extern "C" int tl_two_opt(tl_ctx *c, const float *xy, uint32_t n, const float *d
     HIPCHK(c, hipMemcpyAsync(&cost, c->out_cost.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(raw, c->out_stats.p, TL_STATS_STRIDE * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->stats_valid = true;
     if (raw[3] == 2) return fail(c, TL_ERR_BADARG, "two_opt: the initial tour holds a position >= n");
     if (raw[3] != 0) return fail(c, TL_ERR_NO_CONVERGE, "two_opt: sweep cap reached");
     if (out_cost) *out_cost = cost;
@@ -387,6 +408,7 @@ extern "C" int tl_two_opt_trace(tl_ctx *c, const float *xy, uint32_t n, const fl
     HIPCHK(c, hipMemcpyAsync(&cost, c->out_cost.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(raw, c->out_stats.p, TL_STATS_STRIDE * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->stats_valid = true;
     if (raw[3] == 2) return fail(c, TL_ERR_BADARG, "two_opt: the initial tour holds a position >= n");
     if (raw[3] != 0) return fail(c, TL_ERR_NO_CONVERGE, "two_opt: sweep cap reached");
     *log_len = (uint32_t)raw[15];  // words: moves applied + one mark per sweep after the first; more than log_cap: the log holds the first log_cap
@@ -436,6 +458,7 @@ static int multistart_finish(tl_ctx *c, uint32_t n, uint32_t first, uint32_t cou
     HIPCHK(c, hipMemcpyAsync(costs, c->out_cost.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(raw, c->out_stats.p, (size_t)count * TL_STATS_STRIDE * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->stats_valid = true;
     for (uint32_t r = 0; r < count; ++r) {
         if (raw[TL_STATS_STRIDE * r + 3] != 0) return fail(c, TL_ERR_NO_CONVERGE, "two_opt: sweep cap reached in restart %u", first + r);
         const uint64_t k = tl_pack_cost_key(costs[r], first + r);
@@ -581,35 +604,44 @@ extern "C" int tl_two_opt_multistart_devices(tl_ctx *const *ctxs, int n_ctxs, co
     std::vector<Shard> shard((size_t)n_ctxs);
     for (int d = 0; d < n_ctxs; ++d) (void)tl_multistart_shard(first, count, n_ctxs, d, &shard[d].first, &shard[d].count);
     int rc;
-    if (n > lds_max_n(c0->lds_bytes)) {
-        // beyond the LDS-resident descent (round 5): the restarts one after the other through the HBM form, each
-        // shard on its own context — the same start permutations, so the same tours as a (hypothetical) batch would give
+    if (batch_runs_hbm_form(c0, n)) {
+        // beyond the LDS-resident descent (round 5), or TL_FLAG_2OPT_FORCE_HBM on ctxs[0]: the restarts one after the other
+        // through the HBM form, each shard on its own context — the same start permutations, so the same tours as a (hypothetical) batch
+        // would give.  The shards, too, run one after the other (two_opt_ref_large polls its descent on the calling thread): kernel_ms is
+        // the largest of the shards' summed device times — the slowest shard's, what devices side by side would wait for — and
+        // total_ms is the sum of all of them.
         if (mode != TL_MODE_REF_ORDER) return fail(c0, TL_ERR_UNSUPPORTED, "batch 2-opt supports TL_MODE_REF_ORDER only");
         std::vector<uint32_t> perm, pos(n), bestpos(n);
         uint64_t bestkey = ~0ull;
         tl_stats acc{};
         std::vector<float> costs(count);
-        for (int d = 0; d < n_ctxs; ++d)
-            for (uint32_t r = shard[d].first; r < shard[d].first + shard[d].count; ++r) {
+        for (int d = 0; d < n_ctxs; ++d) {
+            if (!shard[d].count) continue;
+            double shard_ms = 0;
+            rc = hbm_upload_xy(ctxs[d], xy, n);
+            for (uint32_t r = shard[d].first; rc == TL_OK && r < shard[d].first + shard[d].count; ++r) {
                 restart_perm_host(n, seed, r, perm);
                 float cst = 0.f;
                 tl_stats st1{};
-                if ((rc = two_opt_ref_large(ctxs[d], xy, n, perm.data(), pos.data(), &cst, &st1))) {
-                    if (d) fail(c0, rc, "device shard %d: %s", d, ctxs[d]->err.c_str());
-                    return rc;
-                }
+                if ((rc = two_opt_ref_large(ctxs[d], nullptr, n, perm.data(), pos.data(), &cst, &st1))) break;
                 costs[r - first] = cst;
                 acc.sweeps += st1.sweeps;
                 acc.moves += st1.moves;
                 acc.reversed += st1.reversed;
                 acc.candidates += st1.candidates;
-                acc.kernel_ms += st1.kernel_ms;
+                shard_ms += st1.kernel_ms;
                 const uint64_t key = tl_pack_cost_key(cst, r);
                 if (key < bestkey) {
                     bestkey = key;
                     bestpos = pos;
                 }
             }
+            if (rc) {
+                if (d) fail(c0, rc, "device shard %d: %s", d, ctxs[d]->err.c_str());
+                return rc;
+            }
+            acc.kernel_ms = shard_ms > acc.kernel_ms ? shard_ms : acc.kernel_ms;
+        }
         memcpy(out_best_pos, bestpos.data(), (size_t)n * 4);
         const uint32_t br = (uint32_t)(bestkey & 0xFFFFFFFFull);
         if (out_best_cost) *out_best_cost = costs[br - first];
@@ -725,13 +757,15 @@ extern "C" int tl_two_opt_population(tl_ctx *c, const float *xy, uint32_t n, con
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if (!dm_packed && n > lds_max_n(c->lds_bytes)) {
-        // beyond the LDS-resident descent: the tours one after the other through the HBM form (every individual's result equals tl_two_opt on it alone)
+    if (!dm_packed && batch_runs_hbm_form(c, n)) {
+        // beyond the LDS-resident descent, or TL_FLAG_2OPT_FORCE_HBM: the tours one after the other through the HBM form (every individual's
+        // result equals tl_two_opt on it alone); kernel_ms is the sum of the descents' device times
         tl_stats acc{};
+        if ((rc = hbm_upload_xy(c, xy, n))) return rc;
         for (uint32_t r = 0; r < count; ++r) {
             float cst = 0.f;
             tl_stats st1{};
-            if ((rc = two_opt_ref_large(c, xy, n, init_pos + (size_t)r * n, out_pos + (size_t)r * n, &cst, &st1))) return rc;
+            if ((rc = two_opt_ref_large(c, nullptr, n, init_pos + (size_t)r * n, out_pos + (size_t)r * n, &cst, &st1))) return rc;
             if (out_costs) out_costs[r] = cst;
             acc.sweeps += st1.sweeps;
             acc.moves += st1.moves;
@@ -767,6 +801,7 @@ extern "C" int tl_two_opt_population(tl_ctx *c, const float *xy, uint32_t n, con
     HIPCHK(c, hipMemcpyAsync(costs.data(), c->out_cost.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(raw.data(), c->out_stats.p, (size_t)count * TL_STATS_STRIDE * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->stats_valid = true;
     for (uint32_t r = 0; r < count; ++r)
         if (raw[TL_STATS_STRIDE * r + 3] != 0) return fail(c, TL_ERR_NO_CONVERGE, "two_opt: sweep cap reached in tour %u", r);
     if (out_costs) memcpy(out_costs, costs.data(), (size_t)count * 4);
@@ -786,6 +821,7 @@ static int two_opt_best_sweep(tl_ctx *c, const float *xy, uint32_t n, const floa
     if (n > 65535) return fail(c, TL_ERR_UNSUPPORTED, "TL_MODE_BEST_SWEEP: n=%u > 65535 (packed (i,j) key)", n);
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(c, hipSetDevice(c->device));
+    c->stats_valid = false;  // (this form keeps its counters in the workspace: nothing for tl_two_opt_last_counters)
     if (stats) memset(stats, 0, sizeof(*stats));
     int rc;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };

@@ -67,6 +67,12 @@ hipError_t launch_two_opt_nl_build(const float2 *xy, uint32_t n, void *ws, bool 
 // reverse relation, cut from the full matrix once per call and shared by every descent of the batch
 constexpr int kDmK = 16;     // nearest cities per city (the c side of a row: D[a][c] < D[a][b])
 constexpr int kDmInv = 48;   // reverse-list slots per city (the e side: D[b][e] < D[c][e]; lanes 16..63 of a row's pass)
+#ifndef TL_DM_LONG_CAP
+#define TL_DM_LONG_CAP 1024  // (256 / 512 / 1024 measured: n = 1 002 alike, n = 5 000 population 148 / 134 / 131 ms)
+#endif
+// cities with a tour edge beyond their kDmK-th distance a descent's list (LDS) can hold in its late sweeps.  ONE constant for the kernel
+// (two_opt_dm.hip) and for the host's threshold (tl_api_two_opt.hip: TL_DM_LONG_MAX <= this, by static_assert; the kernel clamps too)
+constexpr uint32_t kDmLongCap = TL_DM_LONG_CAP;
 struct DmLists {
     const uint16_t *id;       // [n][kDmK] nearest cities in (distance, id) order, the city itself excluded; nullptr = no lists
     const float *d;           // [n][kDmK] their distances
@@ -74,7 +80,7 @@ struct DmLists {
     const uint16_t *inv_id;   // [n][kDmInv] the cities that hold this one among their kDmK (0xFFFF: empty slot)
     const float *inv_d;       // [n][kDmInv] D[that city][this one]
     const uint32_t *inv_cnt;  // [n] entries offered (beyond kDmInv: the list is incomplete, the row walks the matrix row)
-    uint32_t long_max;        // a sweep runs on the lists while at most this many cities have a tour edge beyond their dk
+    uint32_t long_max;        // a sweep runs on the lists while at most this many cities have a tour edge beyond their dk (<= kDmLongCap)
     uint32_t moves_max;       // ... and the sweep before it applied at most this many moves
 };
 size_t dm_lists_ws_bytes(uint32_t n);

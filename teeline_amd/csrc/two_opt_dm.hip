@@ -37,10 +37,7 @@ constexpr uint32_t kDmChain = TL_DM_CHAIN;  // improving moves one wave may chai
 #endif
 constexpr size_t kDmWarmBytes = (size_t)TL_DM_WARM_MB << 20;  // matrices up to this size are read once at the start of a descent (L2 / MALL warm-up)
 constexpr uint32_t kDmXl = 32;        // ... and entries of a city's cached "nearer than its successor" record
-#ifndef TL_DM_LONG_CAP
-#define TL_DM_LONG_CAP 1024  // (256 / 512 / 1024 measured: n = 1 002 alike, n = 5 000 population 148 / 134 / 131 ms)
-#endif
-constexpr uint32_t kDmLongCap = TL_DM_LONG_CAP;  // cities with a tour edge beyond their kDmK-th distance a descent can hold (late sweeps)
+// (kDmLongCap, the size of a descent's list of long cities: tl_kernels.h — the host's threshold DmLists::long_max is bounded by it)
 #ifndef TL_DM_LATE_ROWS
 #define TL_DM_LATE_ROWS 2
 #endif
@@ -262,7 +259,7 @@ __global__ __launch_bounds__(kDmNT) void k_two_opt_ref_dm(TwoOptBatchArgs A)
         // on the lists a move is a whole step (two dependent look-ups and a barrier), in the other block shapes a hit-free sweep is
         // n / 16 steps: the lists take the sweeps that follow one with few moves (the first sweep: the long cities stand in for them)
         const uint32_t nl0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lctl[0]);
-        late = nl0 <= A.dml.long_max && (prev_moves == 0xFFFFFFFFu ? nl0 : prev_moves) <= A.dml.moves_max;
+        late = nl0 <= (A.dml.long_max < kDmLongCap ? A.dml.long_max : kDmLongCap) && (prev_moves == 0xFFFFFFFFu ? nl0 : prev_moves) <= A.dml.moves_max;
         if (late) ++n_late_sweeps;
     };
     if (LATE) {

@@ -56,3 +56,24 @@ def test_every_ds_min_is_drained_before_the_next_barrier(lib):
     if not os.path.exists(path):
         pytest.skip(f"{os.path.basename(path)} not built")
     assert B.verify_ds_min_waits(path) == []
+
+
+def _syntax_check_two_opt_api(*defines):
+    """hipcc over the one translation unit that holds the matrix form's host-side thresholds, host and gfx950 passes, no code generation"""
+    import subprocess
+    src = os.path.join(B.CSRC, "tl_api_two_opt.hip")
+    cmd = [B._hipcc()] + [f for f in B.FLAGS if f != "-shared"] + list(defines) + ["-I", os.path.join(B.ROOT, "include"), "-fsyntax-only", src]
+    return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+
+
+def test_long_list_threshold_beyond_the_kernels_capacity_does_not_compile():
+    # ADVICE r05: the host's TL_DM_LONG_MAX and the kernel's list of long cities (kDmLongCap, tl_kernels.h) were unrelated macros; a
+    # threshold beyond the list made late sweeps read it past its end.  One constant now, and the build refuses a larger threshold.
+    ok = _syntax_check_two_opt_api()
+    assert ok.returncode == 0, ok.stdout[-2000:]
+    ok = _syntax_check_two_opt_api("-DTL_DM_LONG_MAX=512")
+    assert ok.returncode == 0, ok.stdout[-2000:]
+    bad = _syntax_check_two_opt_api("-DTL_DM_LONG_MAX=2048")
+    assert bad.returncode != 0 and "TL_DM_LONG_MAX exceeds TL_DM_LONG_CAP" in bad.stdout, bad.stdout[-2000:]
+    small = _syntax_check_two_opt_api("-DTL_DM_LONG_CAP=256")  # the default threshold follows a smaller list
+    assert small.returncode == 0, small.stdout[-2000:]

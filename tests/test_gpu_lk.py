@@ -370,36 +370,56 @@ def test_progress_messages_arrive_while_the_search_runs(ctx):
     assert stamps[-1] - stamps[0] > 0.1 * run, (stamps[0] - t0, stamps[-1] - t0, run)  # ... and the others come spread over the run
 
 
-def test_live_callback_cannot_re_enter_its_own_context(ctx):
+@pytest.mark.parametrize("form", ["default", "one_workgroup", "ils_lds", "chip_wide"])
+def test_live_callback_cannot_re_enter_its_own_context(ctx, form):
     # the callback runs on the owning thread, so the owner guard used to let it back in — onto the stream and workspace of
     # the running search.  Now every entry into THIS context from inside the callback is TL_ERR_BUSY; another context is free; and the
-    # search's result is untouched.
+    # search's result is untouched.  Every form of the search hands its tours out through a callback of its own (the
+    # one-workgroup form's final message was outside the guard): the default form (the LDS ILS at this size), TL_FLAG_LK_ONE_WORKGROUP,
+    # TL_FLAG_LK_ILS_LDS and TL_FLAG_LK_CHIP_WIDE.
     import ctypes as C
     import teeline_amd as TA
     from teeline_amd import _capi
+    flags = {"default": None, "one_workgroup": TA.TL_FLAG_LK_ONE_WORKGROUP, "ils_lds": TA.TL_FLAG_LK_ILS_LDS, "chip_wide": TA.TL_FLAG_LK_CHIP_WIDE}[form]
     n = 400
     xy = O.synth_xy(n, seed=31)
     seen = []
     out = np.empty(n, dtype=np.uint32)
     cost, st = C.c_float(), _capi.TlStats()
-    with TA.Context(0) as other:
-        @_capi.LK_PROGRESS_FN
-        def cb(user, best_pos, nn, best_dist):
-            ms = C.c_double()
-            rc_same = ctx.lib.tl_last_kernel_ms(ctx.handle, C.byref(ms))
-            tmp = np.empty(n, dtype=np.uint32)
-            c2 = C.c_float()
-            rc_same2 = ctx.lib.tl_nearest_neighbor(ctx.handle, xy.ctypes.data_as(C.c_void_p), None, n, 3, tmp.ctypes.data_as(C.c_void_p), C.byref(c2))
-            rc_other = other.lib.tl_nearest_neighbor(other.handle, xy.ctypes.data_as(C.c_void_p), None, n, 3, tmp.ctypes.data_as(C.c_void_p), C.byref(c2))
-            seen.append((rc_same, rc_same2, rc_other))
-        o = _capi.TlLkOpts(40, 10, 5, 5)
-        ctx.check(ctx.lib.tl_lk_live(ctx.handle, xy.ctypes.data_as(C.c_void_p), n, None, None, C.byref(o), 9, out.ctypes.data_as(C.c_void_p), C.byref(cost),
+    own = None
+    if flags is not None:
+        try:
+            own = TA.Context(0, flags)
+        except TA.TeelineGpuError as e:
+            pytest.skip(f"the product build refuses this form's flag: {e}")
+    c = own or ctx
+    try:
+        with TA.Context(0) as other:
+            @_capi.LK_PROGRESS_FN
+            def cb(user, best_pos, nn, best_dist):
+                ms = C.c_double()
+                rc_same = c.lib.tl_last_kernel_ms(c.handle, C.byref(ms))
+                tmp = np.empty(n, dtype=np.uint32)
+                c2 = C.c_float()
+                rc_same2 = c.lib.tl_nearest_neighbor(c.handle, xy.ctypes.data_as(C.c_void_p), None, n, 3, tmp.ctypes.data_as(C.c_void_p), C.byref(c2))
+                ident = np.arange(n, dtype=np.uint32)
+                rc_same3 = c.lib.tl_tour_length(c.handle, xy.ctypes.data_as(C.c_void_p), None, n, ident.ctypes.data_as(C.c_void_p), C.byref(c2))
+                rc_other = other.lib.tl_nearest_neighbor(other.handle, xy.ctypes.data_as(C.c_void_p), None, n, 3, tmp.ctypes.data_as(C.c_void_p), C.byref(c2))
+                seen.append((rc_same, rc_same2, rc_same3, rc_other))
+            o = _capi.TlLkOpts(40, 10, 5, 5)
+            c.check(c.lib.tl_lk_live(c.handle, xy.ctypes.data_as(C.c_void_p), n, None, None, C.byref(o), 9, out.ctypes.data_as(C.c_void_p), C.byref(cost),
                                      C.byref(st), cb, None))
-    assert seen and all(s == (_capi.TL_ERR_BUSY, _capi.TL_ERR_BUSY, 0) for s in seen), seen[:4]
-    rc, oroute, ocost, ost = O.lin_kernighan_trace(xy, epochs=40, platoo_epochs=10, seed=9)[:4]
-    assert out.tolist() == oroute.tolist() and np.float32(cost.value).tobytes() == np.float32(ocost).tobytes()
-    ms = C.c_double()
-    assert ctx.lib.tl_last_kernel_ms(ctx.handle, C.byref(ms)) == 0          # ... and the context is usable again afterwards
+        assert seen and all(s == (_capi.TL_ERR_BUSY, _capi.TL_ERR_BUSY, _capi.TL_ERR_BUSY, 0) for s in seen), seen[:4]
+        rc, oroute, ocost, ost = O.lin_kernighan_trace(xy, epochs=40, platoo_epochs=10, seed=9)[:4]
+        assert out.tolist() == oroute.tolist() and np.float32(cost.value).tobytes() == np.float32(ocost).tobytes()
+        ms = C.c_double()
+        assert c.lib.tl_last_kernel_ms(c.handle, C.byref(ms)) == 0          # ... and the context is usable again afterwards
+        ident, length = np.arange(n, dtype=np.uint32), C.c_float()
+        c.check(c.lib.tl_tour_length(c.handle, xy.ctypes.data_as(C.c_void_p), None, n, ident.ctypes.data_as(C.c_void_p), C.byref(length)))
+        assert np.float32(length.value).tobytes() == np.float32(O.tour_length(xy, None, ident)).tobytes()
+    finally:
+        if own is not None:
+            own.close()
 
 
 def test_no_progress_messages_below_four_cities(ctx):
