@@ -329,6 +329,28 @@ int tl_nearest_neighbor(tl_ctx *ctx, const float *xy, const float *dm_packed, ui
 int tl_greedy_edge(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, uint32_t *out_pos, float *out_cost,
                    tl_stats *stats);
 
+/* ---- savings construction: replaces savings::solve (savings.rs:34-163 over graph.rs:98-196) ---- */
+/* tl_greedy_edge's selection and path under another order: every edge i < j by its saving s = (dh[i] + dh[j]) - d(i, j) — two f32
+ * operations in that order, dh[k] = d(hub, k), dh[hub] = +0.0 — DESCENDING under f32::total_cmp (-0.0 below +0.0, subnormals kept).
+ * Two orders the reference leaves open are fixed here:
+ *   ties  equal savings go in (i, j) ascending order (the reference's unstable sort leaves that order open);
+ *   NaN   a NaN saving of any sign or payload (inf - inf is -NaN on x86, +NaN on AArch64 and on the GPU, and total_cmp puts those
+ *         at opposite ends) is ONE value that ranks below every number, after -inf, ties by (i, j): such an edge is taken only
+ *         when nothing else is left.
+ * Hub (tl_savings_hub, savings.rs:94-117): the position nearest the centroid of xy, all in f32 — sequential left-to-right sums of
+ * x and of y, each divided by (float)n, d2 = dx*dx + dy*dy unfused, the first position with d2 < best from best = 0, d2 = FLT_MAX;
+ * NaN or inf coordinates therefore give 0, and so does n = 0.  It is host code, O(n), and always reads the coordinates, also where
+ * the distances are a GEO or EXPLICIT matrix.
+ * tl_savings: hub = TL_SAVINGS_HUB_AUTO computes tl_savings_hub(xy); any other hub >= n is TL_ERR_BADARG.  xy is required when the
+ * hub is AUTO or dm_packed is NULL (dm_packed NULL: EUC_2D from xy; otherwise every distance is read from the packed matrix).
+ * *out_hub (optional) receives the hub used.  n <= 2: the identity.  *out_cost is tour_length of the path.  n <= 65 535 (positions
+ * are 16-bit in the sort keys; TL_ERR_UNSUPPORTED beyond).  stats (optional) as tl_greedy_edge's: sweeps = bands of sorted edges,
+ * candidates = edges the selection examined, moves = n. */
+#define TL_SAVINGS_HUB_AUTO 0xFFFFFFFFu
+int tl_savings_hub(const float *xy, uint32_t n, uint32_t *out_hub);
+int tl_savings(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, uint32_t hub, uint32_t *out_pos, float *out_cost,
+               uint32_t *out_hub, tl_stats *stats);
+
 /* ---- multi-start 2-opt (north-star config 4; no counterpart in the reference) ---------------- */
 /* Runs restarts [first, first+count) — restart r starts from the Fisher–Yates permutation drawn
  * from splitmix64(seed + r) (specification: DESIGN.md / oracle tlo_restart_perm) — one descent per

@@ -4,7 +4,7 @@
 //!   `two_opt::solve`        (src/tsp/two_opt.rs:7-67)
 //!   `three_opt::solve`      (src/tsp/three_opt.rs:16-51)
 //!   `lin_kernighan::solve`  (src/tsp/lin_kernighan.rs:35-100)
-//!   `or_opt::solve`, `nearest_neighbor::solve`, `greedy_edge::solve`, `DistanceMatrix::build`
+//!   `or_opt::solve`, `nearest_neighbor::solve`, `greedy_edge::solve`, `savings::solve`, `DistanceMatrix::build`
 //! of the `teeline` crate.  This crate knows nothing about `teeline`'s types (no dependency cycle): tours are
 //! POSITIONS (indices into the city array), coordinates are `[x0, y0, x1, y1, ...]`, the optional matrix is the
 //! reference's packed strict lower triangle (`DistanceMatrix::distances()`, distance_matrix.rs:171-173).
@@ -89,6 +89,9 @@ unsafe extern "C" {
                            out_pos: *mut u32, out_cost: *mut f32) -> c_int;
     fn tl_greedy_edge(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
                       stats: *mut Stats) -> c_int;
+    fn tl_savings_hub(xy: *const f32, n: u32, out_hub: *mut u32) -> c_int;
+    fn tl_savings(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, hub: u32, out_pos: *mut u32, out_cost: *mut f32,
+                  out_hub: *mut u32, stats: *mut Stats) -> c_int;
     fn tl_two_opt_multistart_devices(ctxs: *const *mut TlCtx, n_ctxs: c_int, xy: *const f32, n: u32, seed: u64, first: u32, count: u32,
                                      mode: c_int, out_best_pos: *mut u32, out_best_cost: *mut f32, out_best_restart: *mut u32,
                                      out_costs: *mut f32, stats: *mut Stats) -> c_int;
@@ -417,6 +420,34 @@ impl Context {
         let rc = unsafe { tl_greedy_edge(self.raw, xy.as_ptr(), opt_ptr(dm_packed), n, t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats) };
         self.check(rc).map(|_| t)
     }
+
+    /// `savings::solve` (savings.rs:34-82): every edge in descending order of its saving against the hub (ties: (i, j) ascending;
+    /// a NaN saving ranks below every number), n <= 65 535.  `hub`: a position, or `None` for the one nearest the centroid of `xy`
+    /// (`savings_hub`).  Returns the tour and the hub used.
+    pub fn savings(&self, xy: &[f32], dm_packed: Option<&[f32]>, hub: Option<u32>) -> Result<(Tour, u32), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, None);
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        let mut used = 0u32;
+        // SAFETY: as in two_opt; out_hub points at a live u32.
+        let rc = unsafe {
+            tl_savings(self.raw, xy.as_ptr(), opt_ptr(dm_packed), n, hub.unwrap_or(SAVINGS_HUB_AUTO), t.pos.as_mut_ptr(), &mut t.cost,
+                       &mut used, &mut t.stats)
+        };
+        self.check(rc).map(|_| (t, used))
+    }
+}
+
+/// `TL_SAVINGS_HUB_AUTO` (include/teeline_gpu.h)
+pub const SAVINGS_HUB_AUTO: u32 = 0xFFFF_FFFF;
+
+/// `hub_position` (savings.rs:94-117): the position nearest the centroid of `xy` (x0, y0, x1, y1, ...), in f32 throughout.  Host
+/// code: needs no context and no GPU.
+pub fn savings_hub(xy: &[f32]) -> u32 {
+    let mut hub = 0u32;
+    // SAFETY: xy holds 2 * n floats; out_hub points at a live u32.  The call cannot fail on non-null arguments.
+    let _ = unsafe { tl_savings_hub(xy.as_ptr(), (xy.len() / 2) as u32, &mut hub) };
+    hub
 }
 
 impl Drop for Context {

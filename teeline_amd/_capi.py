@@ -36,6 +36,7 @@ TL_FLAG_LK_SMALL = 1 << 9  # tl_lk: the LDS-resident single-workgroup form where
 TL_FLAG_COUNT_WORK = 1 << 8  # the LDS 2-opt kernel also counts the work of its cascade (stats words 5..8); ~8 % slower
 TL_DM_PACKED_LOWER, TL_DM_FULL = 0, 1
 TL_DIST_EUC2D, TL_DIST_GEO = 0, 1
+TL_SAVINGS_HUB_AUTO = 0xFFFFFFFF  # tl_savings: the hub is tl_savings_hub(xy)
 
 # every symbol include/teeline_gpu.h declares (tests/test_abi.py checks header <-> library <-> this list)
 SYMBOLS = [
@@ -46,7 +47,7 @@ SYMBOLS = [
     "tl_or_opt", "tl_or_opt_find_best_move", "tl_selftest_sqrt", "tl_two_opt_population", "tl_dm_is_euc2d",
     "tl_two_opt_multistart_devices", "tl_two_opt_trace", "tl_three_opt_trace", "tl_lk_trace", "tl_or_opt_trace",
     "tl_lk_live", "tl_two_opt_neighbour_lists", "tl_two_opt_plan", "tl_multistart_shard", "tl_two_opt_last_counters",
-    "tl_greedy_edge",
+    "tl_greedy_edge", "tl_savings_hub", "tl_savings",
 ]
 
 
@@ -128,6 +129,8 @@ def load():
     L.tl_build_candidates.argtypes = [vp, vp, u32, u32, vp]
     L.tl_nearest_neighbor.argtypes = [vp, vp, vp, u32, u32, vp, f32p]
     L.tl_greedy_edge.argtypes = [vp, vp, vp, u32, vp, f32p, C.POINTER(TlStats)]
+    L.tl_savings_hub.argtypes = [vp, u32, C.POINTER(u32)]
+    L.tl_savings.argtypes = [vp, vp, vp, u32, u32, vp, f32p, C.POINTER(u32), C.POINTER(TlStats)]
     L.tl_selftest_sqrt.argtypes = [vp, u32, u64, C.POINTER(u64), C.POINTER(u32)]
     L.tl_two_opt_plan.argtypes = [u32, u32, i32, i32, u32, C.POINTER(i32), C.POINTER(i32)]
     L.tl_multistart_shard.argtypes = [u32, u32, i32, i32, C.POINTER(u32), C.POINTER(u32)]

@@ -1,4 +1,5 @@
-// greedy_edge.hip — greedy-edge construction (reference: src/tsp/greedy_edge.rs:21-65 over graph.rs:54-196), DESIGN.md §4.11.
+// greedy_edge.hip — greedy-edge construction (reference: src/tsp/greedy_edge.rs:21-65 over graph.rs:54-196), DESIGN.md §4.11,
+// and savings construction (src/tsp/savings.rs:34-163: the same selection under another sort key), DESIGN.md §4.12.
 //
 // The reference sorts all n(n-1)/2 edges by f32::total_cmp of their length and walks them once (select_edges): an edge is skipped
 // if an endpoint already has degree 2, or if it would close a cycle before n - 1 edges are in.  Both rejections are final (degrees
@@ -14,6 +15,8 @@
 //
 // Key of the edge (i < j): (total-order key of d) << 32 | i << 16 | j — the reference's order with ties broken by (i, j) ascending
 // (its sort_unstable_by leaves that order open).  Positions fit 16 bits: n <= 65 535 (tl_greedy_edge refuses more).
+// Savings swaps the upper word for KeySavings' (below); nothing else of the band scheme depends on what the key orders by: both
+// rejections are final, degrees never fall, fragments never split.
 #include "tl_kernels.h"
 
 namespace tl {
@@ -31,10 +34,34 @@ __device__ __forceinline__ uint32_t total_key(float d)
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
+// Key policies: the upper 32 bits of an edge's sort key from its length d and its two endpoints (the lower 32 are i << 16 | j).
+// greedy-edge: ascending f32::total_cmp of the length
+struct KeyLength {
+    __device__ __forceinline__ uint32_t operator()(float d, uint32_t, uint32_t) const { return total_key(d); }
+};
+
+constexpr uint32_t kSavNanKey = 0xFF800001u;  // one past -inf's inverted key (~total_key(-inf) = 0xFF800000)
+
+// savings (savings.rs:136-163): s = (dh[i] + dh[j]) - d in two f32 operations in that order (the sum commutes bit for bit, so
+// which endpoint is i does not matter), DESCENDING f32::total_cmp — the inverted total-order key — with -0.0 and +0.0 distinct
+// and subnormals kept.  A NaN saving of any sign or payload (inf - inf is +NaN here and -NaN on x86; total_cmp would put them at
+// opposite ends) is ONE value that ranks below every number, after -inf: tested explicitly, never this device's default NaN.
+// What the host relies on (tl_api_greedy.hip) holds as for KeyLength: every key is > 0 (j >= 1 in the low bits), and no key is
+// all-ones (the largest upper word is kSavNanKey — ~total_key(s) of a non-NaN s is at most 0xFF800000 — and i < j <= 65 534 keeps
+// the low word below 0xFFFFFFFF too), so ~0 stays free as the sort's padding and as "every edge walked".
+struct KeySavings {
+    const float *__restrict__ dh;
+    __device__ __forceinline__ uint32_t operator()(float d, uint32_t i, uint32_t j) const
+    {
+        const float s = (dh[i] + dh[j]) - d;
+        return s != s ? kSavNanKey : ~total_key(s);
+    }
+};
+
 // Calls visit(key) for every pair a < b of the free list (positions free[a], free[b]), tile by tile over a grid-stride loop.
-template <bool DM, class Visit>
+template <bool DM, class Key, class Visit>
 __device__ __forceinline__ void for_each_pair(const float2 *__restrict__ xy, const float *__restrict__ dm, const uint16_t *__restrict__ free,
-                                              uint32_t f, Visit visit)
+                                              uint32_t f, Key key32, Visit visit)
 {
     const uint32_t nrt = (f + kGeRows - 1) / kGeRows, ncb = (f + kGeCols - 1) / kGeCols;
     const uint64_t tiles = (uint64_t)nrt * ncb;
@@ -53,7 +80,7 @@ __device__ __forceinline__ void for_each_pair(const float2 *__restrict__ xy, con
             float d;
             if (DM) d = dm[(uint64_t)j * (j - 1) / 2 + i];
             else d = dist(xy[pa], qb);
-            visit(((uint64_t)total_key(d) << 32) | ((uint64_t)i << 16) | (uint64_t)j);
+            visit(((uint64_t)key32(d, i, j) << 32) | ((uint64_t)i << 16) | (uint64_t)j);
         }
     }
 }
@@ -62,11 +89,11 @@ constexpr int kGeDigitBits = 12;
 constexpr int kGeBins = 1 << kGeDigitBits;
 
 // Histogram of digit (key >> shift) & (2^width - 1) over the pairs with key > t_prev whose bits above shift + width equal `prefix`.
-template <bool DM>
+template <bool DM, class Key>
 __global__ __launch_bounds__(kGeCols) void k_ge_hist(const float2 *__restrict__ xy, const float *__restrict__ dm,
                                                      const uint16_t *__restrict__ free, const uint32_t *__restrict__ state,
                                                      uint64_t t_prev, uint64_t prefix, uint32_t shift, uint32_t width,
-                                                     uint32_t *__restrict__ hist)
+                                                     uint32_t *__restrict__ hist, Key key32)
 {
     __shared__ uint32_t lh[kGeBins];
     for (int k = threadIdx.x; k < kGeBins; k += kGeCols) lh[k] = 0;
@@ -74,7 +101,7 @@ __global__ __launch_bounds__(kGeCols) void k_ge_hist(const float2 *__restrict__ 
     const uint32_t f = state[4];
     const uint32_t pshift = shift + width;
     const uint64_t mask = ((uint64_t)1 << width) - 1;
-    for_each_pair<DM>(xy, dm, free, f, [&](uint64_t key) {
+    for_each_pair<DM>(xy, dm, free, f, key32, [&](uint64_t key) {
         if (key > t_prev && (pshift >= 64 || (key >> pshift) == prefix)) atomicAdd(&lh[(key >> shift) & mask], 1u);
     });
     TL_SYNC();
@@ -83,13 +110,13 @@ __global__ __launch_bounds__(kGeCols) void k_ge_hist(const float2 *__restrict__ 
 }
 
 // Every pair key in (t_lo, t_hi], unordered; state[3] counts them (the host has sized the band: never more than cap)
-template <bool DM>
+template <bool DM, class Key>
 __global__ __launch_bounds__(kGeCols) void k_ge_compact(const float2 *__restrict__ xy, const float *__restrict__ dm,
                                                         const uint16_t *__restrict__ free, uint32_t *__restrict__ state,
-                                                        uint64_t t_lo, uint64_t t_hi, uint64_t *__restrict__ keys, uint32_t cap)
+                                                        uint64_t t_lo, uint64_t t_hi, uint64_t *__restrict__ keys, uint32_t cap, Key key32)
 {
     const uint32_t f = state[4];
-    for_each_pair<DM>(xy, dm, free, f, [&](uint64_t key) {
+    for_each_pair<DM>(xy, dm, free, f, key32, [&](uint64_t key) {
         if (key > t_lo && key <= t_hi) {
             const uint32_t at = atomicAdd(&state[3], 1u);
             if (at < cap) keys[at] = key;
@@ -221,6 +248,22 @@ __global__ __launch_bounds__(256) void k_ge_init(uint16_t *__restrict__ end_g, u
     if (k < 8) state[k] = k == 4 ? n : 0u;
 }
 
+// savings: dh[k] = d(hub, k), +0.0 at the hub itself (distance_by_pos's diagonal rule, also where the coordinates are inf or NaN)
+template <bool DM>
+__global__ __launch_bounds__(256) void k_sav_dh(const float2 *__restrict__ xy, const float *__restrict__ dm, uint32_t n, uint32_t hub,
+                                                float *__restrict__ dh)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= n) return;
+    float d = 0.f;
+    if (k != hub) {
+        const uint32_t i = k < hub ? k : hub, j = k < hub ? hub : k;
+        if (DM) d = dm[(uint64_t)j * (j - 1) / 2 + i];
+        else d = dist(xy[hub], xy[k]);
+    }
+    dh[k] = d;
+}
+
 constexpr uint32_t kGeEnd = 0xFFFFFFFFu;
 
 // Arc 2c + s runs from c to slots[2c + s]; its successor leaves that city by the other slot.  The arc whose successor would be
@@ -277,7 +320,7 @@ uint32_t greedy_band_cap(int lds_bytes)
 size_t greedy_ws_bytes(uint32_t n, uint32_t cap)
 {
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    return up((size_t)cap * 8) + up((size_t)kGeBins * 4) + 256 + 2 * up((size_t)n * 2) + 5 * up((size_t)n * 8);
+    return up((size_t)cap * 8) + up((size_t)kGeBins * 4) + 256 + 2 * up((size_t)n * 2) + 5 * up((size_t)n * 8) + up((size_t)n * 4);
 }
 
 GreedyWs greedy_ws_layout(void *ws, uint32_t n, uint32_t cap)
@@ -294,7 +337,8 @@ GreedyWs greedy_ws_layout(void *ws, uint32_t n, uint32_t cap)
     w.succ[0] = (uint32_t *)p, p += up((size_t)n * 8);
     w.succ[1] = (uint32_t *)p, p += up((size_t)n * 8);
     w.dte[0] = (uint32_t *)p, p += up((size_t)n * 8);
-    w.dte[1] = (uint32_t *)p;
+    w.dte[1] = (uint32_t *)p, p += up((size_t)n * 8);
+    w.dh = (float *)p;
     w.cap = cap;
     return w;
 }
@@ -305,27 +349,46 @@ hipError_t launch_greedy_init(const GreedyWs &w, uint32_t n, hipStream_t s)
     return hipGetLastError();
 }
 
+hipError_t launch_savings_dh(const GreedyWs &w, const float2 *xy, const float *dm, uint32_t n, uint32_t hub, hipStream_t s)
+{
+    if (dm) hipLaunchKernelGGL(k_sav_dh<true>, dim3((n + 255) / 256), dim3(256), 0, s, xy, dm, n, hub, w.dh);
+    else hipLaunchKernelGGL(k_sav_dh<false>, dim3((n + 255) / 256), dim3(256), 0, s, xy, dm, n, hub, w.dh);
+    return hipGetLastError();
+}
+
 hipError_t launch_greedy_hist(const GreedyWs &w, const float2 *xy, const float *dm, uint32_t f, uint64_t t_prev, uint64_t prefix,
-                              uint32_t shift, uint32_t width, int blocks, hipStream_t s)
+                              uint32_t shift, uint32_t width, int blocks, bool savings, hipStream_t s)
 {
     hipError_t e = hipMemsetAsync(w.hist, 0, (size_t)kGeBins * 4, s);
     if (e != hipSuccess) return e;
     const uint64_t tiles = (uint64_t)((f + kGeRows - 1) / kGeRows) * ((f + kGeCols - 1) / kGeCols);
     const int g = (int)(tiles < (uint64_t)blocks ? (tiles ? tiles : 1) : (uint64_t)blocks);
-    if (dm) hipLaunchKernelGGL(k_ge_hist<true>, dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_prev, prefix, shift, width, w.hist);
-    else hipLaunchKernelGGL(k_ge_hist<false>, dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_prev, prefix, shift, width, w.hist);
+    const KeySavings ks{w.dh};
+    if (savings) {
+        if (dm) hipLaunchKernelGGL((k_ge_hist<true, KeySavings>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_prev, prefix, shift, width, w.hist, ks);
+        else hipLaunchKernelGGL((k_ge_hist<false, KeySavings>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_prev, prefix, shift, width, w.hist, ks);
+    } else {
+        if (dm) hipLaunchKernelGGL((k_ge_hist<true, KeyLength>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_prev, prefix, shift, width, w.hist, KeyLength{});
+        else hipLaunchKernelGGL((k_ge_hist<false, KeyLength>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_prev, prefix, shift, width, w.hist, KeyLength{});
+    }
     return hipGetLastError();
 }
 
 hipError_t launch_greedy_band(const GreedyWs &w, const float2 *xy, const float *dm, uint32_t n, uint32_t f, uint64_t t_lo, uint64_t t_hi,
-                              int blocks, hipStream_t s)
+                              int blocks, bool savings, hipStream_t s)
 {
     hipError_t e = hipMemsetAsync(w.state + 3, 0, 4, s);
     if (e != hipSuccess) return e;
     const uint64_t tiles = (uint64_t)((f + kGeRows - 1) / kGeRows) * ((f + kGeCols - 1) / kGeCols);
     const int g = (int)(tiles < (uint64_t)blocks ? (tiles ? tiles : 1) : (uint64_t)blocks);
-    if (dm) hipLaunchKernelGGL(k_ge_compact<true>, dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_lo, t_hi, w.keys, w.cap);
-    else hipLaunchKernelGGL(k_ge_compact<false>, dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_lo, t_hi, w.keys, w.cap);
+    const KeySavings ks{w.dh};
+    if (savings) {
+        if (dm) hipLaunchKernelGGL((k_ge_compact<true, KeySavings>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_lo, t_hi, w.keys, w.cap, ks);
+        else hipLaunchKernelGGL((k_ge_compact<false, KeySavings>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_lo, t_hi, w.keys, w.cap, ks);
+    } else {
+        if (dm) hipLaunchKernelGGL((k_ge_compact<true, KeyLength>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_lo, t_hi, w.keys, w.cap, KeyLength{});
+        else hipLaunchKernelGGL((k_ge_compact<false, KeyLength>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_lo, t_hi, w.keys, w.cap, KeyLength{});
+    }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if ((e = allow_max_lds((const void *)k_ge_sort)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_ge_sort, dim3(1), dim3(1024), (size_t)w.cap * 8, s, w.keys, w.state, w.cap);

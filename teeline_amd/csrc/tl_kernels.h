@@ -336,7 +336,7 @@ hipError_t launch_selftest_sqrt(uint32_t first_bits, uint64_t count, unsigned lo
 hipError_t launch_tour_length(const float2 *xy, const float *dm, uint32_t n, const uint32_t *perm,
                               float *out_cost, hipStream_t s);
 
-// greedy_edge.hip — greedy-edge construction in bands of at most `cap` sorted keys
+// greedy_edge.hip — greedy-edge and savings construction in bands of at most `cap` sorted keys
 struct GreedyWs {
     uint64_t *keys;       // [cap] the band's keys
     uint32_t *hist;       // [4096] digit histogram
@@ -346,17 +346,21 @@ struct GreedyWs {
     uint32_t *slots;      // [n][2] both neighbours of a city in acceptance order
     uint32_t *succ[2];    // [2n] list ranking of the directed arcs (double-buffered)
     uint32_t *dte[2];
+    float *dh;            // [n] savings only: d(hub, k), +0.0 at the hub (after every greedy-edge field: those keep their offsets)
     uint32_t cap;
 };
 uint32_t greedy_band_cap(int lds_bytes);  // keys per band: a power of two whose keys fit one workgroup's LDS (16 384 on 160 KB)
 size_t greedy_ws_bytes(uint32_t n, uint32_t cap);
 GreedyWs greedy_ws_layout(void *ws, uint32_t n, uint32_t cap);
 hipError_t launch_greedy_init(const GreedyWs &w, uint32_t n, hipStream_t s);
+// savings: w.dh[k] = d(hub, k) — dist() in coordinate form (the matrix builder's bits), a packed-triangle gather in matrix form
+hipError_t launch_savings_dh(const GreedyWs &w, const float2 *xy, const float *dm, uint32_t n, uint32_t hub, hipStream_t s);
+// savings = false: keys of the edge length (greedy-edge); true: keys of the saving against w.dh
 hipError_t launch_greedy_hist(const GreedyWs &w, const float2 *xy, const float *dm, uint32_t f, uint64_t t_prev, uint64_t prefix,
-                              uint32_t shift, uint32_t width, int blocks, hipStream_t s);
+                              uint32_t shift, uint32_t width, int blocks, bool savings, hipStream_t s);
 // compact the keys in (t_lo, t_hi], sort them, walk them
 hipError_t launch_greedy_band(const GreedyWs &w, const float2 *xy, const float *dm, uint32_t n, uint32_t f, uint64_t t_lo, uint64_t t_hi,
-                              int blocks, hipStream_t s);
+                              int blocks, bool savings, hipStream_t s);
 hipError_t launch_greedy_path(const GreedyWs &w, uint32_t n, uint32_t *out_pos, hipStream_t s);
 
 }  // namespace tl
