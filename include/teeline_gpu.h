@@ -351,6 +351,25 @@ int tl_savings_hub(const float *xy, uint32_t n, uint32_t *out_hub);
 int tl_savings(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, uint32_t hub, uint32_t *out_pos, float *out_cost,
                uint32_t *out_hub, tl_stats *stats);
 
+/* ---- Christofides construction: replaces christofides::solve (christofides.rs:12-241) ---------- */
+/* The reference's six steps on positions: Prim's tree from position 0, its odd-degree vertices, a GREEDY matching of them (all
+ * pairs by length, a pair taken when both ends are unmatched — not a blossom matching), the multigraph of tree and matching, its
+ * Euler circuit from position 0 (Hierholzer) and the shortcut to first occurrences.  Tree and matching run on the GPU, the O(n)
+ * walk of steps 4 to 6 on the host inside the call.  Orders fixed here:
+ *   Prim      each round takes the non-tree vertex of smallest key, the FIRST in position order among equals; -0.0 equals +0.0;
+ *             key[v] falls to d(u, v) only where d(u, v) < key[v] strictly (keys start at f32::MAX, 0.0 at position 0);
+ *   matching  ascending length, -0.0 equal to +0.0, equal lengths in (i, j) ascending order (the reference's stable sort);
+ *   NaN       a NaN length between two odd vertices makes the reference's comparator inconsistent and its order unspecified:
+ *             here every NaN ranks after +inf, ties by (i, j);
+ *   tree      a vertex other than 0 that joins without a parent (every distance to it NaN or >= f32::MAX) leaves the reference
+ *             with a result that is no tour: TL_ERR_UNSUPPORTED, the message names the position.
+ * dm_packed NULL: EUC_2D from xy; otherwise every distance is read from the packed matrix and xy may be NULL.  n < 4: the
+ * identity.  *out_cost is tour_length of the route.  n <= 65 535 (positions are 16-bit in the sort keys; TL_ERR_UNSUPPORTED
+ * beyond).  stats (optional): sweeps = bands of sorted pairs, candidates = pairs the matching examined, moves = n, kernel_ms =
+ * tree + odd vertices + matching, reversed = the tree's launch alone in nanoseconds, total_ms includes the host walk. */
+int tl_christofides(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, uint32_t *out_pos, float *out_cost,
+                    tl_stats *stats);
+
 /* ---- multi-start 2-opt (north-star config 4; no counterpart in the reference) ---------------- */
 /* Runs restarts [first, first+count) — restart r starts from the Fisher–Yates permutation drawn
  * from splitmix64(seed + r) (specification: DESIGN.md / oracle tlo_restart_perm) — one descent per

@@ -4,7 +4,7 @@
 //!   `two_opt::solve`        (src/tsp/two_opt.rs:7-67)
 //!   `three_opt::solve`      (src/tsp/three_opt.rs:16-51)
 //!   `lin_kernighan::solve`  (src/tsp/lin_kernighan.rs:35-100)
-//!   `or_opt::solve`, `nearest_neighbor::solve`, `greedy_edge::solve`, `savings::solve`, `DistanceMatrix::build`
+//!   `or_opt::solve`, `nearest_neighbor::solve`, `greedy_edge::solve`, `savings::solve`, `christofides::solve`, `DistanceMatrix::build`
 //! of the `teeline` crate.  This crate knows nothing about `teeline`'s types (no dependency cycle): tours are
 //! POSITIONS (indices into the city array), coordinates are `[x0, y0, x1, y1, ...]`, the optional matrix is the
 //! reference's packed strict lower triangle (`DistanceMatrix::distances()`, distance_matrix.rs:171-173).
@@ -89,6 +89,8 @@ unsafe extern "C" {
                            out_pos: *mut u32, out_cost: *mut f32) -> c_int;
     fn tl_greedy_edge(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
                       stats: *mut Stats) -> c_int;
+    fn tl_christofides(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
+                       stats: *mut Stats) -> c_int;
     fn tl_savings_hub(xy: *const f32, n: u32, out_hub: *mut u32) -> c_int;
     fn tl_savings(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, hub: u32, out_pos: *mut u32, out_cost: *mut f32,
                   out_hub: *mut u32, stats: *mut Stats) -> c_int;
@@ -418,6 +420,19 @@ impl Context {
         let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
         // SAFETY: as in two_opt.
         let rc = unsafe { tl_greedy_edge(self.raw, xy.as_ptr(), opt_ptr(dm_packed), n, t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats) };
+        self.check(rc).map(|_| t)
+    }
+
+    /// `christofides::solve` (christofides.rs:12-68): Prim's tree from position 0 (first minimum in position order), a greedy
+    /// matching of its odd vertices (equal lengths in (i, j) order, a NaN length after +inf), Euler circuit and shortcut; n < 4 is
+    /// the identity, n <= 65 535.  A tree that cannot span (a position every distance to which is NaN or >= f32::MAX) is
+    /// `Error` with `TL_ERR_UNSUPPORTED`.
+    pub fn christofides(&self, xy: &[f32], dm_packed: Option<&[f32]>) -> Result<Tour, Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, None);
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        // SAFETY: as in two_opt.
+        let rc = unsafe { tl_christofides(self.raw, xy.as_ptr(), opt_ptr(dm_packed), n, t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats) };
         self.check(rc).map(|_| t)
     }
 

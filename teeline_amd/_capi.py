@@ -47,7 +47,7 @@ SYMBOLS = [
     "tl_or_opt", "tl_or_opt_find_best_move", "tl_selftest_sqrt", "tl_two_opt_population", "tl_dm_is_euc2d",
     "tl_two_opt_multistart_devices", "tl_two_opt_trace", "tl_three_opt_trace", "tl_lk_trace", "tl_or_opt_trace",
     "tl_lk_live", "tl_two_opt_neighbour_lists", "tl_two_opt_plan", "tl_multistart_shard", "tl_two_opt_last_counters",
-    "tl_greedy_edge", "tl_savings_hub", "tl_savings",
+    "tl_greedy_edge", "tl_savings_hub", "tl_savings", "tl_christofides",
 ]
 
 
@@ -129,6 +129,7 @@ def load():
     L.tl_build_candidates.argtypes = [vp, vp, u32, u32, vp]
     L.tl_nearest_neighbor.argtypes = [vp, vp, vp, u32, u32, vp, f32p]
     L.tl_greedy_edge.argtypes = [vp, vp, vp, u32, vp, f32p, C.POINTER(TlStats)]
+    L.tl_christofides.argtypes = [vp, vp, vp, u32, vp, f32p, C.POINTER(TlStats)]
     L.tl_savings_hub.argtypes = [vp, u32, C.POINTER(u32)]
     L.tl_savings.argtypes = [vp, vp, vp, u32, u32, vp, f32p, C.POINTER(u32), C.POINTER(TlStats)]
     L.tl_selftest_sqrt.argtypes = [vp, u32, u64, C.POINTER(u64), C.POINTER(u32)]

@@ -1,5 +1,6 @@
 // greedy_edge.hip — greedy-edge construction (reference: src/tsp/greedy_edge.rs:21-65 over graph.rs:54-196), DESIGN.md §4.11,
-// and savings construction (src/tsp/savings.rs:34-163: the same selection under another sort key), DESIGN.md §4.12.
+// savings construction (src/tsp/savings.rs:34-163: the same selection under another sort key), DESIGN.md §4.12, and the greedy
+// matching of Christofides (src/tsp/christofides.rs:138-166: the same bands, capacity 1 instead of 2, no cycle test), §4.13.
 //
 // The reference sorts all n(n-1)/2 edges by f32::total_cmp of their length and walks them once (select_edges): an edge is skipped
 // if an endpoint already has degree 2, or if it would close a cycle before n - 1 edges are in.  Both rejections are final (degrees
@@ -55,6 +56,20 @@ struct KeySavings {
     {
         const float s = (dh[i] + dh[j]) - d;
         return s != s ? kSavNanKey : ~total_key(s);
+    }
+};
+
+constexpr uint32_t kMatchNanKey = 0xFF800001u;  // one past +inf's key (total_key(+inf) = 0xFF800000)
+
+// Christofides' matching (christofides.rs:153): ascending partial_cmp of the length, so -0.0 and +0.0 are ONE value (zero is
+// canonicalised before the total-order key is formed).  A NaN length makes the reference's comparator inconsistent and its order
+// unspecified; here a NaN of any sign or payload is ONE value above +inf, ties by (i, j).  The host's invariants
+// hold as for the other two: every key is > 0 (j >= 1), none is all-ones (the largest upper word is kMatchNanKey).
+struct KeyMatching {
+    __device__ __forceinline__ uint32_t operator()(float d, uint32_t, uint32_t) const
+    {
+        if (d != d) return kMatchNanKey;
+        return total_key(d == 0.0f ? 0.0f : d);
     }
 };
 
@@ -160,9 +175,15 @@ __global__ __launch_bounds__(1024) void k_ge_sort(uint64_t *__restrict__ keys, c
 // good, and so does end[u] == v while fewer than n - 1 edges can be in before that key.  Lane 0 then walks the survivors in order
 // with the exact test.  An accepted edge (u, v) lands in the first free of the two neighbour slots of u and of v (slot 0 = the
 // earlier edge: adj[c][0] of hamiltonian_cycle_to_path).  At the end the wave writes the table back and lists the free cities.
+// MATCH (greedy_matching, christofides.rs:158-164): a city's capacity is 1 — the table holds c for an unmatched odd vertex and
+// kGeFull for everything else — so a pair is taken iff neither end is full, both ends then are, there is no cycle test, and the
+// pairs go to slots[2a], slots[2a + 1] in acceptance order (a = the pair's index) until `target` = k / 2 of them are in.
+template <bool MATCH>
 __global__ __launch_bounds__(64) void k_ge_walk(const uint64_t *__restrict__ keys, uint32_t *__restrict__ state, uint16_t *__restrict__ end_g,
-                                                uint32_t *__restrict__ slots, uint16_t *__restrict__ free, uint32_t n, uint32_t cap)
+                                                uint32_t *__restrict__ slots, uint16_t *__restrict__ free, uint32_t n, uint32_t cap,
+                                                uint32_t target)
 {
+    const uint32_t goal = MATCH ? target : n;
     extern __shared__ uint16_t lend[];
     __shared__ uint32_t ch[64];
     __shared__ uint32_t sh_acc, sh_done;
@@ -173,7 +194,7 @@ __global__ __launch_bounds__(64) void k_ge_walk(const uint64_t *__restrict__ key
     uint64_t examined = 0;
     if (l == 0) sh_done = 0;
     TL_SYNC();
-    for (uint32_t base = 0; base < count && acc < n; base += 64) {
+    for (uint32_t base = 0; base < count && acc < goal; base += 64) {
         const bool valid = base + l < count;
         uint32_t u = 0, v = 0;
         bool alive = false;
@@ -182,7 +203,7 @@ __global__ __launch_bounds__(64) void k_ge_walk(const uint64_t *__restrict__ key
             u = (uint32_t)(key >> 16) & 0xFFFFu;
             v = (uint32_t)key & 0xFFFFu;
             const uint32_t eu = lend[u], ev = lend[v];
-            alive = eu != kGeFull && ev != kGeFull && !(eu == v && acc + 64 < n);
+            alive = eu != kGeFull && ev != kGeFull && (MATCH || !(eu == v && acc + 64 < n));
         }
         ch[l] = (u << 16) | v;
         uint64_t live = __builtin_amdgcn_ballot_w64(alive);
@@ -195,15 +216,22 @@ __global__ __launch_bounds__(64) void k_ge_walk(const uint64_t *__restrict__ key
                 const uint32_t uu = ch[bit] >> 16, vv = ch[bit] & 0xFFFFu;
                 const uint32_t eu = lend[uu], ev = lend[vv];
                 if (eu == kGeFull || ev == kGeFull) continue;
-                if (eu == vv && acc != n - 1) continue;
-                const uint32_t du = eu != uu, dv = ev != vv;  // degree before this edge (0 / 1)
-                slots[2 * uu + du] = vv;
-                slots[2 * vv + dv] = uu;
-                lend[eu] = (uint16_t)ev;
-                lend[ev] = (uint16_t)eu;
-                if (du) lend[uu] = kGeFull;
-                if (dv) lend[vv] = kGeFull;
-                if (++acc == n) {
+                if constexpr (MATCH) {
+                    slots[2 * acc] = uu;
+                    slots[2 * acc + 1] = vv;
+                    lend[uu] = kGeFull;
+                    lend[vv] = kGeFull;
+                } else {
+                    if (eu == vv && acc != n - 1) continue;
+                    const uint32_t du = eu != uu, dv = ev != vv;  // degree before this edge (0 / 1)
+                    slots[2 * uu + du] = vv;
+                    slots[2 * vv + dv] = uu;
+                    lend[eu] = (uint16_t)ev;
+                    lend[ev] = (uint16_t)eu;
+                    if (du) lend[uu] = kGeFull;
+                    if (dv) lend[vv] = kGeFull;
+                }
+                if (++acc == goal) {
                     stop = bit + 1;
                     break;
                 }
@@ -356,45 +384,63 @@ hipError_t launch_savings_dh(const GreedyWs &w, const float2 *xy, const float *d
     return hipGetLastError();
 }
 
+namespace {
+
+// Calls f(policy) with the key policy `key` names
+template <class F>
+hipError_t with_key(GreedyKey key, const GreedyWs &w, F f)
+{
+    if (key == kGeKeySavings) return f(KeySavings{w.dh});
+    if (key == kGeKeyMatching) return f(KeyMatching{});
+    return f(KeyLength{});
+}
+
+int pair_grid(uint32_t f, int blocks)
+{
+    const uint64_t tiles = (uint64_t)((f + kGeRows - 1) / kGeRows) * ((f + kGeCols - 1) / kGeCols);
+    return (int)(tiles < (uint64_t)blocks ? (tiles ? tiles : 1) : (uint64_t)blocks);
+}
+
+}  // namespace
+
 hipError_t launch_greedy_hist(const GreedyWs &w, const float2 *xy, const float *dm, uint32_t f, uint64_t t_prev, uint64_t prefix,
-                              uint32_t shift, uint32_t width, int blocks, bool savings, hipStream_t s)
+                              uint32_t shift, uint32_t width, int blocks, GreedyKey key, hipStream_t s)
 {
     hipError_t e = hipMemsetAsync(w.hist, 0, (size_t)kGeBins * 4, s);
     if (e != hipSuccess) return e;
-    const uint64_t tiles = (uint64_t)((f + kGeRows - 1) / kGeRows) * ((f + kGeCols - 1) / kGeCols);
-    const int g = (int)(tiles < (uint64_t)blocks ? (tiles ? tiles : 1) : (uint64_t)blocks);
-    const KeySavings ks{w.dh};
-    if (savings) {
-        if (dm) hipLaunchKernelGGL((k_ge_hist<true, KeySavings>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_prev, prefix, shift, width, w.hist, ks);
-        else hipLaunchKernelGGL((k_ge_hist<false, KeySavings>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_prev, prefix, shift, width, w.hist, ks);
-    } else {
-        if (dm) hipLaunchKernelGGL((k_ge_hist<true, KeyLength>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_prev, prefix, shift, width, w.hist, KeyLength{});
-        else hipLaunchKernelGGL((k_ge_hist<false, KeyLength>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_prev, prefix, shift, width, w.hist, KeyLength{});
-    }
-    return hipGetLastError();
+    const int g = pair_grid(f, blocks);
+    return with_key(key, w, [&](auto k) {
+        using K = decltype(k);
+        if (dm) hipLaunchKernelGGL((k_ge_hist<true, K>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_prev, prefix, shift, width, w.hist, k);
+        else hipLaunchKernelGGL((k_ge_hist<false, K>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_prev, prefix, shift, width, w.hist, k);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_greedy_band(const GreedyWs &w, const float2 *xy, const float *dm, uint32_t n, uint32_t f, uint64_t t_lo, uint64_t t_hi,
-                              int blocks, bool savings, hipStream_t s)
+                              int blocks, GreedyKey key, uint32_t target, hipStream_t s)
 {
     hipError_t e = hipMemsetAsync(w.state + 3, 0, 4, s);
     if (e != hipSuccess) return e;
-    const uint64_t tiles = (uint64_t)((f + kGeRows - 1) / kGeRows) * ((f + kGeCols - 1) / kGeCols);
-    const int g = (int)(tiles < (uint64_t)blocks ? (tiles ? tiles : 1) : (uint64_t)blocks);
-    const KeySavings ks{w.dh};
-    if (savings) {
-        if (dm) hipLaunchKernelGGL((k_ge_compact<true, KeySavings>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_lo, t_hi, w.keys, w.cap, ks);
-        else hipLaunchKernelGGL((k_ge_compact<false, KeySavings>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_lo, t_hi, w.keys, w.cap, ks);
-    } else {
-        if (dm) hipLaunchKernelGGL((k_ge_compact<true, KeyLength>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_lo, t_hi, w.keys, w.cap, KeyLength{});
-        else hipLaunchKernelGGL((k_ge_compact<false, KeyLength>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_lo, t_hi, w.keys, w.cap, KeyLength{});
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const int g = pair_grid(f, blocks);
+    e = with_key(key, w, [&](auto k) {
+        using K = decltype(k);
+        if (dm) hipLaunchKernelGGL((k_ge_compact<true, K>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_lo, t_hi, w.keys, w.cap, k);
+        else hipLaunchKernelGGL((k_ge_compact<false, K>), dim3(g), dim3(kGeCols), 0, s, xy, dm, w.free, w.state, t_lo, t_hi, w.keys, w.cap, k);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
     if ((e = allow_max_lds((const void *)k_ge_sort)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_ge_sort, dim3(1), dim3(1024), (size_t)w.cap * 8, s, w.keys, w.state, w.cap);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = allow_max_lds((const void *)k_ge_walk)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ge_walk, dim3(1), dim3(64), ((size_t)n * 2 + 15) & ~(size_t)15, s, w.keys, w.state, w.end, w.slots, w.free, n, w.cap);
+    const size_t lds = ((size_t)n * 2 + 15) & ~(size_t)15;
+    if (key == kGeKeyMatching) {
+        if ((e = allow_max_lds((const void *)k_ge_walk<true>)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_ge_walk<true>, dim3(1), dim3(64), lds, s, w.keys, w.state, w.end, w.slots, w.free, n, w.cap, target);
+    } else {
+        if ((e = allow_max_lds((const void *)k_ge_walk<false>)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_ge_walk<false>, dim3(1), dim3(64), lds, s, w.keys, w.state, w.end, w.slots, w.free, n, w.cap, n);
+    }
     return hipGetLastError();
 }
 

@@ -336,7 +336,13 @@ hipError_t launch_selftest_sqrt(uint32_t first_bits, uint64_t count, unsigned lo
 hipError_t launch_tour_length(const float2 *xy, const float *dm, uint32_t n, const uint32_t *perm,
                               float *out_cost, hipStream_t s);
 
-// greedy_edge.hip — greedy-edge and savings construction in bands of at most `cap` sorted keys
+// greedy_edge.hip — greedy-edge and savings construction, and Christofides' greedy matching, in bands of at most `cap` sorted
+// keys
+enum GreedyKey : int {
+    kGeKeyLength = 0,    // greedy-edge: f32::total_cmp of the edge length
+    kGeKeySavings = 1,   // savings: descending total_cmp of the saving against w.dh
+    kGeKeyMatching = 2,  // Christofides' matching: partial_cmp of the length (-0.0 = +0.0), NaN above +inf; capacity 1, no cycle test
+};
 struct GreedyWs {
     uint64_t *keys;       // [cap] the band's keys
     uint32_t *hist;       // [4096] digit histogram
@@ -355,12 +361,28 @@ GreedyWs greedy_ws_layout(void *ws, uint32_t n, uint32_t cap);
 hipError_t launch_greedy_init(const GreedyWs &w, uint32_t n, hipStream_t s);
 // savings: w.dh[k] = d(hub, k) — dist() in coordinate form (the matrix builder's bits), a packed-triangle gather in matrix form
 hipError_t launch_savings_dh(const GreedyWs &w, const float2 *xy, const float *dm, uint32_t n, uint32_t hub, hipStream_t s);
-// savings = false: keys of the edge length (greedy-edge); true: keys of the saving against w.dh
 hipError_t launch_greedy_hist(const GreedyWs &w, const float2 *xy, const float *dm, uint32_t f, uint64_t t_prev, uint64_t prefix,
-                              uint32_t shift, uint32_t width, int blocks, bool savings, hipStream_t s);
-// compact the keys in (t_lo, t_hi], sort them, walk them
+                              uint32_t shift, uint32_t width, int blocks, GreedyKey key, hipStream_t s);
+// compact the keys in (t_lo, t_hi], sort them, walk them.  target: kGeKeyMatching only — the walk stops at that many pairs and
+// lists them in w.slots (pair a at [2a], [2a + 1]); the other two stop at n edges.
 hipError_t launch_greedy_band(const GreedyWs &w, const float2 *xy, const float *dm, uint32_t n, uint32_t f, uint64_t t_lo, uint64_t t_hi,
-                              int blocks, bool savings, hipStream_t s);
+                              int blocks, GreedyKey key, uint32_t target, hipStream_t s);
 hipError_t launch_greedy_path(const GreedyWs &w, uint32_t n, uint32_t *out_pos, hipStream_t s);
+
+// christofides.hip — Prim's tree and the odd vertices of Christofides.  The fields alias the list-ranking part
+// of a GreedyWs (succ / dte: Christofides ranks no list) and the words of its state block behind the band state.
+struct ChrWs {
+    float *key;        // [n] Prim's keys where they do not fit LDS
+    uint16_t *par;     // [n] ... and the tentative parents
+    uint16_t *parent;  // [n] out: parent[v], 0xFFFF = none (position 0, or a vertex no finite distance reaches)
+    uint16_t *order;   // [n] out: order[r] = the vertex that joined in round r
+    uint32_t *status;  // [0] != 0: a vertex other than 0 joined without a parent, [1] the first such position
+};
+ChrWs chr_ws_layout(const GreedyWs &w, uint32_t n);
+// The whole tree in one launch of one workgroup (prim_mst, christofides.rs:75-114)
+hipError_t launch_chr_prim(const ChrWs &cw, const float2 *xy, const float *dm, uint32_t n, int lds_bytes, hipStream_t s);
+// Degrees from cw.parent: the odd vertices go to w.free in position order, w.end holds c for them and "full" for every other
+// city, w.state is reset with state[4] = their number
+hipError_t launch_chr_odd(const GreedyWs &w, const ChrWs &cw, uint32_t n, hipStream_t s);
 
 }  // namespace tl

@@ -11,9 +11,10 @@ import warnings
 SOLVER_NAMES = {"nn": "nearest_neighbor", "nearest_neighbor": "nearest_neighbor", "2opt": "two_opt", "two_opt": "two_opt",
                 "3opt": "three_opt", "three_opt": "three_opt", "oropt": "or_opt", "or_opt": "or_opt", "or-opt": "or_opt",
                 "lk": "lin_kernighan", "lin_kernighan": "lin_kernighan", "shuffle": "random_shuffle",
-                "random_shuffle": "random_shuffle", "greedy_edge": "greedy_edge", "gec": "greedy_edge", "savings": "savings", "sav": "savings"}
+                "random_shuffle": "random_shuffle", "greedy_edge": "greedy_edge", "gec": "greedy_edge", "savings": "savings", "sav": "savings",
+                "christofides": "christofides", "chr": "christofides"}
 PRESETS = {"fast": ["nn", "2opt"]}  # resolve_preset (main.rs:354-369); classic / thorough end in SA (not accelerated)
-AUTO_EXPAND_WITH_NN = {"two_opt", "three_opt", "or_opt", "lin_kernighan"}  # mod.rs:129-139 (greedy_edge and savings are seeds: `solve gec` / `solve sav` run alone)
+AUTO_EXPAND_WITH_NN = {"two_opt", "three_opt", "or_opt", "lin_kernighan"}  # mod.rs:129-139 (greedy_edge, savings and christofides are seeds: `solve gec` / `solve sav` / `solve chr` run alone)
 
 
 def steps_for_solve(solver, no_seed=False):
@@ -72,11 +73,11 @@ class StageOutcome:
 
 
 def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1):
-    """steps: iterable of solver names ("nn", "gec", "sav", "2opt", "3opt", "or_opt", "lk", "shuffle"); opts: {name: options} (optional)."""
-    from . import (HeuristicOptions, LKOptions, greedy_edge, lin_kernighan, nearest_neighbor, or_opt, savings, three_opt, two_opt,
+    """steps: iterable of solver names ("nn", "gec", "sav", "chr", "2opt", "3opt", "or_opt", "lk", "shuffle"); opts: {name: options} (optional)."""
+    from . import (HeuristicOptions, LKOptions, christofides, greedy_edge, lin_kernighan, nearest_neighbor, or_opt, savings, three_opt, two_opt,
                    validate_tour)
     mods = {"nearest_neighbor": nearest_neighbor, "two_opt": two_opt, "three_opt": three_opt, "or_opt": or_opt,
-            "lin_kernighan": lin_kernighan, "greedy_edge": greedy_edge, "savings": savings}
+            "lin_kernighan": lin_kernighan, "greedy_edge": greedy_edge, "savings": savings, "christofides": christofides}
     opts = opts or {}
     outcomes, seed = [], None
     for step in steps:

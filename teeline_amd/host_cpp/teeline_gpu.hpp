@@ -7,7 +7,7 @@
 //   src/tsp/mod.rs:1731-1814         TspProblem, Solution
 //   src/tsp/mod.rs:596-613,1249-1267 HeuristicOptions, LKOptions
 //   src/tsp/tsplib.rs:101-255        tsplib::read_from_file
-//   src/tsp/{two_opt,three_opt,or_opt,lin_kernighan,nearest_neighbor,greedy_edge,savings}.rs  solve(problem, opts, progress, init_tour)
+//   src/tsp/{two_opt,three_opt,or_opt,lin_kernighan,nearest_neighbor,greedy_edge,savings,christofides}.rs  solve(problem, opts, progress, init_tour)
 //   src/tsp/pipeline.rs:53-80        run_pipeline_stages (warm start + validate_tour)
 // Same names, argument meaning and error behaviour: dispatcher-level failures throw std::runtime_error (the
 // reference returns Err(String), mod.rs:1661), inputs on which the reference panics throw teeline::ReferencePanic.
@@ -502,6 +502,33 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOp
 }
 }  // namespace savings
 
+namespace christofides {  // christofides.rs:12-68
+inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions & /*_opts*/, const ProgressFn *progress_tx,
+                      const std::vector<size_t> * /*_init_tour*/)
+{
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size();
+    std::vector<uint32_t> out(n);
+    float cost = 0.f;
+    tl_stats st{};
+    // GEO / EXPLICIT: every distance is the packed matrix's (distance_by_pos, christofides.rs:102-104, :147-149)
+    ctx.check(tl_christofides(ctx.get(), xy.data(), problem.explicit_packed(), n, out.data(), &cost, &st));
+    Solution s = detail::finish(problem, out, cost, st, nullptr);
+    if (progress_tx && *progress_tx) {
+        // christofides.rs:24-65: n < 4 sends Done alone; otherwise the identity (cities in file order) with 0.0 once the tree is
+        // built, then the route with its length, then Done
+        if (n >= 4) {
+            std::vector<size_t> identity(n);
+            for (uint32_t k = 0; k < n; ++k) identity[k] = problem.cities[k].id;
+            (*progress_tx)(ProgressKind::PathUpdate, identity, 0.0f);
+            (*progress_tx)(ProgressKind::PathUpdate, s.route_, cost);
+        }
+        (*progress_tx)(ProgressKind::Done, s.route_, cost);
+    }
+    return s;
+}
+}  // namespace christofides
+
 namespace lin_kernighan {  // lin_kernighan.rs:35-100
 inline Solution solve(Context &ctx, const TspProblem &problem, const LKOptions &opts, const ProgressFn *progress_tx,
                       const std::vector<size_t> *init_tour, uint64_t seed = 1)
@@ -782,7 +809,7 @@ inline Solution solve(Context &ctx, const TspProblem &problem, uint64_t seed)
 }  // namespace random_shuffle
 
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
-enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings };
+enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides };
 
 inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
 {
@@ -795,14 +822,15 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
     else if (s == "shuffle" || s == "random_shuffle") out = Solvers::RandomShuffle;
     else if (s == "gec" || s == "greedy_edge") out = Solvers::GreedyEdge;
     else if (s == "sav" || s == "savings") out = Solvers::Savings;
+    else if (s == "chr" || s == "christofides") out = Solvers::Christofides;
     else {
-        static const char *cpu_only[] = {"aco", "ant_colony", "bhk", "bellman_karp", "branch_bound", "christofides", "chr",
+        static const char *cpu_only[] = {"aco", "ant_colony", "bhk", "bellman_karp", "branch_bound",
                                          "cs", "cuckoo_search", "fpa", "flower_pollination", "fourier", "ga", "genetic_algorithm", "gsa",
                                          "gravitational_search", "pso", "particle_swarm", "sa", "simulated_annealing",
                                          "som", "kohonen", "kohonen_som", "stochastic_hill", "tabu", "tabu_search"};
         for (const char *c : cpu_only)
             if (s == c) {
-                why = "solver `" + s + "` is not accelerated by this build (nn, gec, sav, 2opt, 3opt, or_opt, lk, shuffle are)";
+                why = "solver `" + s + "` is not accelerated by this build (nn, gec, sav, chr, 2opt, 3opt, or_opt, lk, shuffle are)";
                 return false;
             }
         why = "unknown solver";  // FromStr's Err (mod.rs:588)
@@ -821,6 +849,7 @@ inline const char *solver_name(Solvers s)
         case Solvers::LinKernighan: return "lk";
         case Solvers::GreedyEdge: return "greedy_edge";
         case Solvers::Savings: return "savings";
+        case Solvers::Christofides: return "christofides";
         default: return "shuffle";
     }
 }
@@ -882,6 +911,7 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             case Solvers::RandomShuffle: sol = random_shuffle::solve(ctx, problem, o.seed); break;
             case Solvers::GreedyEdge: sol = greedy_edge::solve(ctx, problem, o.heuristic, o.progress, init); break;
             case Solvers::Savings: sol = savings::solve(ctx, problem, o.heuristic, o.progress, init); break;
+            case Solvers::Christofides: sol = christofides::solve(ctx, problem, o.heuristic, o.progress, init); break;
         }
         const auto t1 = std::chrono::steady_clock::now();
         const uint64_t ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();

@@ -5,9 +5,9 @@
 //                                     [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P] [--n_nearest K] [--max-depth D]
 //   teeline-gpu pipeline --steps=nn,2opt,... [-i FILE] [same options]
 //   teeline-gpu solvers [--short]
-//     solver  : nn, gec, sav, 2opt, 3opt, or_opt, lk, shuffle (and their long names, mod.rs:559-590); preset: fast = nn,2opt (main.rs:354-369)
+//     solver  : nn, gec, sav, chr, 2opt, 3opt, or_opt, lk, shuffle (and their long names, mod.rs:559-590); preset: fast = nn,2opt (main.rs:354-369)
 //     solve   : 2opt / 3opt / or_opt / lk auto-expand to pipeline(nn, solver) unless --no-seed (main.rs:387-397, mod.rs:129-139);
-//               gec (greedy_edge) and sav (savings) are constructions and run alone
+//               gec (greedy_edge), sav (savings) and chr (christofides) are constructions and run alone
 //     stdout  : print_solution "{:.5} {0|1}\n<id id ... >\n" (main.rs:645-652) or the JSON object of main.rs:700-712;
 //               with --optimal-tour the comparison goes to stderr in text mode and into the JSON object in JSON mode
 //   own flags (no counterpart in the reference): --seed S (LK kicks and the shuffle stage; the reference draws both from an
@@ -40,11 +40,11 @@ struct Args {
 {
     if (why) std::fprintf(stderr, "error: %s\n", why);
     std::fprintf(stderr,
-                 "usage: teeline-gpu solve <nn|gec|sav|2opt|3opt|or_opt|lk|shuffle|fast> [-i FILE] [--no-seed] [--output-format text|json]\n"
+                 "usage: teeline-gpu solve <nn|gec|sav|chr|2opt|3opt|or_opt|lk|shuffle|fast> [-i FILE] [--no-seed] [--output-format text|json]\n"
                  "                         [--optimal-tour FILE] [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P]\n"
                  "                         [--n_nearest K] [--max-depth D] [--seed S] [--best-sweep] [--device N] [--stats]\n"
                  "                         [--progress-digest]\n"
-                 "       teeline-gpu pipeline --steps=nn,2opt,... | --steps=greedy_edge,2opt,... | --steps=savings,2opt,... [-i FILE] [options as above]\n"
+                 "       teeline-gpu pipeline --steps=nn,2opt,... | --steps=greedy_edge,2opt,... | --steps=savings,2opt,... | --steps=christofides,lk,... [-i FILE] [options as above]\n"
                  "       teeline-gpu solvers [--short]\n");
     std::exit(2);  // clap's usage-error exit code
 }
