@@ -238,12 +238,11 @@ extern "C" int tl_dm_is_euc2d(tl_ctx *c, const float *xy, const float *dm_packed
     if (n < 2) return TL_OK;
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    const size_t b = (size_t)n * (n - 1) / 2 * 4;
-    if ((rc = ensure(c, c->xy, (size_t)n * 8)) || (rc = ensure(c, c->dm, b)) || (rc = ensure(c, c->misc, 16))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dm.p, dm_packed, b, hipMemcpyHostToDevice, c->stream));
+    const float2 *dxy = nullptr;
+    const float *ddm = nullptr;
+    if ((rc = upload_xy(c, xy, n, &dxy)) || (rc = upload_dm(c, dm_packed, n, &ddm)) || (rc = ensure(c, c->misc, 16))) return rc;
     HIPCHK(c, hipMemsetAsync(c->misc.p, 0, 4, c->stream));
-    HIPCHK(c, launch_dm_compare((const float2 *)c->xy.p, n, (const float *)c->dm.p, (uint32_t *)c->misc.p, c->stream));
+    HIPCHK(c, launch_dm_compare(dxy, n, ddm, (uint32_t *)c->misc.p, c->stream));
     uint32_t differs = 0;
     HIPCHK(c, hipMemcpyAsync(&differs, c->misc.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -266,16 +265,7 @@ extern "C" int tl_tour_length(tl_ctx *c, const float *xy, const float *dm_packed
     if ((rc = ensure(c, c->init, (size_t)n * 4)) || (rc = ensure(c, c->out_cost, 4))) return rc;
     const float2 *dxy = nullptr;
     const float *ddm = nullptr;
-    if (dm_packed) {
-        const size_t b = (size_t)n * (n - 1) / 2 * 4;
-        if ((rc = ensure(c, c->dm, b))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->dm.p, dm_packed, b, hipMemcpyHostToDevice, c->stream));
-        ddm = (const float *)c->dm.p;
-    } else {
-        if ((rc = ensure(c, c->xy, (size_t)n * 8))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        dxy = (const float2 *)c->xy.p;
-    }
+    if ((rc = upload_input(c, xy, dm_packed, n, &dxy, &ddm))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->init.p, perm, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, launch_tour_length(dxy, ddm, n, (const uint32_t *)c->init.p, (float *)c->out_cost.p, c->stream));
     HIPCHK(c, hipMemcpyAsync(out_cost, c->out_cost.p, 4, hipMemcpyDeviceToHost, c->stream));

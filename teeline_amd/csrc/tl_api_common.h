@@ -1,6 +1,7 @@
 // tl_api_common.h — what the host-side translation units of the C ABI share (internal to libteeline_gpu): the context, its
 // single-thread guard, error reporting and the grow-only device buffers.  tl_api.hip (context, matrix, tour length),
-// tl_api_two_opt.hip, tl_api_scans.hip (3-opt, Or-opt) and tl_api_lk.hip (candidate lists, NN seed, Lin-Kernighan) include it.
+// tl_api_two_opt.hip, tl_api_scans.hip (3-opt, Or-opt), tl_api_lk.hip (candidate lists, NN seed, Lin-Kernighan) and tl_api_greedy.hip
+// (greedy-edge, savings, Christofides) include it.
 #pragma once
 #include "../../include/teeline_gpu.h"
 #include "tl_kernels.h"
@@ -128,4 +129,112 @@ inline int knn_form(const tl_ctx *c) { return (tune_flags(c) & TL_FLAG_KNN_1LANE
 // tl_api_lk.hip: device-side candidate lists and NN seed, also used by tl_lk
 int build_candidates_dev(tl_ctx *c, const float *xy_host, const float2 *d_xy, uint32_t n, uint32_t k, uint32_t *d_cand);
 int nn_seed_dev(tl_ctx *c, const float2 *d_xy, uint32_t n, uint32_t n_nearest, uint32_t *d_path);
+
+inline size_t packed_dm_bytes(uint32_t n) { return (size_t)n * (n - 1) / 2 * 4; }  // the reference's packed lower triangle, f32
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }                  // where a region of a workspace may begin
+
+// The instance onto the device, on the context's stream: the coordinates into c->xy, the packed matrix into c->dm.  The caller's
+// arrays are the entry point's arguments, which outlive the call's last synchronise.
+inline int upload_xy(tl_ctx *c, const float *xy, uint32_t n, const float2 **dxy)
+{
+    int rc;
+    if ((rc = ensure(c, c->xy, (size_t)n * 8))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    *dxy = (const float2 *)c->xy.p;
+    return TL_OK;
+}
+inline int upload_dm(tl_ctx *c, const float *dm_packed, uint32_t n, const float **ddm)
+{
+    int rc;
+    if ((rc = ensure(c, c->dm, packed_dm_bytes(n)))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->dm.p, dm_packed, packed_dm_bytes(n), hipMemcpyHostToDevice, c->stream));
+    *ddm = (const float *)c->dm.p;
+    return TL_OK;
+}
+// The packed matrix (then every distance is read from it) or the coordinates: exactly one of the two, the other pointer stays as it
+// is.  (tl_two_opt and its trace upload both where both are given: the matrix drives the descent, c->xy the neighbour lists' cache.)
+inline int upload_input(tl_ctx *c, const float *xy, const float *dm_packed, uint32_t n, const float2 **dxy, const float **ddm)
+{
+    return dm_packed ? upload_dm(c, dm_packed, n, ddm) : upload_xy(c, xy, n, dxy);
+}
+
+// The start permutation (init == NULL: the identity) to d_perm, and a synchronise: the identity lives in here, and every host
+// vector whose copy the caller enqueued before this call may go out of scope behind it.  The last upload of a setup.
+inline int upload_start_sync(tl_ctx *c, const uint32_t *init, uint32_t n, void *d_perm)
+{
+    std::vector<uint32_t> ident;
+    if (!init) {
+        ident.resize(n);
+        for (uint32_t i = 0; i < n; ++i) ident[i] = i;
+        init = ident.data();
+    }
+    HIPCHK(c, hipMemcpyAsync(d_perm, init, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TL_OK;
+}
+
+// The ending of a call that fills tl_stats: kernel_ms between the context's event pair (0 where none is valid), total_ms since t0.
+inline void stamp_times(tl_ctx *c, tl_stats *st, std::chrono::steady_clock::time_point t0)
+{
+    if (!st) return;
+    double kms = 0;
+    tl_last_kernel_ms(c, &kms);
+    st->kernel_ms = kms;
+    st->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// `rounds` rounds of a search per host poll of its done flag (the kernels are no-ops once it is set).  The first batch is enqueued
+// launch by launch; a search still running after it replays the same rounds as ONE hipGraph launch per poll — a round is a few
+// short dependent kernels, and the host's per-launch cost and the gaps between separately enqueued kernels are a visible part of
+// it.  Where capture or instantiation fails (or allowed == false) every batch is enqueued launch by launch.
+class RoundGraph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    bool first = true, ok;
+
+public:
+    explicit RoundGraph(bool allowed = true) : ok(allowed) {}
+    ~RoundGraph()
+    {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+    }
+    RoundGraph(const RoundGraph &) = delete;
+    RoundGraph &operator=(const RoundGraph &) = delete;
+    // enqueue_round(r) -> hipError_t enqueues round r on `stream`
+    template <class F>
+    hipError_t launch(hipStream_t stream, int rounds, F &&enqueue_round)
+    {
+        if (!first && ok && !exec) {
+            ok = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+            if (ok) {
+                hipError_t le = hipSuccess;
+                for (int r = 0; r < rounds && le == hipSuccess; ++r) le = enqueue_round((uint32_t)r);
+                const hipError_t ce = hipStreamEndCapture(stream, &graph);
+                ok = le == hipSuccess && ce == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
+            }
+            if (!ok) {
+                // separately enqueued launches from here on — after making sure the stream has left capture mode (a capture
+                // that another thread's legacy-stream operation invalidated stays "active, invalidated" until it is ended)
+                (void)hipGetLastError();
+                hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+                if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+                    hipGraph_t g2 = nullptr;
+                    (void)hipStreamEndCapture(stream, &g2);
+                    if (g2) (void)hipGraphDestroy(g2);
+                }
+                (void)hipGetLastError();
+                if (graph) {
+                    (void)hipGraphDestroy(graph);
+                    graph = nullptr;
+                }
+            }
+        }
+        first = false;
+        if (exec) return hipGraphLaunch(exec, stream);
+        hipError_t e = hipSuccess;
+        for (int r = 0; r < rounds && e == hipSuccess; ++r) e = enqueue_round((uint32_t)r);
+        return e;
+    }
+};
 }  // namespace tlapi

@@ -105,23 +105,6 @@ int run_bands(tl_ctx *c, const char *who, const GreedyWs &w, const float2 *dxy, 
     return TL_OK;
 }
 
-// The packed matrix (then every distance is read from it) or the coordinates, on the context's stream
-int upload_input(tl_ctx *c, const float *xy, const float *dm_packed, uint32_t n, const float2 **dxy, const float **ddm)
-{
-    int rc;
-    if (dm_packed) {
-        const size_t b = (size_t)n * (n - 1) / 2 * 4;
-        if ((rc = ensure(c, c->dm, b))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->dm.p, dm_packed, b, hipMemcpyHostToDevice, c->stream));
-        *ddm = (const float *)c->dm.p;
-    } else {
-        if ((rc = ensure(c, c->xy, (size_t)n * 8))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        *dxy = (const float2 *)c->xy.p;
-    }
-    return TL_OK;
-}
-
 // The limits the bands set, and the identity answer of the smallest inputs (n <= small_n: the cities in file order).  Returns
 // TL_OK with *done = true when the answer is already written.
 int limits_and_small(tl_ctx *c, const char *who, uint32_t small_n, const float *xy, const float *dm_packed, uint32_t n, uint32_t *out_pos,

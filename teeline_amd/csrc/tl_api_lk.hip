@@ -31,7 +31,7 @@ int tlapi::build_candidates_dev(tl_ctx *c, const float *xy_host, const float2 *d
     }
     (void)xy_host;
     int rc;
-    const size_t nodes_b = (((size_t)n * sizeof(KdNode)) + 255) & ~(size_t)255;
+    const size_t nodes_b = up256((size_t)n * sizeof(KdNode));
     if ((rc = ensure(c, c->kd, nodes_b + kdtree_build_ws_bytes(n, nullptr)))) return rc;
     KdNode *nodes = (KdNode *)c->kd.p;
     HIPCHK(c, kdtree_build_dev(d_xy, n, (unsigned char *)c->kd.p + nodes_b, nodes, c->stream));
@@ -52,9 +52,9 @@ extern "C" int tl_build_candidates(tl_ctx *c, const float *xy, uint32_t n, uint3
     if (k > 64) return fail(c, TL_ERR_UNSUPPORTED, "tl_build_candidates: k=%u > 64 (the k-nearest buffer of a query lives in registers; the reference's k is unbounded)", k);
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensure(c, c->xy, (size_t)n * 8)) || (rc = ensure(c, c->misc, (size_t)n * k * 4))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    if ((rc = build_candidates_dev(c, xy, (const float2 *)c->xy.p, n, k, (uint32_t *)c->misc.p))) return rc;
+    const float2 *dxy = nullptr;
+    if ((rc = upload_xy(c, xy, n, &dxy)) || (rc = ensure(c, c->misc, (size_t)n * k * 4))) return rc;
+    if ((rc = build_candidates_dev(c, xy, dxy, n, k, (uint32_t *)c->misc.p))) return rc;
     HIPCHK(c, hipMemcpyAsync(out, c->misc.p, (size_t)n * k * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return TL_OK;
@@ -82,7 +82,7 @@ int tlapi::nn_seed_dev(tl_ctx *c, const float2 *d_xy, uint32_t n, uint32_t n_nea
             if (kk <= n - 1u && (size_t)n + 16 + (size_t)n * kk * 2u + 16 <= cap) { kint = kk; break; }
         k = kint;
     }
-    const size_t cand_b = ((size_t)n * (k ? k : 1) * 4 + 255) & ~(size_t)255;
+    const size_t cand_b = up256((size_t)n * (k ? k : 1) * 4);
     if ((rc = ensure(c, c->misc, cand_b))) return rc;
     uint32_t *d_cand = (uint32_t *)c->misc.p;
     if (k) HIPCHK(c, launch_knn(d_xy, n, k, d_cand, c->stream, knn_form(c)));
@@ -109,17 +109,11 @@ extern "C" int tl_nearest_neighbor(tl_ctx *c, const float *xy, const float *dm_p
     if (dm_packed) {
         if ((size_t)n + 1024 > (size_t)c->lds_bytes)
             return fail(c, TL_ERR_UNSUPPORTED, "nearest_neighbor: n=%u exceeds the LDS-resident visited flags (%d bytes of LDS)", n, c->lds_bytes);
-        const size_t b = (size_t)n * (n - 1) / 2 * 4;
-        if ((rc = ensure(c, c->dm, b))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->dm.p, dm_packed, b, hipMemcpyHostToDevice, c->stream));
-        ddm = (const float *)c->dm.p;
+        if ((rc = upload_dm(c, dm_packed, n, &ddm))) return rc;
         HIPCHK(c, hipEventRecord(c->ev0, c->stream));
         HIPCHK(c, launch_nn_seed_dm(ddm, n, (uint32_t *)c->out_pos.p, c->lds_bytes, c->stream));
     } else {
-        if (!xy) return fail(c, TL_ERR_BADARG, "tl_nearest_neighbor: xy is NULL");
-        if ((rc = ensure(c, c->xy, (size_t)n * 8))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        dxy = (const float2 *)c->xy.p;
+        if ((rc = upload_xy(c, xy, n, &dxy))) return rc;
         HIPCHK(c, hipEventRecord(c->ev0, c->stream));
         if ((rc = nn_seed_dev(c, dxy, n, n_nearest, (uint32_t *)c->out_pos.p))) {
             c->ev_valid = false;
@@ -179,9 +173,8 @@ static int lk_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
     const uint32_t k = o.n_nearest > n - 1 ? n - 1 : o.n_nearest;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t arr = up((size_t)n * 4);
-    const size_t o_cand = 0, o_tour = up((size_t)n * (k ? k : 1) * 4), o_alt = o_tour + arr, o_pos = o_alt + arr, o_next = o_pos + arr,
+    const size_t arr = up256((size_t)n * 4);
+    const size_t o_cand = 0, o_tour = up256((size_t)n * (k ? k : 1) * 4), o_alt = o_tour + arr, o_pos = o_alt + arr, o_next = o_pos + arr,
                  o_prev = o_next + arr, o_ids = o_prev + arr, o_best = o_ids + arr, o_cnt = o_best + arr, o_state = o_cnt + 256,
                  o_chains = o_state + 256;
     // default: scans spread over all CUs; TL_FLAG_LK_ONE_WORKGROUP runs the whole ILS in one persistent workgroup instead
@@ -200,7 +193,7 @@ static int lk_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed
     const uint32_t variant_flags = TL_FLAG_LK_ONE_WORKGROUP | TL_FLAG_LK_NO_SPLIT | TL_FLAG_LK_SPLIT2 | TL_FLAG_LK_NO_SUBCHAINS | TL_FLAG_LK_SEPARATE_PICK | TL_FLAG_LK_NO_GRAPH | TL_FLAG_LK_SEPARATE_STEP | TL_FLAG_LK_SCAN_PERSIST;
     const bool lk_small = ((tf & TL_FLAG_LK_SMALL) || (!((c->flags | tf) & variant_flags) && n <= small_max_n)) &&
                           lk_small_lds_bytes(n, k_small) + 4096 <= (size_t)c->lds_bytes;
-    // Small instances (round 5): the whole ILS as ONE persistent workgroup with every array in LDS and a level-synchronous search
+    // Small instances: the whole ILS as ONE persistent workgroup with every array in LDS and a level-synchronous search
     // (k_lk_ils, lk.hip) — no kernel boundary per round.  Wherever its state and its level queues fit one CU's LDS, up to the size
     // from which the chip-wide scans are faster (kLkIlsMaxN, measured: scripts/timing_lk_ils.py); TL_FLAG_LK_ILS_LDS: wherever it
     // fits; TL_FLAG_LK_CHIP_WIDE: never.
@@ -214,7 +207,7 @@ static int lk_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed
     const bool multi_cu = !(c->flags & TL_FLAG_LK_ONE_WORKGROUP) && !lk_small && !lk_ils;
     const size_t slot_words = deep ? tl_lk_deep::lk_chain_slot_words() : lk_chain_slot_words();
     const size_t sub_bytes = (deep ? tl_lk_deep::lk_sub_slot_words() : lk_sub_slot_words()) * 4;  // 64 at depth <= 6
-    const size_t o_pairmin = o_chains + (multi_cu ? up((size_t)2 * n * slot_words * 4) : 0);
+    const size_t o_pairmin = o_chains + (multi_cu ? up256((size_t)2 * n * slot_words * 4) : 0);
     const bool split_scan = multi_cu && max_depth_ge2_split(o.max_depth) && !(tf & TL_FLAG_LK_NO_SPLIT);
     // every successful sub-search keeps its chain (64 B) so that the pick step does not walk the winner again; sized for
     // 288 GB of HBM (45 MB at n = 13 509, k = 5), skipped beyond 4 GB
@@ -226,18 +219,18 @@ static int lk_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed
     const bool fused_pick = split_scan && (size_t)k * (k + 1) * (levels == 3u ? k + 1 : 1) <= 1024 &&
                             !(tf & (TL_FLAG_LK_SEPARATE_PICK | TL_FLAG_LK_NO_SUBCHAINS));
     const bool keep_sub = split_scan && !fused_pick && sub_b <= ((size_t)4 << 30) && !(tf & TL_FLAG_LK_NO_SUBCHAINS);
-    const size_t o_sub = o_pairmin + (split_scan ? up((size_t)2 * n * 4) : 0);
+    const size_t o_sub = o_pairmin + (split_scan ? up256((size_t)2 * n * 4) : 0);
     // k_lk_ils with speculative epochs: the candidates' distances and, per epoch of a batch, its final tour, length and counters
     const bool ils_spec = lk_ils && !(c->flags & TL_FLAG_LK_NO_SPECULATION);
     const size_t ils_lds = lk_ils ? (deep ? tl_lk_deep::lk_ils_lds_bytes(n, k_small, o.max_depth, ils_qcap) : lk_ils_lds_bytes(n, k_small, o.max_depth, ils_qcap)) : 0;
     const uint32_t ils_P = ils_spec ? (uint32_t)c->cus * (2 * ils_lds <= (size_t)c->lds_bytes ? 2u : 1u) : 0u;  // two epochs per CU where their images fit
-    const size_t o_ils_dc = o_sub + (keep_sub ? up(sub_b) : 0), o_ils_tour = o_ils_dc + (ils_spec ? up((size_t)n * k_small * 4) : 0),
-                 o_ils_dist = o_ils_tour + up((size_t)ils_P * n * 4), o_ils_cnt = o_ils_dist + up((size_t)ils_P * 4);
+    const size_t o_ils_dc = o_sub + (keep_sub ? up256(sub_b) : 0), o_ils_tour = o_ils_dc + (ils_spec ? up256((size_t)n * k_small * 4) : 0),
+                 o_ils_dist = o_ils_tour + up256((size_t)ils_P * n * 4), o_ils_cnt = o_ils_dist + up256((size_t)ils_P * 4);
     // the packed view of the chip-wide scan (LkViewPk): candidates with their distances, successor records
     const bool chip_step_form = fused_pick && levels == 3u && n >= 1500u && !(tf & TL_FLAG_LK_SEPARATE_STEP);
     const bool packed_view = chip_step_form && !(c->flags & TL_FLAG_LK_CLASSIC_VIEW);
-    const size_t o_pk_c = o_ils_cnt + up((size_t)ils_P * 32), o_pk_n = o_pk_c + (packed_view ? up((size_t)n * k * 8) : 0);
-    const size_t total = o_pk_n + (packed_view ? up((size_t)n * 16) : 0);
+    const size_t o_pk_c = o_ils_cnt + up256((size_t)ils_P * 32), o_pk_n = o_pk_c + (packed_view ? up256((size_t)n * k * 8) : 0);
+    const size_t total = o_pk_n + (packed_view ? up256((size_t)n * 16) : 0);
     // every mode / size check and every allocation comes before the first event record and the first enqueue: a rejected call
     // leaves the previous kernel sequence's event pair intact and nothing in flight
     // (the single-workgroup forms keep no snapshots on the device: a trace of theirs is the final best tour alone, below)
@@ -251,12 +244,8 @@ static int lk_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed
     unsigned char *w = (unsigned char *)c->work.p;
     HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     const float *ddm = nullptr;
-    if (dm_packed) {  // problem.distances of a GEO / EXPLICIT problem: the NN seed and the reported total read it
-        const size_t b = (size_t)n * (n - 1) / 2 * 4;
-        if ((rc = ensure(c, c->dm, b))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->dm.p, dm_packed, b, hipMemcpyHostToDevice, c->stream));
-        ddm = (const float *)c->dm.p;
-    }
+    // problem.distances of a GEO / EXPLICIT problem: the NN seed and the reported total read it
+    if (dm_packed && (rc = upload_dm(c, dm_packed, n, &ddm))) return rc;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     c->ev_valid = false;
     if (init_pos) {
@@ -409,51 +398,16 @@ static int lk_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed
         HIPCHK(c, deep ? tl_lk_deep::launch_lk_begin(G, c->stream) : launch_lk_begin(G, c->stream));
         auto lk_round = [&](uint32_t r) { return deep ? tl_lk_deep::launch_lk_round(G, c->stream, r) : launch_lk_round(G, c->stream, r); };
         LkState hs{};
-        // 64 rounds per poll of `finished` (the kernels are no-ops once it is set).  The first batch is enqueued launch by
-        // launch; a search that is still running after it replays the same 64 rounds as ONE hipGraph launch per poll — a round
-        // is 2-3 short kernels (tens of microseconds), and the host's per-launch cost and the gaps between separately
-        // enqueued kernels are a visible part of it.
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t gexec = nullptr;
-        bool first = true, graph_ok = !(tf & TL_FLAG_LK_NO_GRAPH);
+        RoundGraph batch(!(tf & TL_FLAG_LK_NO_GRAPH));  // 64 rounds (2-3 short kernels each) per poll of `finished`
         int rc_loop = TL_OK;
         for (;;) {
-            if (!first && graph_ok && !gexec) {
-                graph_ok = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                if (graph_ok) {
-                    hipError_t le = hipSuccess;
-                    for (int r = 0; r < 64 && le == hipSuccess; ++r) le = lk_round((uint32_t)r);
-                    const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
-                    graph_ok = le == hipSuccess && ce == hipSuccess && graph &&
-                               hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) == hipSuccess;
-                }
-                if (!graph_ok) {
-                    // separately enqueued launches from here on — after making sure the stream has left capture mode (a capture
-                    // that another thread's legacy-stream operation invalidated stays "active, invalidated" until it is ended)
-                    (void)hipGetLastError();
-                    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-                    if (hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
-                        hipGraph_t g2 = nullptr;
-                        (void)hipStreamEndCapture(c->stream, &g2);
-                        if (g2) (void)hipGraphDestroy(g2);
-                    }
-                    (void)hipGetLastError();
-                    if (graph) {
-                        (void)hipGraphDestroy(graph);
-                        graph = nullptr;
-                    }
-                }
-            }
-            hipError_t e = hipSuccess;
-            if (gexec) e = hipGraphLaunch(gexec, c->stream);
-            else for (int r = 0; r < 64 && e == hipSuccess; ++r) e = lk_round((uint32_t)r);
+            hipError_t e = batch.launch(c->stream, 64, lk_round);
             if (e == hipSuccess) e = hipMemcpyAsync(&hs, G.state, sizeof(hs), hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) {
                 rc_loop = fail(c, TL_ERR_HIP, "tl_lk: %s", hipGetErrorString(e));
                 break;
             }
-            first = false;
             if (live) {  // lin_kernighan.rs:71,90 send_progress(best_tour, best_dist), as the search goes
                 for (; delivered < hs.snaps; ++delivered) {
                     const uint32_t at = delivered % snap_cap;
@@ -472,8 +426,6 @@ static int lk_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed
             }
             if (hs.finished) break;
         }
-        if (gexec) (void)hipGraphExecDestroy(gexec);
-        if (graph) (void)hipGraphDestroy(graph);
         if (rc_loop != TL_OK) return rc_loop;
         if (hs.finished == 2u)
             return fail(c, TL_ERR_NO_CONVERGE, "tl_lk: an lk_pass does not terminate (the reference's loop cycles on this input: chains of rounded f32 gain that lead back to the same tour)");
@@ -526,10 +478,7 @@ static int lk_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed
         stats->candidates = cnt[1];
         stats->moves = cnt[2];
         stats->reversed = cnt[3];
-        double kms = 0;
-        tl_last_kernel_ms(c, &kms);
-        stats->kernel_ms = kms;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stamp_times(c, stats, t0);
     }
     return TL_OK;
 }

@@ -76,7 +76,7 @@ static int two_opt_enqueue(tl_ctx *c, const float2 *d_xy, const float *d_dm, uin
         // (the descents' per-city records are 264 bytes per city and descent: a batch that would need more than 8 GB of them runs without lists)
         const bool lists = !(c->flags & (TL_FLAG_NO_PRUNE | TL_FLAG_2OPT_NO_NL)) && (n >= TL_DM_LISTS_MIN_N || (c->flags & TL_FLAG_2OPT_NL_ALWAYS)) &&
                            two_opt_ref_dm_late_fits(n, c->lds_bytes) && two_opt_ref_dm_late_work_bytes(n, count) <= ((size_t)8 << 30);
-        const size_t full_bytes = ((size_t)n * n * 4 + 255u) & ~(size_t)255u;
+        const size_t full_bytes = up256((size_t)n * n * 4);
         if ((rc2 = ensure(c, c->dmfull, full_bytes + (lists ? dm_lists_ws_bytes(n) : 0u)))) return rc2;
         HIPCHK(c, launch_dm_expand_full(d_dm, n, (float *)c->dmfull.p, s));
         A.dm_full = (const float *)c->dmfull.p;
@@ -173,11 +173,11 @@ extern "C" int tl_two_opt_neighbour_lists(tl_ctx *c, const float *xy, uint32_t n
     if (n <= (uint32_t)kNlKB + 1u || n > 65535u) return fail(c, TL_ERR_UNSUPPORTED, "tl_two_opt_neighbour_lists: n=%u outside (%d, 65535]", n, kNlKB + 1);
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensure(c, c->xy, (size_t)n * 8)) || (rc = ensure(c, c->nl, two_opt_nl_ws_bytes(n))) || (rc = ws_order(c, c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    const float2 *dxy = nullptr;
+    if ((rc = ensure(c, c->nl, two_opt_nl_ws_bytes(n))) || (rc = ws_order(c, c->stream)) || (rc = upload_xy(c, xy, n, &dxy))) return rc;
     TwoOptNl L{};
     HIPCHK(c, hipMemsetAsync(c->nl.p, 0, 256, c->stream));  // (always a fresh build here)
-    HIPCHK(c, launch_two_opt_nl_build((const float2 *)c->xy.p, n, c->nl.p, true, &L, c->stream, form == 1 ? 1 : 0));
+    HIPCHK(c, launch_two_opt_nl_build(dxy, n, c->nl.p, true, &L, c->stream, form == 1 ? 1 : 0));
     HIPCHK(c, hipMemcpyAsync(rec, L.rec, (size_t)n * 128, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(dkb2, L.dkb2, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(knn_b, L.knn_b, (size_t)n * kNlKB * 2, hipMemcpyDeviceToHost, c->stream));
@@ -201,7 +201,8 @@ extern "C" int tl_two_opt_batch_dev(tl_ctx *c, const float *d_xy, uint32_t n, co
                            count, mode, d_out_pos, d_out_cost, d_out_stats, s);
 }
 
-static void fill_stats(tl_stats *st, uint32_t n, const uint64_t *raw, uint32_t count, double kernel_ms, double total_ms)
+// zeroes *st and sums the descents' kernel-side counters into it (the times: stamp_times, or the batch entry's own)
+static void fill_stats(tl_stats *st, uint32_t n, const uint64_t *raw, uint32_t count)
 {
     if (!st) return;
     memset(st, 0, sizeof(*st));
@@ -212,12 +213,43 @@ static void fill_stats(tl_stats *st, uint32_t n, const uint64_t *raw, uint32_t c
         st->reversed += raw[TL_STATS_STRIDE * r + 2];
     }
     st->candidates = st->sweeps * per_sweep;
-    st->kernel_ms = kernel_ms;
-    st->total_ms = total_ms;
 }
 
 static int two_opt_best_sweep(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos,
                               uint32_t *out_pos, float *out_cost, tl_stats *stats);
+
+// What the two HBM forms (two_opt_large.hip, two_opt_best.hip) share: the workspace in c->work begins perm | P | tbox | tmsq, on
+// the padded lengths both kernels' tiles assume.  `end`: where the form's own regions begin.
+struct HbmTourWs {
+    uint32_t n_pad, ntile_cap;
+    size_t o_P, o_box, o_msq, end;
+    explicit HbmTourWs(uint32_t n)
+        : n_pad(((n + 64u + 63u) / 64u) * 64u), ntile_cap((((n_pad >> 6) + 63u) / 64u) * 64u), o_P(up256((size_t)n * 4)),
+          o_box(up256(o_P + (size_t)(n_pad + 1) * 8)), o_msq(up256(o_box + (size_t)ntile_cap * 16)), end(up256(o_msq + (size_t)ntile_cap * 4))
+    {
+    }
+    template <class Args>
+    void bind(Args &A, const tl_ctx *c, uint32_t n) const
+    {
+        unsigned char *w = (unsigned char *)c->work.p;
+        A.xy = (const float2 *)c->xy.p;
+        A.perm = (uint32_t *)w;
+        A.P = (float2 *)(w + o_P);
+        A.tbox = (float4 *)(w + o_box);
+        A.tmsq = (float *)(w + o_msq);
+        A.n = n;
+        A.n_pad = n_pad;
+        A.ntile_cap = ntile_cap;
+    }
+};
+
+// the instance into c->xy: once for the two_opt_ref_large calls of a batch (the first of them waits for the copy)
+static int hbm_upload_xy(tl_ctx *c, const float *xy, uint32_t n)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    const float2 *dxy = nullptr;
+    return upload_xy(c, xy, n, &dxy);
+}
 
 // REF_ORDER for n beyond the LDS-resident kernel: tour state in HBM, scan spread over the chip (two_opt_large.hip)
 // xy == NULL: the instance already lies in c->xy (hbm_upload_xy: the batch entries upload it once, not once per descent)
@@ -228,31 +260,13 @@ static int two_opt_ref_large(tl_ctx *c, const float *xy, uint32_t n, const uint3
     HIPCHK(c, hipSetDevice(c->device));
     c->stats_valid = false;  // (this form keeps its counters in the workspace: nothing for tl_two_opt_last_counters)
     int rc;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const uint32_t n_pad = ((n + 64u + 63u) / 64u) * 64u, ntile_cap = (((n_pad >> 6) + 63u) / 64u) * 64u;
-    const size_t o_perm = 0, o_P = up((size_t)n * 4), o_box = up(o_P + (size_t)(n_pad + 1) * 8), o_msq = up(o_box + (size_t)ntile_cap * 16),
-                 o_st = up(o_msq + (size_t)ntile_cap * 4), total = o_st + 256;
-    if ((rc = ensure(c, c->xy, (size_t)n * 8)) || (rc = ensure(c, c->work, total)) || (rc = ensure(c, c->out_cost, 4))) return rc;
-    unsigned char *w = (unsigned char *)c->work.p;
-    std::vector<uint32_t> ident;
-    if (!init_pos) {
-        ident.resize(n);
-        for (uint32_t i = 0; i < n; ++i) ident[i] = i;
-        init_pos = ident.data();
-    }
-    if (xy) HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w + o_perm, init_pos, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const HbmTourWs L(n);
+    if ((rc = ensure(c, c->work, L.end + 256)) || (rc = ensure(c, c->out_cost, 4)) || (xy && (rc = hbm_upload_xy(c, xy, n))) ||
+        (rc = upload_start_sync(c, init_pos, n, c->work.p)))
+        return rc;
     LargeTwoOptArgs A{};
-    A.xy = (const float2 *)c->xy.p;
-    A.perm = (uint32_t *)(w + o_perm);
-    A.P = (float2 *)(w + o_P);
-    A.tbox = (float4 *)(w + o_box);
-    A.tmsq = (float *)(w + o_msq);
-    A.state = (LargeTwoOptState *)(w + o_st);
-    A.n = n;
-    A.n_pad = n_pad;
-    A.ntile_cap = ntile_cap;
+    L.bind(A, c, n);
+    A.state = (LargeTwoOptState *)((unsigned char *)c->work.p + L.end);
     A.max_sweeps = TL_MAX_SWEEPS;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     HIPCHK(c, launch_large_two_opt_init(A, c->stream));
@@ -278,27 +292,65 @@ static int two_opt_ref_large(tl_ctx *c, const float *xy, uint32_t n, const uint3
         stats->moves = hs.moves;
         stats->reversed = hs.reversed;
         stats->candidates = (uint64_t)hs.sweeps * ((uint64_t)(n - 3) * (n - 2) / 2);
-        double kms = 0;
-        tl_last_kernel_ms(c, &kms);
-        stats->kernel_ms = kms;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stamp_times(c, stats, t0);
     }
-    return TL_OK;
-}
-
-// the instance into c->xy, once, for the two_opt_ref_large calls of a batch (the first of them waits for the copy)
-static int hbm_upload_xy(tl_ctx *c, const float *xy, uint32_t n)
-{
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = ensure(c, c->xy, (size_t)n * 8))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     return TL_OK;
 }
 
 // the batch entries' branch through the HBM form: beyond the LDS-resident descent, or wherever TL_FLAG_2OPT_FORCE_HBM asks for it
 // (n == 3 has no candidate: the LDS kernel's empty descent serves it)
 static bool batch_runs_hbm_form(const tl_ctx *c, uint32_t n) { return n > lds_max_n(c->lds_bytes) || ((c->flags & TL_FLAG_2OPT_FORCE_HBM) && n >= 4u); }
+
+// The LDS-resident REF_ORDER descent of one tour, on coordinates or on the matrix, behind tl_two_opt and tl_two_opt_trace (the
+// entries validate and route).  Both inputs are uploaded where both are given: the matrix drives the descent, but c->xy is what
+// the `same coordinates` check of the neighbour lists' cache (c->nl) compares against.
+// move_log (trace only): the descent's moves into c->work, the first log_cap of them to the caller, *log_len = all of them.
+static int two_opt_lds_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t *out_pos,
+                           float *out_cost, tl_stats *stats, uint32_t *move_log, uint32_t log_cap, uint32_t *log_len)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->out_pos, (size_t)n * 4)) || (rc = ensure(c, c->out_cost, 4)) || (rc = ensure(c, c->out_stats, TL_STATS_STRIDE * 8)) ||
+        (move_log && (rc = ensure(c, c->work, (size_t)(log_cap ? log_cap : 1) * 4))))
+        return rc;
+    const float2 *dxy = nullptr;
+    const float *ddm = nullptr;
+    if ((dm_packed && (rc = upload_dm(c, dm_packed, n, &ddm))) || (xy && (rc = upload_xy(c, xy, n, &dxy)))) return rc;
+    const uint32_t *dinit = nullptr;
+    if (init_pos) {
+        if ((rc = ensure(c, c->init, (size_t)n * 4))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->init.p, init_pos, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        dinit = (const uint32_t *)c->init.p;
+    }
+    if (move_log) HIPCHK(c, hipMemsetAsync(c->out_stats.p, 0, TL_STATS_STRIDE * 8, c->stream));
+    if ((rc = two_opt_enqueue(c, dxy, ddm, n, dinit, dinit ? TL_INIT_ARRAY : TL_INIT_IDENTITY, 0, 0, 1, TL_MODE_REF_ORDER, (uint32_t *)c->out_pos.p,
+                              (float *)c->out_cost.p, (uint64_t *)c->out_stats.p, c->stream, move_log ? (uint32_t *)c->work.p : nullptr, log_cap)))
+        return rc;
+    uint64_t raw[TL_STATS_STRIDE];
+    float cost = 0.f;
+    HIPCHK(c, hipMemcpyAsync(out_pos, c->out_pos.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&cost, c->out_cost.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(raw, c->out_stats.p, TL_STATS_STRIDE * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->stats_valid = true;
+    if (raw[3] == 2) return fail(c, TL_ERR_BADARG, "two_opt: the initial tour holds a position >= n");
+    if (raw[3] != 0) return fail(c, TL_ERR_NO_CONVERGE, "two_opt: sweep cap reached");
+    if (move_log) {
+        *log_len = (uint32_t)raw[15];  // words: moves applied + one mark per sweep after the first; more than log_cap: the log holds the first log_cap
+        const uint32_t have = *log_len < log_cap ? *log_len : log_cap;
+        // (on the context's own stream: a synchronous hipMemcpy goes through the legacy default stream, which may not meet another
+        //  thread's capturing stream — tl_lk records its round loop as a hipGraph; found by tests/test_gpu_threads.py)
+        if (have) {
+            HIPCHK(c, hipMemcpyAsync(move_log, c->work.p, (size_t)have * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+    }
+    if (out_cost) *out_cost = cost;
+    fill_stats(stats, n, raw, 1);
+    stamp_times(c, stats, t0);
+    return TL_OK;
+}
 
 extern "C" int tl_two_opt(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, int mode,
                           uint32_t *out_pos, float *out_cost, tl_stats *stats)
@@ -317,46 +369,7 @@ extern "C" int tl_two_opt(tl_ctx *c, const float *xy, uint32_t n, const float *d
         }
         return two_opt_ref_large(c, xy, n, init_pos, out_pos, out_cost, stats);
     }
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = ensure(c, c->out_pos, (size_t)n * 4)) || (rc = ensure(c, c->out_cost, 4)) || (rc = ensure(c, c->out_stats, TL_STATS_STRIDE * 8))) return rc;
-    const float2 *dxy = nullptr;
-    const float *ddm = nullptr;
-    if (dm_packed) {
-        const size_t b = (size_t)n * (n - 1) / 2 * 4;
-        if ((rc = ensure(c, c->dm, b))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->dm.p, dm_packed, b, hipMemcpyHostToDevice, c->stream));
-        ddm = (const float *)c->dm.p;
-    }
-    if (xy) {
-        if ((rc = ensure(c, c->xy, (size_t)n * 8))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        dxy = (const float2 *)c->xy.p;
-    }
-    const uint32_t *dinit = nullptr;
-    if (init_pos) {
-        if ((rc = ensure(c, c->init, (size_t)n * 4))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->init.p, init_pos, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        dinit = (const uint32_t *)c->init.p;
-    }
-    if ((rc = two_opt_enqueue(c, dxy, ddm, n, dinit, dinit ? TL_INIT_ARRAY : TL_INIT_IDENTITY, 0, 0, 1, mode,
-                              (uint32_t *)c->out_pos.p, (float *)c->out_cost.p, (uint64_t *)c->out_stats.p, c->stream)))
-        return rc;
-    uint64_t raw[TL_STATS_STRIDE];
-    float cost = 0.f;
-    HIPCHK(c, hipMemcpyAsync(out_pos, c->out_pos.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&cost, c->out_cost.p, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(raw, c->out_stats.p, TL_STATS_STRIDE * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->stats_valid = true;
-    if (raw[3] == 2) return fail(c, TL_ERR_BADARG, "two_opt: the initial tour holds a position >= n");
-    if (raw[3] != 0) return fail(c, TL_ERR_NO_CONVERGE, "two_opt: sweep cap reached");
-    if (out_cost) *out_cost = cost;
-    double kms = 0;
-    tl_last_kernel_ms(c, &kms);
-    fill_stats(stats, n, raw, 1, kms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    return TL_OK;
+    return two_opt_lds_run(c, xy, n, dm_packed, init_pos, out_pos, out_cost, stats, nullptr, 0, nullptr);
 }
 
 // tl_two_opt + the list of the moves it applied, in the reference's order: what a caller that was handed a progress channel
@@ -373,57 +386,7 @@ extern "C" int tl_two_opt_trace(tl_ctx *c, const float *xy, uint32_t n, const fl
     if (init_pos && !is_permutation(init_pos, n)) return fail(c, TL_ERR_BADARG, "tl_two_opt_trace: init tour is not a permutation of 0..n-1");
     if (!dm_packed && (n > lds_max_n(c->lds_bytes) || n > 65535u))
         return fail(c, TL_ERR_UNSUPPORTED, "tl_two_opt_trace: n=%u exceeds the LDS-resident descent (%u): no move log beyond it", n, lds_max_n(c->lds_bytes));
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = ensure(c, c->out_pos, (size_t)n * 4)) || (rc = ensure(c, c->out_cost, 4)) || (rc = ensure(c, c->out_stats, TL_STATS_STRIDE * 8)) ||
-        (rc = ensure(c, c->work, (size_t)(log_cap ? log_cap : 1) * 4)))
-        return rc;
-    const float2 *dxy = nullptr;
-    const float *ddm = nullptr;
-    if (dm_packed) {
-        const size_t b = (size_t)n * (n - 1) / 2 * 4;
-        if ((rc = ensure(c, c->dm, b))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->dm.p, dm_packed, b, hipMemcpyHostToDevice, c->stream));
-        ddm = (const float *)c->dm.p;
-    }
-    if (xy) {
-        if ((rc = ensure(c, c->xy, (size_t)n * 8))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        dxy = (const float2 *)c->xy.p;
-    }
-    const uint32_t *dinit = nullptr;
-    if (init_pos) {
-        if ((rc = ensure(c, c->init, (size_t)n * 4))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->init.p, init_pos, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        dinit = (const uint32_t *)c->init.p;
-    }
-    HIPCHK(c, hipMemsetAsync(c->out_stats.p, 0, TL_STATS_STRIDE * 8, c->stream));
-    if ((rc = two_opt_enqueue(c, dxy, ddm, n, dinit, dinit ? TL_INIT_ARRAY : TL_INIT_IDENTITY, 0, 0, 1, TL_MODE_REF_ORDER,
-                              (uint32_t *)c->out_pos.p, (float *)c->out_cost.p, (uint64_t *)c->out_stats.p, c->stream, (uint32_t *)c->work.p, log_cap)))
-        return rc;
-    uint64_t raw[TL_STATS_STRIDE];
-    float cost = 0.f;
-    HIPCHK(c, hipMemcpyAsync(out_pos, c->out_pos.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&cost, c->out_cost.p, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(raw, c->out_stats.p, TL_STATS_STRIDE * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->stats_valid = true;
-    if (raw[3] == 2) return fail(c, TL_ERR_BADARG, "two_opt: the initial tour holds a position >= n");
-    if (raw[3] != 0) return fail(c, TL_ERR_NO_CONVERGE, "two_opt: sweep cap reached");
-    *log_len = (uint32_t)raw[15];  // words: moves applied + one mark per sweep after the first; more than log_cap: the log holds the first log_cap
-    const uint32_t have = *log_len < log_cap ? *log_len : log_cap;
-    // (on the context's own stream: a synchronous hipMemcpy goes through the legacy default stream, which may not meet another
-    //  thread's capturing stream — tl_lk records its round loop as a hipGraph; found by tests/test_gpu_threads.py)
-    if (have) {
-        HIPCHK(c, hipMemcpyAsync(move_log, c->work.p, (size_t)have * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    if (out_cost) *out_cost = cost;
-    double kms = 0;
-    tl_last_kernel_ms(c, &kms);
-    fill_stats(stats, n, raw, 1, kms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    return TL_OK;
+    return two_opt_lds_run(c, xy, n, dm_packed, init_pos, out_pos, out_cost, stats, move_log, log_cap, log_len);
 }
 
 extern "C" uint64_t tl_pack_cost_key(float cost, uint32_t restart)
@@ -438,11 +401,11 @@ static int multistart_begin(tl_ctx *c, const float *xy, uint32_t n, uint64_t see
 {
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensure(c, c->xy, (size_t)n * 8)) || (rc = ensure(c, c->out_pos, (size_t)count * n * 4)) ||
-        (rc = ensure(c, c->out_cost, (size_t)count * 4)) || (rc = ensure(c, c->out_stats, (size_t)count * TL_STATS_STRIDE * 8)))
+    const float2 *dxy = nullptr;
+    if ((rc = ensure(c, c->out_pos, (size_t)count * n * 4)) || (rc = ensure(c, c->out_cost, (size_t)count * 4)) ||
+        (rc = ensure(c, c->out_stats, (size_t)count * TL_STATS_STRIDE * 8)) || (rc = upload_xy(c, xy, n, &dxy)))
         return rc;
-    HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    return two_opt_enqueue(c, (const float2 *)c->xy.p, nullptr, n, nullptr, TL_INIT_SEEDED, seed, first, count, mode,
+    return two_opt_enqueue(c, dxy, nullptr, n, nullptr, TL_INIT_SEEDED, seed, first, count, mode,
                            (uint32_t *)c->out_pos.p, (float *)c->out_cost.p, (uint64_t *)c->out_stats.p, c->stream);
 }
 
@@ -451,7 +414,7 @@ struct ShardBest {
     uint32_t local = 0;  // index inside the shard
 };
 
-static int multistart_finish(tl_ctx *c, uint32_t n, uint32_t first, uint32_t count, float *costs /*count*/, uint64_t *raw /*count x stride*/,
+static int multistart_finish(tl_ctx *c, uint32_t first, uint32_t count, float *costs /*count*/, uint64_t *raw /*count x stride*/,
                              ShardBest &best)
 {
     HIPCHK(c, hipSetDevice(c->device));
@@ -467,8 +430,23 @@ static int multistart_finish(tl_ctx *c, uint32_t n, uint32_t first, uint32_t cou
             best.local = r;
         }
     }
-    (void)n;
     return TL_OK;
+}
+
+// the failure of device d's shard, reported where the caller reads it: on ctxs[0]
+static int shard_fail(tl_ctx *const *ctxs, int d, int rc)
+{
+    if (d) fail(ctxs[0], rc, "device shard %d: %s", d, ctxs[d]->err.c_str());
+    return rc;
+}
+
+// the HBM branches of the batch entries run their descents one after the other: the counters add up (the times are the branch's own)
+static void add_counters(tl_stats &acc, const tl_stats &st1)
+{
+    acc.sweeps += st1.sweeps;
+    acc.moves += st1.moves;
+    acc.reversed += st1.reversed;
+    acc.candidates += st1.candidates;
 }
 
 extern "C" int tl_two_opt_multistart(tl_ctx *c, const float *xy, uint32_t n, uint64_t seed, uint32_t first, uint32_t count,
@@ -605,7 +583,7 @@ extern "C" int tl_two_opt_multistart_devices(tl_ctx *const *ctxs, int n_ctxs, co
     for (int d = 0; d < n_ctxs; ++d) (void)tl_multistart_shard(first, count, n_ctxs, d, &shard[d].first, &shard[d].count);
     int rc;
     if (batch_runs_hbm_form(c0, n)) {
-        // beyond the LDS-resident descent (round 5), or TL_FLAG_2OPT_FORCE_HBM on ctxs[0]: the restarts one after the other
+        // beyond the LDS-resident descent, or TL_FLAG_2OPT_FORCE_HBM on ctxs[0]: the restarts one after the other
         // through the HBM form, each shard on its own context — the same start permutations, so the same tours as a (hypothetical) batch
         // would give.  The shards, too, run one after the other (two_opt_ref_large polls its descent on the calling thread): kernel_ms is
         // the largest of the shards' summed device times — the slowest shard's, what devices side by side would wait for — and
@@ -625,10 +603,7 @@ extern "C" int tl_two_opt_multistart_devices(tl_ctx *const *ctxs, int n_ctxs, co
                 tl_stats st1{};
                 if ((rc = two_opt_ref_large(ctxs[d], nullptr, n, perm.data(), pos.data(), &cst, &st1))) break;
                 costs[r - first] = cst;
-                acc.sweeps += st1.sweeps;
-                acc.moves += st1.moves;
-                acc.reversed += st1.reversed;
-                acc.candidates += st1.candidates;
+                add_counters(acc, st1);
                 shard_ms += st1.kernel_ms;
                 const uint64_t key = tl_pack_cost_key(cst, r);
                 if (key < bestkey) {
@@ -636,10 +611,7 @@ extern "C" int tl_two_opt_multistart_devices(tl_ctx *const *ctxs, int n_ctxs, co
                     bestpos = pos;
                 }
             }
-            if (rc) {
-                if (d) fail(c0, rc, "device shard %d: %s", d, ctxs[d]->err.c_str());
-                return rc;
-            }
+            if (rc) return shard_fail(ctxs, d, rc);
             acc.kernel_ms = shard_ms > acc.kernel_ms ? shard_ms : acc.kernel_ms;
         }
         memcpy(out_best_pos, bestpos.data(), (size_t)n * 4);
@@ -654,10 +626,7 @@ extern "C" int tl_two_opt_multistart_devices(tl_ctx *const *ctxs, int n_ctxs, co
         return TL_OK;
     }
     for (int d = 0; d < n_ctxs; ++d)
-        if (shard[d].count && (rc = multistart_begin(ctxs[d], xy, n, seed, shard[d].first, shard[d].count, mode))) {
-            if (d) fail(c0, rc, "device shard %d: %s", d, ctxs[d]->err.c_str());
-            return rc;
-        }
+        if (shard[d].count && (rc = multistart_begin(ctxs[d], xy, n, seed, shard[d].first, shard[d].count, mode))) return shard_fail(ctxs, d, rc);
     std::vector<float> costs(count);
     std::vector<uint64_t> raw((size_t)count * TL_STATS_STRIDE);
     ShardBest best;
@@ -667,10 +636,8 @@ extern "C" int tl_two_opt_multistart_devices(tl_ctx *const *ctxs, int n_ctxs, co
         if (!shard[d].count) continue;
         const uint32_t off = shard[d].first - first;
         ShardBest b;
-        if ((rc = multistart_finish(ctxs[d], n, shard[d].first, shard[d].count, costs.data() + off, raw.data() + (size_t)off * TL_STATS_STRIDE, b))) {
-            if (d) fail(c0, rc, "device shard %d: %s", d, ctxs[d]->err.c_str());
-            return rc;
-        }
+        if ((rc = multistart_finish(ctxs[d], shard[d].first, shard[d].count, costs.data() + off, raw.data() + (size_t)off * TL_STATS_STRIDE, b)))
+            return shard_fail(ctxs, d, rc);
         if (b.key < best.key) {
             best = b;
             best_dev = d;
@@ -738,7 +705,11 @@ extern "C" int tl_two_opt_multistart_devices(tl_ctx *const *ctxs, int n_ctxs, co
     if (out_best_cost) *out_best_cost = costs[best_restart - first];
     if (out_best_restart) *out_best_restart = best_restart;
     if (out_costs) memcpy(out_costs, costs.data(), (size_t)count * 4);
-    fill_stats(stats, n, raw.data(), count, kms_max, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    fill_stats(stats, n, raw.data(), count);
+    if (stats) {
+        stats->kernel_ms = kms_max;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
     return TL_OK;
 }
 
@@ -767,10 +738,7 @@ extern "C" int tl_two_opt_population(tl_ctx *c, const float *xy, uint32_t n, con
             tl_stats st1{};
             if ((rc = two_opt_ref_large(c, nullptr, n, init_pos + (size_t)r * n, out_pos + (size_t)r * n, &cst, &st1))) return rc;
             if (out_costs) out_costs[r] = cst;
-            acc.sweeps += st1.sweeps;
-            acc.moves += st1.moves;
-            acc.reversed += st1.reversed;
-            acc.candidates += st1.candidates;
+            add_counters(acc, st1);
             acc.kernel_ms += st1.kernel_ms;
         }
         if (stats) {
@@ -779,20 +747,14 @@ extern "C" int tl_two_opt_population(tl_ctx *c, const float *xy, uint32_t n, con
         }
         return TL_OK;
     }
-    const size_t dm_bytes = dm_packed ? (size_t)n * (n - 1) / 2 * 4 : 0;
     if ((rc = ensure(c, c->init, (size_t)count * n * 4)) || (rc = ensure(c, c->out_pos, (size_t)count * n * 4)) ||
         (rc = ensure(c, c->out_cost, (size_t)count * 4)) || (rc = ensure(c, c->out_stats, (size_t)count * TL_STATS_STRIDE * 8)))
         return rc;
-    if (dm_packed) {
-        if ((rc = ensure(c, c->dm, dm_bytes))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->dm.p, dm_packed, dm_bytes, hipMemcpyHostToDevice, c->stream));
-    } else {
-        if ((rc = ensure(c, c->xy, (size_t)n * 8))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    }
+    const float2 *dxy = nullptr;
+    const float *ddm = nullptr;
+    if ((rc = upload_input(c, xy, dm_packed, n, &dxy, &ddm))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->init.p, init_pos, (size_t)count * n * 4, hipMemcpyHostToDevice, c->stream));
-    if ((rc = two_opt_enqueue(c, dm_packed ? nullptr : (const float2 *)c->xy.p, dm_packed ? (const float *)c->dm.p : nullptr, n,
-                              (const uint32_t *)c->init.p, TL_INIT_ARRAY, 0, 0, count, TL_MODE_REF_ORDER, (uint32_t *)c->out_pos.p,
+    if ((rc = two_opt_enqueue(c, dxy, ddm, n, (const uint32_t *)c->init.p, TL_INIT_ARRAY, 0, 0, count, TL_MODE_REF_ORDER, (uint32_t *)c->out_pos.p,
                               (float *)c->out_cost.p, (uint64_t *)c->out_stats.p, c->stream)))
         return rc;
     std::vector<uint64_t> raw((size_t)count * TL_STATS_STRIDE);
@@ -805,9 +767,8 @@ extern "C" int tl_two_opt_population(tl_ctx *c, const float *xy, uint32_t n, con
     for (uint32_t r = 0; r < count; ++r)
         if (raw[TL_STATS_STRIDE * r + 3] != 0) return fail(c, TL_ERR_NO_CONVERGE, "two_opt: sweep cap reached in tour %u", r);
     if (out_costs) memcpy(out_costs, costs.data(), (size_t)count * 4);
-    double kms = 0;
-    tl_last_kernel_ms(c, &kms);
-    fill_stats(stats, n, raw.data(), count, kms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    fill_stats(stats, n, raw.data(), count);
+    stamp_times(c, stats, t0);
     return TL_OK;
 }
 
@@ -824,92 +785,36 @@ static int two_opt_best_sweep(tl_ctx *c, const float *xy, uint32_t n, const floa
     c->stats_valid = false;  // (this form keeps its counters in the workspace: nothing for tl_two_opt_last_counters)
     if (stats) memset(stats, 0, sizeof(*stats));
     int rc;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const uint32_t n_pad = ((n + 64u + 63u) / 64u) * 64u, ntile_cap = (((n_pad >> 6) + 63u) / 64u) * 64u;
+    const HbmTourWs L(n);
     const uint32_t nblocks = n >= 4 ? best_sweep_scan_blocks(n) : 1;
-    const size_t o_perm = 0, o_P = up((size_t)n * 4), o_box = up(o_P + (size_t)(n_pad + 1) * 8), o_msq = up(o_box + (size_t)ntile_cap * 16),
-                 o_par = up(o_msq + (size_t)ntile_cap * 4), o_rk = up(o_par + (size_t)nblocks * 8), o_cnt = up(o_rk + (size_t)n * 8), total = o_cnt + 256;
-    if ((rc = ensure(c, c->xy, (size_t)n * 8)) || (rc = ensure(c, c->work, total)) || (rc = ensure(c, c->out_cost, 4))) return rc;
+    const size_t o_par = L.end, o_rk = up256(o_par + (size_t)nblocks * 8), o_cnt = up256(o_rk + (size_t)n * 8), total = o_cnt + 256;
+    if ((rc = ensure(c, c->work, total)) || (rc = ensure(c, c->out_cost, 4)) || (rc = hbm_upload_xy(c, xy, n))) return rc;
     unsigned char *w = (unsigned char *)c->work.p;
-    std::vector<uint32_t> ident;
-    if (!init_pos) {
-        ident.resize(n);
-        for (uint32_t i = 0; i < n; ++i) ident[i] = i;
-        init_pos = ident.data();
-    }
-    HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w + o_perm, init_pos, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(w + o_cnt, 0, 128, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = upload_start_sync(c, init_pos, n, w))) return rc;
     BestSweepArgs A{};
-    A.xy = (const float2 *)c->xy.p;
-    A.perm = (uint32_t *)(w + o_perm);
-    A.P = (float2 *)(w + o_P);
-    A.tbox = (float4 *)(w + o_box);
-    A.tmsq = (float *)(w + o_msq);
+    L.bind(A, c, n);
     A.partials = (unsigned long long *)(w + o_par);
     A.rowkey = (unsigned long long *)(w + o_rk);
     A.move = (uint32_t *)(w + o_cnt + 64);  // (zeroed with the counters: no move yet)
     A.counters = (uint64_t *)(w + o_cnt);
-    A.n = n;
-    A.n_pad = n_pad;
-    A.ntile_cap = ntile_cap;
     uint64_t cnt[4] = {1, 0, 1, 0};  // n == 3: one empty sweep
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (n >= 4) {
         HIPCHK(c, launch_best_sweep_init(A, c->stream));
         const uint64_t cap = 64ull * n + 1024;
-        // 64 sweeps (scan + apply) per poll of the done flag; after the first batch the same 64 sweeps replay as ONE hipGraph launch — a
-        // sweep is two short dependent kernels, and what it costs is mostly the gaps between separately enqueued launches (as in tl_lk)
-        constexpr int kSweepsPerPoll = 64;
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t gexec = nullptr;
-        bool first = true, graph_ok = true;
-        int rc_loop = TL_OK;
+        RoundGraph batch;  // 64 sweeps (scan + apply: two short dependent kernels) per poll of the done flag
         for (;;) {
-            if (!first && graph_ok && !gexec) {
-                graph_ok = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                if (graph_ok) {
-                    hipError_t le = hipSuccess;
-                    for (int r = 0; r < kSweepsPerPoll && le == hipSuccess; ++r) le = launch_best_sweep_round(A, c->stream);
-                    const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
-                    graph_ok = le == hipSuccess && ce == hipSuccess && graph && hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) == hipSuccess;
-                }
-                if (!graph_ok) {  // separately enqueued launches from here on, after making sure the stream has left capture mode
-                    (void)hipGetLastError();
-                    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-                    if (hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
-                        hipGraph_t g2 = nullptr;
-                        (void)hipStreamEndCapture(c->stream, &g2);
-                        if (g2) (void)hipGraphDestroy(g2);
-                    }
-                    (void)hipGetLastError();
-                    if (graph) {
-                        (void)hipGraphDestroy(graph);
-                        graph = nullptr;
-                    }
-                }
-            }
-            hipError_t e = hipSuccess;
-            if (gexec) e = hipGraphLaunch(gexec, c->stream);
-            else for (int r = 0; r < kSweepsPerPoll && e == hipSuccess; ++r) e = launch_best_sweep_round(A, c->stream);  // kernels no-op once done
+            hipError_t e = batch.launch(c->stream, 64, [&](uint32_t) { return launch_best_sweep_round(A, c->stream); });
             if (e == hipSuccess) e = hipMemcpyAsync(cnt, A.counters, 32, hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
-                rc_loop = fail(c, TL_ERR_HIP, "two_opt (BEST_SWEEP): %s", hipGetErrorString(e));
-                break;
+                return fail(c, TL_ERR_HIP, "two_opt (BEST_SWEEP): %s", hipGetErrorString(e));
             }
-            first = false;
             if (cnt[2]) break;
-            if (cnt[0] > cap) {
-                rc_loop = fail(c, TL_ERR_NO_CONVERGE, "two_opt (BEST_SWEEP): sweep cap reached");
-                break;
-            }
+            if (cnt[0] > cap) return fail(c, TL_ERR_NO_CONVERGE, "two_opt (BEST_SWEEP): sweep cap reached");
         }
-        if (gexec) (void)hipGraphExecDestroy(gexec);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (rc_loop != TL_OK) return rc_loop;
     }
     HIPCHK(c, launch_tour_length(A.xy, nullptr, n, A.perm, (float *)c->out_cost.p, c->stream));
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
@@ -924,10 +829,7 @@ static int two_opt_best_sweep(tl_ctx *c, const float *xy, uint32_t n, const floa
         stats->moves = cnt[1];
         stats->reversed = cnt[3];
         stats->candidates = cnt[0] * (n >= 4 ? (uint64_t)(n - 3) * (n - 2) / 2 : 0);
-        double kms = 0;
-        tl_last_kernel_ms(c, &kms);
-        stats->kernel_ms = kms;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stamp_times(c, stats, t0);
     }
     return TL_OK;
 }
