@@ -74,7 +74,7 @@ uint32_t lds_max_n(int lds_bytes)
     uint32_t lo = 0, hi = 65535;  // u16 tour entries, (i<<16|j) keys
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (two_opt_ref_lds_bytes(mid, nullptr, TL_TWO_OPT_NT) <= (size_t)lds_bytes) lo = mid;
+        if (two_opt_ref_lds_bytes(mid, nullptr) <= (size_t)lds_bytes) lo = mid;
         else hi = mid - 1;
     }
     return lo;

@@ -113,7 +113,7 @@ struct TwoOptBatchArgs {
 };
 
 // two_opt_ref.hip
-size_t two_opt_ref_lds_bytes(uint32_t n, uint32_t *n_pad_out, int nt);
+size_t two_opt_ref_lds_bytes(uint32_t n, uint32_t *n_pad_out);
 size_t two_opt_ref_nl_lds_bytes(uint32_t n);  // ... with the neighbour-list state (city -> position table, long list) beside the tour
 // would a batch of `count` descents run in the form that reads neighbour lists (16 waves, float2 points, lists + tour fit the LDS)?
 bool two_opt_ref_nl_applies(uint32_t n, uint32_t count, int cus, int lds_budget, int force_nt);

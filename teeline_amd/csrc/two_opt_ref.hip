@@ -39,6 +39,12 @@ namespace tl {
 namespace {
 
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;
+// the profile builds that take stats words 5..15 for themselves (TL_PROFILE2 writes its counters there, TL_PROFILE3 leaves them)
+#if defined(TL_PROFILE2) || defined(TL_PROFILE3)
+constexpr bool kProbeOwnsStats = true;
+#else
+constexpr bool kProbeOwnsStats = false;
+#endif
 #ifndef TL_RMAX
 #define TL_RMAX 63
 #endif
@@ -69,6 +75,15 @@ struct Ctl {                     // kCtlBytes of LDS
 };
 constexpr size_t kCtlBytes = 384;
 static_assert(sizeof(Ctl) <= kCtlBytes, "Ctl block");
+
+// The one description of a descent's LDS: its parts in carve order, in bytes.  The kernel carves by these names and the host's
+// size functions sum them.  Per city: the points (float2, or the grid form's packed word + y's high byte), then perm; fixed: tile
+// boxes, tile msq, Ctl, the hit lists (kQCap words per wave and step parity; later the cost sum's scratch); where the late phase
+// runs, behind them: pos (per city), the long list, one scratch row per wave.
+constexpr size_t kXyBytes = 8, kFxLoBytes = 4, kFxHiBytes = 1, kPermBytes = 2, kNlPosBytes = 2;
+constexpr size_t kTboxBytes = kMaxGroups * 64 * 16, kTmsqBytes = kMaxGroups * 64 * 4, kQueuesBytes = 32 * kQCap * 4;
+constexpr size_t kNlLongBytes = (size_t)kNlLongCap * 16, kNlSurvBytes = 16 * 64 * 2;
+static_assert(kQueuesBytes >= TL_TWO_OPT_NT * 4, "the hit lists double as the cost-sum scratch");
 
 // Deferred reversals (dense mode).  The hits (i, g_0 < g_1 < ... < g_{k-1}) of ONE row all reverse a prefix that starts at
 // lo = i+1 (two_opt.rs:50 swap_2opt(path, i+1, j)), and the rest of that row's scan reads only positions > g and
@@ -222,6 +237,21 @@ struct Acct {
     uint32_t log_cap, log_n;             // where a new sweep begins), its capacity and the number of words so far (counted on beyond it)
 };
 
+// rows of the next speculative block: one in dense shape, up to kRMax in pruned shape
+__device__ __forceinline__ uint32_t block_rows(const Cursor &c, uint32_t nrows)
+{
+    return c.pruned ? ((uint32_t)kRMax < nrows - c.i0 ? (uint32_t)kRMax : nrows - c.i0) : 1u;
+}
+
+// One word for the move log: row << 16 | column per applied move, in order; 0xFFFFFFFF where a new sweep begins.
+__device__ __forceinline__ void log_word(Acct &a, int lane, uint32_t w)
+{
+    if (a.log) {
+        if (lane == 0 && a.log_n < a.log_cap) a.log[a.log_n] = w;
+        a.log_n += 1u;
+    }
+}
+
 // The deferred reversals of row c.i0, composed (flush_deferred), by every wave.  `sync_first`: the hits were filed in this very
 // boundary (by their owner, behind B2), so a barrier comes before they are read.
 template <bool CONTROL, int NT, int SLOTS, typename PT>
@@ -322,10 +352,7 @@ __device__ __forceinline__ bool step_boundary(Cursor &c, Acct &a, const PT &P, u
         reverse_segment<NT>(P, perm, is + 1u, js, tid);  // two_opt.rs:50,69-79  swap_2opt(path, i+1, j)
         TL_SYNC();
         if (CONTROL) {
-            if (a.log) {
-                if (lane == 0 && a.log_n < a.log_cap) a.log[a.log_n] = key;  // row << 16 | column
-                a.log_n += 1u;
-            }
+            log_word(a, lane, key);
             a.since += (float)(is - c.i0) * rowlen;
             a.moves += 1u;
             a.reversed += (uint64_t)(js - is);
@@ -496,10 +523,7 @@ __device__ __forceinline__ void late_phase(const TwoOptBatchArgs &A, const PT &P
             i0 = 0u;
             j0 = 2u;
             nl_ok = false;  // the long list is rebuilt once per sweep (entries that are no longer long go)
-            if (control && acct.log) {
-                if (lane == 0 && acct.log_n < acct.log_cap) acct.log[acct.log_n] = 0xFFFFFFFFu;
-                acct.log_n += 1u;
-            }
+            if (control) log_word(acct, lane, 0xFFFFFFFFu);
         }
         // A step scans the REST of the sweep under "no move yet": rows are dealt in chunks of 64 (the lane-resident row table), wave w
         // takes rows 4w .. 4w+3 of every chunk and goes from chunk to chunk without a barrier — the tour does not change while a
@@ -713,10 +737,7 @@ __device__ __forceinline__ void late_phase(const TwoOptBatchArgs &A, const PT &P
             reverse_segment<NT>(P, perm, is + 1u, js, tid, L.pos);  // two_opt.rs:50,69-79  swap_2opt(path, i+1, j)
             TL_SYNC();
             if (control) {
-                if (acct.log) {
-                    if (lane == 0 && acct.log_n < acct.log_cap) acct.log[acct.log_n] = key;  // row << 16 | column
-                    acct.log_n += 1u;
-                }
+                log_word(acct, lane, key);
                 acct.moves += 1u;
                 acct.reversed += (uint64_t)(js - is);
             }
@@ -769,27 +790,27 @@ __global__ __launch_bounds__(NT, 4) void k_two_opt_ref_lds(TwoOptBatchArgs A)
     unsigned char *tailp;
     if constexpr (FX) {
         P.lo = reinterpret_cast<uint32_t *>(smem);
-        P.hi = reinterpret_cast<uint8_t *>(smem + (size_t)npad * 4);
+        P.hi = reinterpret_cast<uint8_t *>(smem + (size_t)npad * kFxLoBytes);
         P.inv = A.fx_inv;
-        perm = reinterpret_cast<uint16_t *>(smem + (size_t)npad * 5);
-        tailp = smem + (size_t)npad * 7;
+        perm = reinterpret_cast<uint16_t *>(smem + (size_t)npad * (kFxLoBytes + kFxHiBytes));
+        tailp = smem + (size_t)npad * (kFxLoBytes + kFxHiBytes + kPermBytes);
     } else {
         P = reinterpret_cast<float2 *>(smem);
-        perm = reinterpret_cast<uint16_t *>(smem + (size_t)npad * 8);
-        tailp = smem + (size_t)npad * 10;
+        perm = reinterpret_cast<uint16_t *>(smem + (size_t)npad * kXyBytes);
+        tailp = smem + (size_t)npad * (kXyBytes + kPermBytes);
     }
     float4 *tbox = reinterpret_cast<float4 *>(tailp);                        // kMaxGroups*64 entries
-    float *tmsq = reinterpret_cast<float *>(tailp + kMaxGroups * 64 * 16);     // kMaxGroups*64
-    Ctl *ctl = reinterpret_cast<Ctl *>(tailp + kMaxGroups * 64 * 20);
+    float *tmsq = reinterpret_cast<float *>(tailp + kTboxBytes);     // kMaxGroups*64
+    Ctl *ctl = reinterpret_cast<Ctl *>(tailp + kTboxBytes + kTmsqBytes);
     // hit lists (kQCap words per (wave, step parity)) during the descent; reused as NT floats for the cost sum
     uint32_t *queues = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(ctl) + kCtlBytes);
     float *scratch = reinterpret_cast<float *>(queues);
     NlLds L{nullptr, nullptr, nullptr};  // late phase: city -> position, long list, per-wave scratch (behind the hit lists)
     if constexpr (NL) {
-        unsigned char *nlp = reinterpret_cast<unsigned char *>(queues) + 32 * kQCap * 4;
+        unsigned char *nlp = reinterpret_cast<unsigned char *>(queues) + kQueuesBytes;
         L.pos = reinterpret_cast<uint16_t *>(nlp);
-        L.longe = reinterpret_cast<uint4 *>(nlp + (size_t)npad * 2);
-        L.surv = reinterpret_cast<uint16_t *>(nlp + (size_t)npad * 2 + (size_t)kNlLongCap * 16);
+        L.longe = reinterpret_cast<uint4 *>(nlp + (size_t)npad * kNlPosBytes);
+        L.surv = reinterpret_cast<uint16_t *>(nlp + (size_t)npad * kNlPosBytes + kNlLongBytes);
     }
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -903,7 +924,6 @@ __global__ __launch_bounds__(NT, 4) void k_two_opt_ref_lds(TwoOptBatchArgs A)
     uint64_t late_clk = 0;  // shader clocks of the late phase (stats word 13, high part)
     constexpr int NWK = NW - 1;                                  // workers
     constexpr uint32_t kLead = kDenseLead < (uint32_t)NWK ? kDenseLead : (uint32_t)NWK;
-    static_assert(4u <= kQCap, "a hit list fits its slot");
     if (n >= 4 && wave == 0) {
         // ------------------------------------------------------------ control wave
         Cursor c{0u, 2u, 0u, 0u, 0u, 0xFFFFFFFFu, 0u, false};
@@ -957,10 +977,7 @@ __global__ __launch_bounds__(NT, 4) void k_two_opt_ref_lds(TwoOptBatchArgs A)
                             c.dirty_hi = ntile - 1u;
                             new_sweep = true;
                         }
-                        if (acct.log) {  // a new sweep begins here (the same row can hold moves of two consecutive sweeps back to back)
-                            if (lane == 0 && acct.log_n < acct.log_cap) acct.log[acct.log_n] = 0xFFFFFFFFu;
-                            acct.log_n += 1u;
-                        }
+                        log_word(acct, lane, 0xFFFFFFFFu);  // a new sweep begins here (the same row can hold moves of two consecutive sweeps back to back)
                     }
                 }
                 // block shape: dense (moves every few rows: one row, every tile) or pruned (up to kRMax rows, L0)
@@ -982,7 +999,7 @@ __global__ __launch_bounds__(NT, 4) void k_two_opt_ref_lds(TwoOptBatchArgs A)
             if (lane == 0) ctl->kr[slot_next].x = kNoKey;  // slot of the next step (its last readers are two barriers behind)
             ++step;
             n_pruned_steps += c.pruned ? 1u : 0u;
-            const uint32_t R = c.pruned ? ((uint32_t)kRMax < nrows - c.i0 ? (uint32_t)kRMax : nrows - c.i0) : 1u;
+            const uint32_t R = block_rows(c, nrows);
             if (c.pruned) {
                 if (c.dirty_lo <= c.dirty_hi) {  // stale tile boxes: every wave takes its share (this one has nothing else to do here)
 #ifdef TL_PROFILE4
@@ -1087,14 +1104,12 @@ __global__ __launch_bounds__(NT, 4) void k_two_opt_ref_lds(TwoOptBatchArgs A)
             printf("sweep %u: dense hit %lu steps %lu cyc | dense none %lu steps %lu cyc, tiles %lu of which with valid boxes %lu | pruned hit %lu steps %lu cyc | pruned none %lu steps %lu cyc\n",
                    sweeps, q4[0], q4[1], q4[2], q4[3], q4[8], q4[9], q4[4], q4[5], q4[6], q4[7]);
 #endif
-#if !defined(TL_PROFILE2) && !defined(TL_PROFILE3)
-        if (tid == 0) {
+        if constexpr (!kProbeOwnsStats) if (tid == 0) {
             uint64_t *st = A.out_stats + (size_t)d * TL_STATS_STRIDE;
             st[13] = (uint64_t)n_desc | (late_clk << 24);  // descriptors published (sweep ends + block-shape changes) | shader clocks of the late phase << 24
             st[14] = (uint64_t)(n_pruned_steps + n_late_steps) | ((uint64_t)n_late_steps << 32);  // steps in pruned shape | of those, late-phase steps << 32
             st[15] = acct.log_n;      // words offered to the move log: moves + sweep marks (more than its capacity: the log is a prefix)
         }
-#endif
 #ifdef TL_PROFILE2
         if (tid == 0) {
             uint64_t *st = A.out_stats + (size_t)d * TL_STATS_STRIDE;
@@ -1145,7 +1160,7 @@ __global__ __launch_bounds__(NT, 4) void k_two_opt_ref_lds(TwoOptBatchArgs A)
             }
             uint32_t *keyslot = &ctl->kr[c.slot].x;
             uint32_t my_hits = 0;
-            const uint32_t R = c.pruned ? ((uint32_t)kRMax < nrows - c.i0 ? (uint32_t)kRMax : nrows - c.i0) : 1u;
+            const uint32_t R = block_rows(c, nrows);
             if (!c.pruned) {
                 // ---- dense step: one row, every tile from the resume column on.  Lead round: kLead waves (one per SIMD) look at
                 // the first tiles, everybody else parks at B1 — moves come every few candidates here, and a wave chaining hits
@@ -1352,7 +1367,7 @@ __global__ __launch_bounds__(NT, 4) void k_two_opt_ref_lds(TwoOptBatchArgs A)
         st[2] = reversed;
         st[3] = status;
         st[4] = step;
-#if !defined(TL_PROFILE2) && !defined(TL_PROFILE3)
+        if constexpr (!kProbeOwnsStats) {
         // [5..8] cascade work (counting instantiation only, else 0): L0 tile bounds, candidates into L1, into L2, into L3;
         // [9] shader clocks of the descent
         // (s_memtime), [10] the same interval in constant 100 MHz ticks (s_memrealtime) -> the clock the CU really held
@@ -1364,38 +1379,32 @@ __global__ __launch_bounds__(NT, 4) void k_two_opt_ref_lds(TwoOptBatchArgs A)
         st[12] = ctl->cnt[5];
         st[9] = __builtin_amdgcn_s_memtime() - ctl->clk0;
         st[10] = __builtin_amdgcn_s_memrealtime() - ctl->rt0;
-#endif
+        }
     }
 }
 
 // ------------------------------------------------------------------------------------------------
 // launch
 // ------------------------------------------------------------------------------------------------
-size_t two_opt_ref_lds_bytes(uint32_t n, uint32_t *n_pad_out, int nt)
+// bytes of a descent at `per_city` bytes of points + perm per padded position (~0 beyond the tile-table capacity)
+static size_t lds_bytes(uint32_t n, size_t per_city, uint32_t *n_pad_out)
 {
     const uint32_t n_pad = ((n + 64u + 63u) / 64u) * 64u;  // P[j+1] of any lane of the last tile is in range
     if (n_pad_out) *n_pad_out = n_pad;
-    if (n_pad > (uint32_t)kMaxGroups * 64u * 64u) return ~(size_t)0;  // beyond the tile-table capacity
-    const size_t meta = (size_t)kMaxGroups * 64 * 20 + kCtlBytes;
-    const size_t lists = (size_t)32 * kQCap * 4;  // chained-hit lists, also the nt floats of cost-sum scratch
-    static_assert(32 * kQCap * 4 >= TL_TWO_OPT_NT * 4, "the hit lists double as the cost-sum scratch");
-    (void)nt;
-    return (size_t)n_pad * 10 + meta + lists;
+    if (n_pad > (uint32_t)kMaxGroups * 64u * 64u) return ~(size_t)0;
+    return (size_t)n_pad * per_city + kTboxBytes + kTmsqBytes + kCtlBytes + kQueuesBytes;
 }
 
-size_t two_opt_ref_fx_lds_bytes(uint32_t n)
-{
-    const uint32_t n_pad = ((n + 64u + 63u) / 64u) * 64u;
-    if (n_pad > (uint32_t)kMaxGroups * 64u * 64u) return ~(size_t)0;
-    return (size_t)n_pad * 7 + (size_t)kMaxGroups * 64 * 20 + kCtlBytes + (size_t)32 * kQCap * 4;
-}
+size_t two_opt_ref_lds_bytes(uint32_t n, uint32_t *n_pad_out) { return lds_bytes(n, kXyBytes + kPermBytes, n_pad_out); }
+
+size_t two_opt_ref_fx_lds_bytes(uint32_t n) { return lds_bytes(n, kFxLoBytes + kFxHiBytes + kPermBytes, nullptr); }
 
 // The grid form costs a decode per point read, so it is used only where it buys a second descent per CU: a batch with more
 // descents than CUs whose tours fit the LDS twice at 7 B per city but not at 10 (7 100 < n <= 10 240 on MI355X).
 // ... or a third and fourth: more than two descents per CU where four tours fit at 7 B per city but not at 10 (3 050 < n <= 4 300).
 bool two_opt_ref_fx_pays(uint32_t n, uint32_t count, int cus, int lds_budget)
 {
-    const size_t plain = two_opt_ref_lds_bytes(n, nullptr, TL_TWO_OPT_NT), fx = two_opt_ref_fx_lds_bytes(n);
+    const size_t plain = two_opt_ref_lds_bytes(n, nullptr), fx = two_opt_ref_fx_lds_bytes(n);
     if (cus <= 0 || count <= (uint32_t)cus) return false;
     const bool two = 2 * plain > (size_t)lds_budget && 2 * fx <= (size_t)lds_budget && (size_t)n <= (size_t)kFlushSlotsFx * 512;
     const bool four = count > 2u * (uint32_t)cus && 4 * plain > (size_t)lds_budget && 4 * fx <= (size_t)lds_budget &&
@@ -1461,7 +1470,7 @@ hipError_t launch_two_opt_ref_lds(const TwoOptBatchArgs &A, uint32_t count, bool
                                   int force_nt)
 {
     uint32_t n_pad = 0;
-    const size_t lds = two_opt_ref_lds_bytes(A.n, &n_pad, TL_TWO_OPT_NT);
+    const size_t lds = two_opt_ref_lds_bytes(A.n, &n_pad);
     TwoOptBatchArgs B = A;
     B.n_pad = n_pad;
     if (A.fx_xy && A.fx_inv != 0.0) {  // grid-coordinate form: two descents per CU on 8 waves, or four on 4 (the caller has checked that it fits)
@@ -1485,7 +1494,7 @@ hipError_t launch_two_opt_ref_lds(const TwoOptBatchArgs &A, uint32_t count, bool
 // four tours, 512 / 256 (2 / 4 descents per CU); a flush holds kFlushSlots elements per thread, so a narrow form also needs n <= 15 NT
 int two_opt_ref_pick_nt(uint32_t n, uint32_t count, int cus, int lds_budget, int force_nt)
 {
-    const size_t lds = two_opt_ref_lds_bytes(n, nullptr, TL_TWO_OPT_NT);
+    const size_t lds = two_opt_ref_lds_bytes(n, nullptr);
     const size_t fit = lds ? (size_t)lds_budget / lds : 1;
     int nt = TL_TWO_OPT_NT;
     if (force_nt) {
@@ -1515,9 +1524,9 @@ bool two_opt_ref_nl_form(uint32_t n, uint32_t count, int cus, int lds_budget, in
 size_t two_opt_ref_nl_lds_bytes(uint32_t n)
 {
     uint32_t n_pad = 0;
-    const size_t base = two_opt_ref_lds_bytes(n, &n_pad, TL_TWO_OPT_NT);
+    const size_t base = two_opt_ref_lds_bytes(n, &n_pad);
     if (base == ~(size_t)0) return base;
-    return base + (size_t)n_pad * 2 + (size_t)kNlLongCap * 16 + (size_t)16 * 64 * 2;
+    return base + (size_t)n_pad * kNlPosBytes + kNlLongBytes + kNlSurvBytes;
 }
 
 bool two_opt_ref_nl_applies(uint32_t n, uint32_t count, int cus, int lds_budget, int force_nt)
