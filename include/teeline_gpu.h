@@ -108,6 +108,8 @@ typedef enum tl_mode {
 #define TL_FLAG_LK_CLASSIC_VIEW (1u << 23)  /* tl_lk, chip-wide scans at n >= 1500: the chain search reads cand -> xy -> next -> xy (default: the
                                               packed view — candidates with their distances, successor records with the successor's point and the
                                               tour edge's length: two dependent look-ups and one square root per branch instead of four and three) */
+#define TL_FLAG_BHK_EXACT_WALK (1u << 25)   /* tl_bellman_karp: read the route back by exact f32 equality instead of the reference's 1e-4 tolerance walk, which
+                                              can leave a result that is no tour — always a permutation while a finite tour exists; the same table and optimum */
 #define TL_FLAG_LK_NO_SPECULATION (1u << 22) /* tl_lk, LDS form: the epochs one after the other in one workgroup (default: one workgroup per epoch,
                                               as many consecutive epochs at once as the chip holds, taken in order up to the first accepted one) */
 /* TUNING BUILDS ONLY (libteeline_gpu_tune.so, -DTL_TUNE: `python -m teeline_amd.build --tune`).  Forms that were measured and
@@ -369,6 +371,31 @@ int tl_savings(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n,
  * tree + odd vertices + matching, reversed = the tree's launch alone in nanoseconds, total_ms includes the host walk. */
 int tl_christofides(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, uint32_t *out_pos, float *out_cost,
                     tl_stats *stats);
+
+/* ---- Bellman-Held-Karp exact solver: replaces bellman_karp::solve (bellman_karp.rs:24-165) ---------- */
+/* The dynamic program over subsets on positions, k = n - 1, last = k: opt[c][S] = the f32 minimum over i in S \ c of
+ * opt[i][S \ c] + d(i, c), started at f32::MAX and replaced under a strict `<` (a NaN term, or one that rounds to f32::MAX or inf,
+ * is never taken), opt[i][{i}] = d(i, last); one kernel launch per subset size, the table (2^k rows of 128 bytes) stays in the
+ * context's workspace.  *out_optimal (optional) = the f32::min fold from f32::MAX over i of opt[i][all] + d(i, last), terms with
+ * both operands < f32::MAX only (f32::MAX itself: no finite tour, or n = 1).  Every table value is the reference's up to the sign of
+ * a zero, which neither the route nor the cost can show.
+ * out_pos: n positions exactly as the reference's walk (read_optimal_route, :122-156) leaves them, out_pos[0] = n - 1: per step the
+ * FIRST j not yet read with |left - (opt[j][unread] + d(j, prev))| <= max(|left|, |that|, 1) * 1e-4, then left -= d(j, prev); the
+ * walk ends once left <= 0.0, and a step that finds no j leaves 0 in its place.  SO THE RESULT NEED NOT BE A TOUR, as in the
+ * reference (seeded random instances of 4..12 cities: 1 in 200): the status is TL_OK all the same, *out_is_tour (optional) is 0
+ * and a pipeline's validate_tour rejects it.  With TL_FLAG_BHK_EXACT_WALK on the context the route is read back by exact equality
+ * instead — the first j not yet read with opt[j][unread] + d(j, prev) == rem, then rem = opt[j][unread], from rem = optimal —
+ * which cannot fail: always a permutation while optimal < f32::MAX (otherwise the tolerance walk's result, unchanged).
+ * *out_cost = tour_length of out_pos as given, a permutation or not: d(out_pos[n-1], out_pos[0]) first, then the n - 1 edges in
+ * order (sequential f32), d(p, p) = 0.  It is NOT *out_optimal: the two sums differ in their last bits.
+ * dm_packed NULL: EUC_2D from xy; otherwise every distance is read from the packed matrix and xy may be NULL.  n = 1: [0], cost 0,
+ * optimal f32::MAX; n = 0: TL_OK, nothing written, cost 0 (the reference underflows).  n > TL_BHK_MAX_N: TL_ERR_UNSUPPORTED
+ * before anything is allocated (n = 26 holds 4 GiB of workspace).  stats (optional): sweeps = layers launched (n - 2),
+ * candidates = k(k-1) 2^(k-2) terms, moves = n, kernel_ms = init + layers + optimum + walk, reversed = the layers alone in
+ * nanoseconds. */
+#define TL_BHK_MAX_N 26u
+int tl_bellman_karp(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, uint32_t *out_pos, float *out_cost,
+                    float *out_optimal, uint32_t *out_is_tour, tl_stats *stats);
 
 /* ---- multi-start 2-opt (north-star config 4; no counterpart in the reference) ---------------- */
 /* Runs restarts [first, first+count) — restart r starts from the Fisher–Yates permutation drawn

@@ -4,7 +4,7 @@
 //!   `two_opt::solve`        (src/tsp/two_opt.rs:7-67)
 //!   `three_opt::solve`      (src/tsp/three_opt.rs:16-51)
 //!   `lin_kernighan::solve`  (src/tsp/lin_kernighan.rs:35-100)
-//!   `or_opt::solve`, `nearest_neighbor::solve`, `greedy_edge::solve`, `savings::solve`, `christofides::solve`, `DistanceMatrix::build`
+//!   `or_opt::solve`, `nearest_neighbor::solve`, `greedy_edge::solve`, `savings::solve`, `christofides::solve`, `bellman_karp::solve`, `DistanceMatrix::build`
 //! of the `teeline` crate.  This crate knows nothing about `teeline`'s types (no dependency cycle): tours are
 //! POSITIONS (indices into the city array), coordinates are `[x0, y0, x1, y1, ...]`, the optional matrix is the
 //! reference's packed strict lower triangle (`DistanceMatrix::distances()`, distance_matrix.rs:171-173).
@@ -91,6 +91,8 @@ unsafe extern "C" {
                       stats: *mut Stats) -> c_int;
     fn tl_christofides(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
                        stats: *mut Stats) -> c_int;
+    fn tl_bellman_karp(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
+                       out_optimal: *mut f32, out_is_tour: *mut u32, stats: *mut Stats) -> c_int;
     fn tl_savings_hub(xy: *const f32, n: u32, out_hub: *mut u32) -> c_int;
     fn tl_savings(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, hub: u32, out_pos: *mut u32, out_cost: *mut f32,
                   out_hub: *mut u32, stats: *mut Stats) -> c_int;
@@ -436,6 +438,23 @@ impl Context {
         self.check(rc).map(|_| t)
     }
 
+    /// `bellman_karp::solve` (bellman_karp.rs:24-87), the exact solver, n <= `BHK_MAX_N`: returns the route as the reference's
+    /// tolerance walk leaves it, the DP's optimum and whether the route is a permutation — it need not be (`Tour::cost` is
+    /// tour_length of the route as given either way).  A context created with `FLAG_BHK_EXACT_WALK` reads the route back by exact
+    /// equality instead: always a tour while a finite one exists.
+    pub fn bellman_karp(&self, xy: &[f32], dm_packed: Option<&[f32]>) -> Result<(Tour, f32, bool), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, None);
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        let (mut optimal, mut is_tour) = (0.0f32, 0u32);
+        // SAFETY: as in two_opt; out_optimal and out_is_tour point at live values.
+        let rc = unsafe {
+            tl_bellman_karp(self.raw, xy.as_ptr(), opt_ptr(dm_packed), n, t.pos.as_mut_ptr(), &mut t.cost, &mut optimal, &mut is_tour,
+                            &mut t.stats)
+        };
+        self.check(rc).map(|_| (t, optimal, is_tour != 0))
+    }
+
     /// `savings::solve` (savings.rs:34-82): every edge in descending order of its saving against the hub (ties: (i, j) ascending;
     /// a NaN saving ranks below every number), n <= 65 535.  `hub`: a position, or `None` for the one nearest the centroid of `xy`
     /// (`savings_hub`).  Returns the tour and the hub used.
@@ -455,6 +474,10 @@ impl Context {
 
 /// `TL_SAVINGS_HUB_AUTO` (include/teeline_gpu.h)
 pub const SAVINGS_HUB_AUTO: u32 = 0xFFFF_FFFF;
+/// `tl_create` flag: `bellman_karp` reads its route back by exact f32 equality instead of the reference's tolerance walk.
+pub const FLAG_BHK_EXACT_WALK: u32 = 1 << 25;
+/// Largest n `bellman_karp` takes (a table of 2^(n-1) rows of 128 bytes).
+pub const BHK_MAX_N: u32 = 26;
 
 /// `hub_position` (savings.rs:94-117): the position nearest the centroid of `xy` (x0, y0, x1, y1, ...), in f32 throughout.  Host
 /// code: needs no context and no GPU.

@@ -32,6 +32,8 @@ TL_FLAG_LK_ILS_LDS = 1 << 21    # tl_lk: the single-workgroup LDS form (k_lk_ils
 TL_FLAG_MULTISTART_RCCL = 1 << 24  # multi-start over several devices of one process: RCCL min-all-reduce + broadcast inside the library
 TL_FLAG_LK_CLASSIC_VIEW = 1 << 23  # tl_lk chip-wide: cand -> xy -> next -> xy look-ups instead of the packed records
 TL_FLAG_LK_NO_SPECULATION = 1 << 22  # tl_lk, LDS form: epochs one after the other (default: a batch of consecutive epochs at once)
+TL_FLAG_BHK_EXACT_WALK = 1 << 25  # tl_bellman_karp: the route by exact f32 equality instead of the reference's tolerance walk (always a tour)
+TL_BHK_MAX_N = 26  # tl_bellman_karp: largest n (a table of 2^(n-1) rows of 128 bytes: 4 GiB)
 TL_FLAG_LK_SMALL = 1 << 9  # tl_lk: the LDS-resident single-workgroup form wherever it fits
 TL_FLAG_COUNT_WORK = 1 << 8  # the LDS 2-opt kernel also counts the work of its cascade (stats words 5..8); ~8 % slower
 TL_DM_PACKED_LOWER, TL_DM_FULL = 0, 1
@@ -47,7 +49,7 @@ SYMBOLS = [
     "tl_or_opt", "tl_or_opt_find_best_move", "tl_selftest_sqrt", "tl_two_opt_population", "tl_dm_is_euc2d",
     "tl_two_opt_multistart_devices", "tl_two_opt_trace", "tl_three_opt_trace", "tl_lk_trace", "tl_or_opt_trace",
     "tl_lk_live", "tl_two_opt_neighbour_lists", "tl_two_opt_plan", "tl_multistart_shard", "tl_two_opt_last_counters",
-    "tl_greedy_edge", "tl_savings_hub", "tl_savings", "tl_christofides",
+    "tl_greedy_edge", "tl_savings_hub", "tl_savings", "tl_christofides", "tl_bellman_karp",
 ]
 
 
@@ -130,6 +132,7 @@ def load():
     L.tl_nearest_neighbor.argtypes = [vp, vp, vp, u32, u32, vp, f32p]
     L.tl_greedy_edge.argtypes = [vp, vp, vp, u32, vp, f32p, C.POINTER(TlStats)]
     L.tl_christofides.argtypes = [vp, vp, vp, u32, vp, f32p, C.POINTER(TlStats)]
+    L.tl_bellman_karp.argtypes = [vp, vp, vp, u32, vp, f32p, f32p, C.POINTER(u32), C.POINTER(TlStats)]
     L.tl_savings_hub.argtypes = [vp, u32, C.POINTER(u32)]
     L.tl_savings.argtypes = [vp, vp, vp, u32, u32, vp, f32p, C.POINTER(u32), C.POINTER(TlStats)]
     L.tl_selftest_sqrt.argtypes = [vp, u32, u64, C.POINTER(u64), C.POINTER(u32)]

@@ -1,7 +1,7 @@
 // tl_api_common.h — what the host-side translation units of the C ABI share (internal to libteeline_gpu): the context, its
 // single-thread guard, error reporting and the grow-only device buffers.  tl_api.hip (context, matrix, tour length),
-// tl_api_two_opt.hip, tl_api_scans.hip (3-opt, Or-opt), tl_api_lk.hip (candidate lists, NN seed, Lin-Kernighan) and tl_api_greedy.hip
-// (greedy-edge, savings, Christofides) include it.
+// tl_api_two_opt.hip, tl_api_scans.hip (3-opt, Or-opt), tl_api_lk.hip (candidate lists, NN seed, Lin-Kernighan), tl_api_greedy.hip
+// (greedy-edge, savings, Christofides) and tl_api_bhk.hip (Bellman-Held-Karp) include it.
 #pragma once
 #include "../../include/teeline_gpu.h"
 #include "tl_kernels.h"

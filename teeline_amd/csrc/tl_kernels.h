@@ -385,4 +385,20 @@ hipError_t launch_chr_prim(const ChrWs &cw, const float2 *xy, const float *dm, u
 // city, w.state is reset with state[4] = their number
 hipError_t launch_chr_odd(const GreedyWs &w, const ChrWs &cw, uint32_t n, hipStream_t s);
 
+// bellman_karp.hip — the Bellman-Held-Karp exact solver, 1 <= n <= TL_BHK_MAX_N
+struct BhkWs {
+    float *dsq;       // [32][32] d(a, b) of the instance, +0.0 on the diagonal and outside it
+    uint32_t *binom;  // [32][32] C(a, b), uploaded by the host
+    float *out_f;     // [0] tour_length of the route, [1] the optimum
+    uint32_t *out_u;  // [0] 1 if the route is a permutation
+    float *opt;       // [2^(n-1)][32] the table, mask-major
+};
+size_t bhk_ws_bytes(uint32_t n);
+BhkWs bhk_ws_layout(void *ws, uint32_t n);
+void bhk_binomials(uint32_t *out);  // host: the [32][32] table w.binom holds
+hipError_t launch_bhk_init(const BhkWs &w, const float2 *xy, const float *dm, uint32_t n, hipStream_t s);
+// layer p (2 <= p <= n - 1): every opt[S][c] with |S| = p from the layer below; count = C(n - 1, p)
+hipError_t launch_bhk_layer(const BhkWs &w, uint32_t n, uint32_t p, uint32_t count, int cus, hipStream_t s);
+hipError_t launch_bhk_walk(const BhkWs &w, uint32_t n, bool exact, uint32_t *out_pos, hipStream_t s);
+
 }  // namespace tl

@@ -208,4 +208,4 @@ def validate_tour(tour_ids, problem):
     return ids == sorted(int(v) for v in problem.ids)
 
 
-from . import christofides, greedy_edge, lin_kernighan, multistart, nearest_neighbor, opt_tour, or_opt, pipeline, savings, synth, three_opt, tsplib, two_opt  # noqa: E402,F401
+from . import bellman_karp, christofides, greedy_edge, lin_kernighan, multistart, nearest_neighbor, opt_tour, or_opt, pipeline, savings, synth, three_opt, tsplib, two_opt  # noqa: E402,F401

@@ -12,9 +12,9 @@ SOLVER_NAMES = {"nn": "nearest_neighbor", "nearest_neighbor": "nearest_neighbor"
                 "3opt": "three_opt", "three_opt": "three_opt", "oropt": "or_opt", "or_opt": "or_opt", "or-opt": "or_opt",
                 "lk": "lin_kernighan", "lin_kernighan": "lin_kernighan", "shuffle": "random_shuffle",
                 "random_shuffle": "random_shuffle", "greedy_edge": "greedy_edge", "gec": "greedy_edge", "savings": "savings", "sav": "savings",
-                "christofides": "christofides", "chr": "christofides"}
+                "christofides": "christofides", "chr": "christofides", "bhk": "bellman_karp", "bellman_karp": "bellman_karp"}
 PRESETS = {"fast": ["nn", "2opt"]}  # resolve_preset (main.rs:354-369); classic / thorough end in SA (not accelerated)
-AUTO_EXPAND_WITH_NN = {"two_opt", "three_opt", "or_opt", "lin_kernighan"}  # mod.rs:129-139 (greedy_edge, savings and christofides are seeds: `solve gec` / `solve sav` / `solve chr` run alone)
+AUTO_EXPAND_WITH_NN = {"two_opt", "three_opt", "or_opt", "lin_kernighan"}  # mod.rs:129-139 (greedy_edge, savings and christofides are seeds: `solve gec` / `solve sav` / `solve chr` run alone; so does the exact solver `solve bhk`, mod.rs:2137)
 
 
 def steps_for_solve(solver, no_seed=False):
@@ -72,12 +72,15 @@ class StageOutcome:
         self.name, self.solution, self.duration_ms = name, solution, duration_ms
 
 
-def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1):
-    """steps: iterable of solver names ("nn", "gec", "sav", "chr", "2opt", "3opt", "or_opt", "lk", "shuffle"); opts: {name: options} (optional)."""
-    from . import (HeuristicOptions, LKOptions, christofides, greedy_edge, lin_kernighan, nearest_neighbor, or_opt, savings, three_opt, two_opt,
+def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact_walk=False):
+    """steps: iterable of solver names ("nn", "gec", "sav", "chr", "bhk", "2opt", "3opt", "or_opt", "lk", "shuffle"); opts: {name: options} (optional).
+    exact_walk: a `bhk` stage reads its route back by exact equality (bellman_karp.solve) instead of the reference's tolerance walk,
+    whose result can fail validate_tour below."""
+    from . import (HeuristicOptions, LKOptions, bellman_karp, christofides, greedy_edge, lin_kernighan, nearest_neighbor, or_opt, savings, three_opt, two_opt,
                    validate_tour)
     mods = {"nearest_neighbor": nearest_neighbor, "two_opt": two_opt, "three_opt": three_opt, "or_opt": or_opt,
-            "lin_kernighan": lin_kernighan, "greedy_edge": greedy_edge, "savings": savings, "christofides": christofides}
+            "lin_kernighan": lin_kernighan, "greedy_edge": greedy_edge, "savings": savings, "christofides": christofides,
+            "bellman_karp": bellman_karp}
     opts = opts or {}
     outcomes, seed = [], None
     for step in steps:
@@ -93,6 +96,8 @@ def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1):
             sol = random_shuffle(problem, lk_seed, ctx=ctx)
         elif name == "lin_kernighan":
             sol = lin_kernighan.solve(problem, opts.get(step) or LKOptions(), None, init, ctx=ctx, seed=lk_seed)
+        elif name == "bellman_karp":
+            sol = mods[name].solve(problem, opts.get(step) or HeuristicOptions(), None, init, ctx=ctx, exact_walk=exact_walk)
         else:
             sol = mods[name].solve(problem, opts.get(step) or HeuristicOptions(), None, init, ctx=ctx)
         ms = (time.perf_counter() - t0) * 1e3

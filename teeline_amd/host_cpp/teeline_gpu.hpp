@@ -7,7 +7,7 @@
 //   src/tsp/mod.rs:1731-1814         TspProblem, Solution
 //   src/tsp/mod.rs:596-613,1249-1267 HeuristicOptions, LKOptions
 //   src/tsp/tsplib.rs:101-255        tsplib::read_from_file
-//   src/tsp/{two_opt,three_opt,or_opt,lin_kernighan,nearest_neighbor,greedy_edge,savings,christofides}.rs  solve(problem, opts, progress, init_tour)
+//   src/tsp/{two_opt,three_opt,or_opt,lin_kernighan,nearest_neighbor,greedy_edge,savings,christofides,bellman_karp}.rs  solve(problem, opts, progress, init_tour)
 //   src/tsp/pipeline.rs:53-80        run_pipeline_stages (warm start + validate_tour)
 // Same names, argument meaning and error behaviour: dispatcher-level failures throw std::runtime_error (the
 // reference returns Err(String), mod.rs:1661), inputs on which the reference panics throw teeline::ReferencePanic.
@@ -529,6 +529,34 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOp
 }
 }  // namespace christofides
 
+namespace bellman_karp {  // bellman_karp.rs:24-87, the exact solver (n <= TL_BHK_MAX_N)
+// The route is what the reference's tolerance walk leaves (:122-156), which need not be a tour: *is_tour (optional) tells, and
+// run_pipeline_stages' validate_tour rejects it as the reference's does.  A Context created with TL_FLAG_BHK_EXACT_WALK reads the
+// route back by exact equality instead: always a tour while a finite one exists.  optimal (optional): the DP's optimum, which
+// differs from Solution::total (tour_length of the route) in its last bits.
+inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions & /*opts: only `verbose` is read, to print the table*/,
+                      const ProgressFn *progress_tx, const std::vector<size_t> * /*_init_tour*/, float *optimal = nullptr, bool *is_tour = nullptr)
+{
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size();
+    std::vector<uint32_t> out(n);
+    float cost = 0.f, opt = 0.f;
+    uint32_t ok = 0;
+    tl_stats st{};
+    ctx.check(tl_bellman_karp(ctx.get(), xy.data(), problem.explicit_packed(), n, out.data(), &cost, &opt, &ok, &st));
+    if (optimal) *optimal = opt;
+    if (is_tour) *is_tour = ok != 0;
+    Solution s = detail::finish(problem, out, cost, st, nullptr);
+    if (progress_tx && *progress_tx) {
+        // :48-52, :81-84: CityChange per city of the subsets in position order, the route with 0.0, Done
+        for (uint32_t k = 0; k + 1 < n; ++k) (*progress_tx)(ProgressKind::CityChange, std::vector<size_t>{problem.cities[k].id}, 0.0f);
+        (*progress_tx)(ProgressKind::PathUpdate, s.route_, 0.0f);
+        (*progress_tx)(ProgressKind::Done, s.route_, cost);
+    }
+    return s;
+}
+}  // namespace bellman_karp
+
 namespace lin_kernighan {  // lin_kernighan.rs:35-100
 inline Solution solve(Context &ctx, const TspProblem &problem, const LKOptions &opts, const ProgressFn *progress_tx,
                       const std::vector<size_t> *init_tour, uint64_t seed = 1)
@@ -809,7 +837,7 @@ inline Solution solve(Context &ctx, const TspProblem &problem, uint64_t seed)
 }  // namespace random_shuffle
 
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
-enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides };
+enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp };
 
 inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
 {
@@ -823,14 +851,15 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
     else if (s == "gec" || s == "greedy_edge") out = Solvers::GreedyEdge;
     else if (s == "sav" || s == "savings") out = Solvers::Savings;
     else if (s == "chr" || s == "christofides") out = Solvers::Christofides;
+    else if (s == "bhk" || s == "bellman_karp") out = Solvers::BellmanKarp;
     else {
-        static const char *cpu_only[] = {"aco", "ant_colony", "bhk", "bellman_karp", "branch_bound",
+        static const char *cpu_only[] = {"aco", "ant_colony", "branch_bound",
                                          "cs", "cuckoo_search", "fpa", "flower_pollination", "fourier", "ga", "genetic_algorithm", "gsa",
                                          "gravitational_search", "pso", "particle_swarm", "sa", "simulated_annealing",
                                          "som", "kohonen", "kohonen_som", "stochastic_hill", "tabu", "tabu_search"};
         for (const char *c : cpu_only)
             if (s == c) {
-                why = "solver `" + s + "` is not accelerated by this build (nn, gec, sav, chr, 2opt, 3opt, or_opt, lk, shuffle are)";
+                why = "solver `" + s + "` is not accelerated by this build (nn, gec, sav, chr, bhk, 2opt, 3opt, or_opt, lk, shuffle are)";
                 return false;
             }
         why = "unknown solver";  // FromStr's Err (mod.rs:588)
@@ -850,6 +879,7 @@ inline const char *solver_name(Solvers s)
         case Solvers::GreedyEdge: return "greedy_edge";
         case Solvers::Savings: return "savings";
         case Solvers::Christofides: return "christofides";
+        case Solvers::BellmanKarp: return "bellman_karp";
         default: return "shuffle";
     }
 }
@@ -873,15 +903,22 @@ struct StageOutcome {  // :11-14
 inline std::vector<std::string> stage_warnings(const std::vector<Solvers> &solvers)
 {
     std::vector<std::string> w;
-    for (size_t i = 1; i < solvers.size(); ++i)
-        if (solvers[i] == Solvers::NearestNeighbor)
-            w.push_back("nn at stage " + std::to_string(i) + " discards the warm-start seed from the previous stage");
-        else if (solvers[i] == Solvers::GreedyEdge)
-            w.push_back("greedy_edge at stage " + std::to_string(i) +
-                        " discards the warm-start seed from the previous stage (it always rebuilds from scratch)");
-        else if (solvers[i] == Solvers::Savings)
-            w.push_back("savings at stage " + std::to_string(i) +
-                        " discards the warm-start seed from the previous stage (it always rebuilds from scratch)");
+    for (size_t i = 0; i < solvers.size(); ++i) {
+        if (i > 0) {
+            if (solvers[i] == Solvers::NearestNeighbor)
+                w.push_back("nn at stage " + std::to_string(i) + " discards the warm-start seed from the previous stage");
+            else if (solvers[i] == Solvers::GreedyEdge)
+                w.push_back("greedy_edge at stage " + std::to_string(i) +
+                            " discards the warm-start seed from the previous stage (it always rebuilds from scratch)");
+            else if (solvers[i] == Solvers::Savings)
+                w.push_back("savings at stage " + std::to_string(i) +
+                            " discards the warm-start seed from the previous stage (it always rebuilds from scratch)");
+        }
+        if (i + 1 != solvers.size() && solvers[i] == Solvers::BellmanKarp)  // :112-118: an exact stage that is not the last
+            w.push_back("BellmanKarp at stage " + std::to_string(i) +
+                        " ignores the warm-start seed entirely (the exact DP has no use for a partial/seed tour) and its optimal result will be "
+                        "superseded by later stages");
+    }
     return w;
 }
 
@@ -912,6 +949,7 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             case Solvers::GreedyEdge: sol = greedy_edge::solve(ctx, problem, o.heuristic, o.progress, init); break;
             case Solvers::Savings: sol = savings::solve(ctx, problem, o.heuristic, o.progress, init); break;
             case Solvers::Christofides: sol = christofides::solve(ctx, problem, o.heuristic, o.progress, init); break;
+            case Solvers::BellmanKarp: sol = bellman_karp::solve(ctx, problem, o.heuristic, o.progress, init); break;
         }
         const auto t1 = std::chrono::steady_clock::now();
         const uint64_t ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();

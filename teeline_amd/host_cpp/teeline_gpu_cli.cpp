@@ -5,13 +5,16 @@
 //                                     [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P] [--n_nearest K] [--max-depth D]
 //   teeline-gpu pipeline --steps=nn,2opt,... [-i FILE] [same options]
 //   teeline-gpu solvers [--short]
-//     solver  : nn, gec, sav, chr, 2opt, 3opt, or_opt, lk, shuffle (and their long names, mod.rs:559-590); preset: fast = nn,2opt (main.rs:354-369)
+//     solver  : nn, gec, sav, chr, bhk, 2opt, 3opt, or_opt, lk, shuffle (and their long names, mod.rs:559-590); preset: fast = nn,2opt (main.rs:354-369)
 //     solve   : 2opt / 3opt / or_opt / lk auto-expand to pipeline(nn, solver) unless --no-seed (main.rs:387-397, mod.rs:129-139);
-//               gec (greedy_edge), sav (savings) and chr (christofides) are constructions and run alone
+//               gec (greedy_edge), sav (savings) and chr (christofides) are constructions and run alone; so does bhk (bellman_karp),
+//               the exact solver (n <= 26, mod.rs:2137) — as a later pipeline stage it ignores its seed
 //     stdout  : print_solution "{:.5} {0|1}\n<id id ... >\n" (main.rs:645-652) or the JSON object of main.rs:700-712;
 //               with --optimal-tour the comparison goes to stderr in text mode and into the JSON object in JSON mode
 //   own flags (no counterpart in the reference): --seed S (LK kicks and the shuffle stage; the reference draws both from an
 //   unseeded thread RNG), --best-sweep (TL_MODE_BEST_SWEEP), --device N, --stats,
+//   --exact-walk (TL_FLAG_BHK_EXACT_WALK: bhk reads its route back by exact equality instead of the reference's tolerance walk, whose
+//   result is now and then no tour — the stage then fails with "invalid tour", as in the reference),
 //   --timing (one JSON line on stderr: milliseconds of main() by phase — read input, create context, every stage's wall and kernel
 //   time, output — what bench.py's drop_in_end_to_end reads), --repeat K (run the stage list K times in this process, the last
 //   run is printed: with --timing the first run is the cold one — code-object load, workspace allocation — the others steady),
@@ -31,7 +34,7 @@ namespace {
 
 struct Args {
     std::string cmd, solver, file, steps, optimal_tour, distance_type, output_format = "text";
-    bool no_seed = false, best = false, stats = false, short_list = false, progress_digest = false, timing = false, full_exit = false;
+    bool no_seed = false, best = false, exact_walk = false, stats = false, short_list = false, progress_digest = false, timing = false, full_exit = false;
     int device = 0, repeat = 1;
     pipeline::StageOptions opt;
 };
@@ -40,10 +43,10 @@ struct Args {
 {
     if (why) std::fprintf(stderr, "error: %s\n", why);
     std::fprintf(stderr,
-                 "usage: teeline-gpu solve <nn|gec|sav|chr|2opt|3opt|or_opt|lk|shuffle|fast> [-i FILE] [--no-seed] [--output-format text|json]\n"
+                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|shuffle|fast> [-i FILE] [--no-seed] [--output-format text|json]\n"
                  "                         [--optimal-tour FILE] [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P]\n"
                  "                         [--n_nearest K] [--max-depth D] [--seed S] [--best-sweep] [--device N] [--stats]\n"
-                 "                         [--progress-digest]\n"
+                 "                         [--progress-digest] [--exact-walk]\n"
                  "       teeline-gpu pipeline --steps=nn,2opt,... | --steps=greedy_edge,2opt,... | --steps=savings,2opt,... | --steps=christofides,lk,... [-i FILE] [options as above]\n"
                  "       teeline-gpu solvers [--short]\n");
     std::exit(2);  // clap's usage-error exit code
@@ -103,6 +106,7 @@ Args parse(int argc, char **argv)
         else if (s == "-v" || s == "--verbose") a.opt.heuristic.verbose = true;
         else if (s == "--seed") a.opt.seed = std::stoull(val());
         else if (s == "--best-sweep") a.best = true;
+        else if (s == "--exact-walk") a.exact_walk = true;
         else if (s == "--device") a.device = std::stoi(val());
         else if (s == "--stats") a.stats = true;
         else if (s == "--short") a.short_list = true;
@@ -260,7 +264,7 @@ int run(int argc, char **argv)
         }
         const double ms_read = ms_since(t_main);
         const auto t_ctx = clk::now();
-        Context ctx(a.device);
+        Context ctx(a.device, a.exact_walk ? TL_FLAG_BHK_EXACT_WALK : TL_FLAG_NONE);
         const double ms_create = ms_since(t_ctx);
         const auto t_prob = clk::now();
         TspProblem problem = data.problem(ctx);
