@@ -43,7 +43,8 @@ extern "C" {
 #endif
 
 #define TL_ABI_VERSION 5 /* bumped when an existing entry point, struct or code changes meaning; additions (round 5: tl_multistart_shard,
-                            tl_two_opt_last_counters, new tl_create flags, k <= 64) leave it — a caller built against 5 runs unchanged */
+                            tl_two_opt_last_counters, new tl_create flags, k <= 64; later: tl_or_opt_population, tl_or_opt_lds_max_n,
+                            TL_FLAG_OR_OPT_FORCE_SCAN) leave it — a caller built against 5 runs unchanged */
 
 typedef struct tl_ctx tl_ctx;
 
@@ -110,6 +111,8 @@ typedef enum tl_mode {
                                               tour edge's length: two dependent look-ups and one square root per branch instead of four and three) */
 #define TL_FLAG_BHK_EXACT_WALK (1u << 25)   /* tl_bellman_karp: read the route back by exact f32 equality instead of the reference's 1e-4 tolerance walk, which
                                               can leave a result that is no tour — always a permutation while a finite tour exists; the same table and optimum */
+#define TL_FLAG_OR_OPT_FORCE_SCAN (1u << 26) /* tl_or_opt_population: the tours one after the other through the chip-wide descent of tl_or_opt at every n
+                                              (default: only beyond the LDS-resident size) */
 #define TL_FLAG_LK_NO_SPECULATION (1u << 22) /* tl_lk, LDS form: the epochs one after the other in one workgroup (default: one workgroup per epoch,
                                               as many consecutive epochs at once as the chip holds, taken in order up to the first accepted one) */
 /* TUNING BUILDS ONLY (libteeline_gpu_tune.so, -DTL_TUNE: `python -m teeline_amd.build --tune`).  Forms that were measured and
@@ -434,6 +437,23 @@ uint64_t tl_pack_cost_key(float cost, uint32_t restart);
 int tl_two_opt_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed,
                           const uint32_t *init_pos, uint32_t count, uint32_t *out_pos, float *out_costs,
                           tl_stats *stats);
+
+/* Or-opt over a population of `count` explicit tours (init_pos: count x n positions), each by its own or_opt::solve descent
+ * (or_opt.rs:18-74), one workgroup per tour with the tour in that CU's LDS (csrc/or_opt_lds.hip), all concurrently.  Tour r of
+ * out_pos / out_costs / out_moves (optional, count entries: the moves that descent applied) is exactly what tl_or_opt returns for
+ * init_pos + r * n alone: the route element for element, the cost bit for bit.  The reference has no batch form.
+ * n < 4: every output tour is the identity and init_pos is ignored (or_opt.rs:31-34).  count == 0: TL_OK, nothing written.  A row
+ * of init_pos that is not a permutation of 0..n-1: TL_ERR_BADARG, the message names the tour; nothing is launched or written.  A
+ * descent still finding moves after 64 n + 1024 passes: TL_ERR_NO_CONVERGE, the message names the tour.
+ * tl_or_opt_lds_max_n: the largest n of the LDS-resident coordinate form (16 bytes per city: position, point, tour edge; 10 224
+ * on 160 KB); the matrix form (dm_packed; distances read from the packed matrix in HBM) keeps 8 bytes per city and takes twice
+ * that n.  Beyond it, or with TL_FLAG_OR_OPT_FORCE_SCAN, the tours run one after the other through tl_or_opt's chip-wide descent:
+ * the same results; stats->kernel_ms is then the sum of the descents' device times.
+ * stats (optional): moves and sweeps (passes, each descent's last one finds nothing) summed over the tours, candidates = the
+ * placements those passes examined, counted as tl_or_opt counts them. */
+uint32_t tl_or_opt_lds_max_n(const tl_ctx *ctx);
+int tl_or_opt_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t count,
+                         uint32_t *out_pos, float *out_costs, uint32_t *out_moves, tl_stats *stats);
 
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts

@@ -33,6 +33,7 @@ TL_FLAG_MULTISTART_RCCL = 1 << 24  # multi-start over several devices of one pro
 TL_FLAG_LK_CLASSIC_VIEW = 1 << 23  # tl_lk chip-wide: cand -> xy -> next -> xy look-ups instead of the packed records
 TL_FLAG_LK_NO_SPECULATION = 1 << 22  # tl_lk, LDS form: epochs one after the other (default: a batch of consecutive epochs at once)
 TL_FLAG_BHK_EXACT_WALK = 1 << 25  # tl_bellman_karp: the route by exact f32 equality instead of the reference's tolerance walk (always a tour)
+TL_FLAG_OR_OPT_FORCE_SCAN = 1 << 26  # tl_or_opt_population: tour after tour through tl_or_opt's chip-wide descent at every n
 TL_BHK_MAX_N = 26  # tl_bellman_karp: largest n (a table of 2^(n-1) rows of 128 bytes: 4 GiB)
 TL_FLAG_LK_SMALL = 1 << 9  # tl_lk: the LDS-resident single-workgroup form wherever it fits
 TL_FLAG_COUNT_WORK = 1 << 8  # the LDS 2-opt kernel also counts the work of its cascade (stats words 5..8); ~8 % slower
@@ -50,6 +51,7 @@ SYMBOLS = [
     "tl_two_opt_multistart_devices", "tl_two_opt_trace", "tl_three_opt_trace", "tl_lk_trace", "tl_or_opt_trace",
     "tl_lk_live", "tl_two_opt_neighbour_lists", "tl_two_opt_plan", "tl_multistart_shard", "tl_two_opt_last_counters",
     "tl_greedy_edge", "tl_savings_hub", "tl_savings", "tl_christofides", "tl_bellman_karp",
+    "tl_or_opt_population", "tl_or_opt_lds_max_n",
 ]
 
 
@@ -142,5 +144,8 @@ def load():
     L.tl_or_opt.argtypes = [vp, vp, u32, vp, vp, vp, f32p, C.POINTER(TlStats)]
     L.tl_or_opt_find_best_move.argtypes = [vp, vp, u32, vp, vp, C.POINTER(i32), f32p, C.POINTER(u32), C.POINTER(u32),
                                            C.POINTER(u32), C.POINTER(i32)]
+    L.tl_or_opt_lds_max_n.argtypes = [vp]
+    L.tl_or_opt_lds_max_n.restype = u32
+    L.tl_or_opt_population.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, C.POINTER(TlStats)]
     _lib = L
     return L

@@ -11,7 +11,7 @@
 // f32 expression associated exactly as the reference writes it; argmin by a packed 96-bit key
 // (~delta_bits << 64 | loop-order index; the index 6 n^2 needs more than 32 bits from n = 26 755 on — round 4) reduced per wave,
 // per workgroup, then by k_or_pick, which also applies the relocation in place.  Exact distances (correctly rounded sqrt); roofline: VALU.
-#include "tl_kernels.h"
+#include "or_opt_scan.h"
 
 #pragma clang fp contract(off)
 
@@ -20,23 +20,8 @@ namespace tl {
 namespace {
 
 constexpr int kOrWaves = 4;
-constexpr int kOrIR = 8;          // consecutive segment starts served from one set of distance registers
 constexpr uint32_t kOrTargetWaves = 4096;  // waves a scan should at least consist of: small tours take fewer 63-wide chunks of
                                            // insertion points per wave (or_opt_chunks)
-typedef unsigned __int128 key_t;  // (~delta bits) << 64 | loop-order index
-constexpr unsigned long long kNoKey64 = ~0ULL;
-__device__ __forceinline__ key_t make_key(unsigned long long hi, unsigned long long lo) { return ((key_t)hi << 64) | (key_t)lo; }
-__device__ __forceinline__ key_t no_key() { return make_key(kNoKey64, kNoKey64); }
-
-__device__ __forceinline__ key_t wave_min_key(key_t v)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long oh = __shfl_down((unsigned long long)(v >> 64), off), ol = __shfl_down((unsigned long long)v, off);
-        const key_t o = make_key(oh, ol);
-        v = o < v ? o : v;
-    }
-    return make_key(__shfl((unsigned long long)(v >> 64), 0), __shfl((unsigned long long)v, 0));
-}
 
 static uint32_t or_opt_grid_x(uint32_t n) { return ((n + kOrIR - 1) / kOrIR + kOrWaves - 1) / kOrWaves; }
 static uint32_t or_opt_chunks(uint32_t n)  // 63-wide chunks of insertion points per wave
@@ -63,13 +48,7 @@ struct Dist {
 
 }  // namespace
 
-// One wave = kOrIR consecutive segment starts i0..i0+kOrIR-1 x a slab of insertion points (kOrChunks chunks of 63).
-// Every placement of the five kinds (len 1 fwd; len 2, 3 fwd and reversed) of a pair (i, j) is a sum of the row constant,
-// the tour edge (x_j, y_j) and two distances out of { d(x_j, P[i+m]), d(y_j, P[i+m]) : m = 0, 1, 2 } — and y_j = x_{j+1}.
-// So a chunk computes d(x_j, P[i0+m]) once for m = 0..kOrIR+1 (lane = j, lane 63 only supplies x of the next j),
-// gets the y-distances from the neighbouring lane, and serves all kOrIR starts from those registers: 1.25 correctly
-// rounded distances per (i, j) instead of the 10 a row-per-wave scan evaluates.  The f32 expressions keep the
-// reference's association (or_opt.rs:136-139, :148-151); distances are symmetric bit for bit.
+// One wave = kOrIR consecutive segment starts i0..i0+kOrIR-1 x a slab of insertion points (`chunks` chunks of 63): or_scan_rows, or_opt_scan.h
 template <bool DM>
 __global__ __launch_bounds__(kOrWaves * 64) void k_or_scan(OrOptArgs A, uint32_t chunks)
 {
@@ -84,74 +63,7 @@ __global__ __launch_bounds__(kOrWaves * 64) void k_or_scan(OrOptArgs A, uint32_t
     float bestd = __builtin_inff();
     if (i0 < n) {
         const Dist<DM> D{A.Pt, A.dm, A.perm};
-        // row constants: lane (len-1)*kOrIR + r holds -remove_gain of (seg_len, i0 + r) (:114-116), rowmask its validity (:90-92, :98-100)
-        float nrg = 0.0f;
-        bool rv = false;
-        if (lane < 3 * kOrIR) {
-            const uint32_t len = (uint32_t)lane / kOrIR + 1u, i = i0 + (uint32_t)lane % kOrIR;
-            rv = i < n && n > len + 1u && i + len <= n;
-            if (rv) {
-                const uint32_t prev = i == 0u ? n - 1u : i - 1u, after = (i + len) % n, pl = i + len - 1u;
-                const float remove_gain = D(prev, i) + D(pl, after) - D(prev, after);
-                nrg = -remove_gain;
-            }
-        }
-        const uint64_t rowmask = __builtin_amdgcn_ballot_w64(rv);
-        for (uint32_t c = 0; c < chunks; ++c) {
-            const uint32_t jb = jlo + c * 63u;
-            if (jb >= n) break;
-            const uint32_t j = jb + (uint32_t)lane;
-            const bool real = lane < 63 && j < n;
-            const uint32_t jj = j < n ? j : 0u;  // position of x_j; j == n is the wrap (y of j = n-1 is P[0]), lanes beyond are unused
-            const float e = real ? A.E[j] : 0.0f;
-            float dX[kOrIR + 2], dY[kOrIR + 2];
-#pragma unroll
-            for (int m = 0; m < kOrIR + 2; ++m) {
-                const uint32_t pm = i0 + (uint32_t)m < n ? i0 + (uint32_t)m : n - 1u;  // beyond the tour: unused by any valid row
-                dX[m] = D(jj, pm);
-                // d(y_j, P[i0+m]) = d(x_{j+1}, P[i0+m]): the lane above, one DPP wave shift (lane 63, the helper lane, gets 0)
-                dY[m] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, dX[m]), 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
-            }
-#pragma unroll
-            for (int r = 0; r < kOrIR; ++r) {
-                const uint32_t i = i0 + (uint32_t)r;
-                if (i >= n) break;
-                const uint32_t prev = i == 0u ? n - 1u : i - 1u;
-                // the five placements of (i, j); an invalid one (row or column excluded, :90-92, :98-100, :123-125) reads +inf.
-                // Only when the smallest of them can still beat this lane's best are the 64-bit keys looked at.
-                float val[5];
-                const bool okj = real & (j != prev);
-                const float inf = __builtin_inff();
-#pragma unroll
-                for (int len = 1; len <= 3; ++len) {
-                    const int rl = (len - 1) * kOrIR + r;
-                    const bool ok = okj & !((j - i) < (uint32_t)len) & (bool)((rowmask >> rl) & 1ull);
-                    const float nr = readlane_f(nrg, rl);
-                    const float fwd = nr + dX[r] + dY[r + len - 1] - e;  // :136-139  -rg + d(x,first) + d(last,y) - d(x,y)
-                    val[len == 1 ? 0 : 2 * len - 3] = ok ? fwd : inf;
-                    if (len > 1) {
-                        const float rev = nr + dX[r + len - 1] + dY[r] - e;  // :148-151  -rg + d(x,last) + d(first,y) - d(x,y)
-                        val[2 * len - 2] = ok ? rev : inf;
-                    }
-                }
-                const float vmin = fminf(fminf(fminf(val[0], val[1]), fminf(val[2], val[3])), val[4]);  // NaN deltas drop out like in `<`
-                if (__builtin_amdgcn_ballot_w64((vmin < -1e-3f) & (vmin <= bestd))) {
-#pragma unroll
-                    for (int q = 0; q < 5; ++q) {  // loop order within (i, j): len 1 fwd; len 2 fwd, rev; len 3 fwd, rev — the order index decides ties
-                        const int len = q == 0 ? 1 : (q + 3) / 2;
-                        const unsigned long long order = ((unsigned long long)((uint32_t)(len - 1) * n + i) * n + j) * 2ull + (unsigned long long)(q != 0 && (q & 1) == 0);
-                        const float v = val[q];
-                        if ((v < -1e-3f) & (v <= bestd)) {
-                            const key_t key = make_key((unsigned long long)(~__builtin_bit_cast(uint32_t, v)), order);
-                            if (key < best) {
-                                best = key;
-                                bestd = v;
-                            }
-                        }
-                    }
-                }
-            }
-        }
+        or_scan_rows(D, A.E, n, i0, jlo, chunks, lane, best, bestd);
     }
     best = wave_min_key(best);
     if (lane == 0) {

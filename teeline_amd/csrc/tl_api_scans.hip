@@ -1,4 +1,5 @@
-// tl_api_scans.hip — C ABI, the best-improvement scans: tl_three_opt* (src/tsp/three_opt.rs:16-218) and tl_or_opt* (src/tsp/or_opt.rs:18-184).
+// tl_api_scans.hip — C ABI, the best-improvement scans: tl_three_opt* (src/tsp/three_opt.rs:16-218) and tl_or_opt* (src/tsp/or_opt.rs:18-184),
+// tl_or_opt_population included.
 #include "tl_api_common.h"
 
 using namespace tl;
@@ -236,18 +237,23 @@ extern "C" int tl_or_opt_find_best_move(tl_ctx *c, const float *xy, uint32_t n, 
     return TL_OK;
 }
 
-// the log's 4 words per move: i, j, seg_len, reversed of or_opt.rs:45-51
-static int or_opt_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos,
-                      uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *move_log, uint32_t log_cap, uint32_t *log_len)
+// deltas evaluated per pass: seg_len 1: n(n-2) forward; seg_len 2: (n-1)(n-3) x 2; seg_len 3: (n-2)(n-4) x 2
+static uint64_t or_opt_per_pass(uint32_t n)
 {
-    // deltas evaluated per pass: seg_len 1: n(n-2) forward; seg_len 2: (n-1)(n-3) x 2; seg_len 3: (n-2)(n-4) x 2
     const uint64_t nn = n;
     uint64_t per = 0;
     if (nn > 2) per += nn * (nn - 2);
     if (nn > 3) per += 2 * (nn - 1) * (nn - 3);
     if (nn > 4) per += 2 * (nn - 2) * (nn - 4);
+    return per;
+}
+
+// the log's 4 words per move: i, j, seg_len, reversed of or_opt.rs:45-51
+static int or_opt_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos,
+                      uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *move_log, uint32_t log_cap, uint32_t *log_len)
+{
     return scan_descent<OrOptArgs>(
-        c, "or_opt", xy, n, dm_packed, init_pos, out_pos, out_cost, stats, move_log, log_cap, log_len, per,
+        c, "or_opt", xy, n, dm_packed, init_pos, out_pos, out_cost, stats, move_log, log_cap, log_len, or_opt_per_pass(n),
         [&](OrOptArgs &A) { return or_opt_setup(c, xy, n, dm_packed, init_pos, A); },
         [&](const OrOptArgs &A) { return launch_or_opt_pass(A, A.dm != nullptr, 1, c->stream, c->lds_bytes); });
 }
@@ -269,3 +275,97 @@ extern "C" int tl_or_opt_trace(tl_ctx *c, const float *xy, uint32_t n, const flo
     return or_opt_run(c, xy, n, dm_packed, init_pos, out_pos, out_cost, stats, move_log, log_cap, log_len);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Or-opt over a population of tours (or_opt_lds.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" uint32_t tl_or_opt_lds_max_n(const tl_ctx *c) { return c ? or_opt_lds_max_n(c->lds_bytes, false) : 0u; }
+
+// Every tour refined by its own descent, one workgroup per tour with the tour in LDS; tour r's result is tl_or_opt's for it alone.
+// Beyond the LDS-resident size, or with TL_FLAG_OR_OPT_FORCE_SCAN, the tours go one after the other through the chip-wide descent.
+extern "C" int tl_or_opt_population(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t count,
+                                    uint32_t *out_pos, float *out_costs, uint32_t *out_moves, tl_stats *stats)
+{
+    TL_ENTER(c);
+    if (!c || (!xy && !dm_packed)) return fail(c, TL_ERR_BADARG, "tl_or_opt_population: NULL argument");
+    if (count == 0) return TL_OK;
+    if (!out_pos || (n >= 4 && !init_pos)) return fail(c, TL_ERR_BADARG, "tl_or_opt_population: NULL argument");
+    if (n >= 4)
+        for (uint32_t r = 0; r < count; ++r)
+            if (!is_permutation(init_pos + (size_t)r * n, n))
+                return fail(c, TL_ERR_BADARG, "tl_or_opt_population: tour %u is not a permutation of 0..n-1", r);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    int rc;
+    if (n < 4) {  // or_opt.rs:31-34: the cities' order, init_tour ignored
+        float cst = 0.0f;
+        for (uint32_t k = 0; k < n; ++k) out_pos[k] = k;
+        if (out_costs && n >= 2 && (rc = tl_tour_length(c, xy, dm_packed, n, out_pos, &cst))) return rc;
+        for (uint32_t r = 0; r < count; ++r) {
+            for (uint32_t k = 0; k < n; ++k) out_pos[(size_t)r * n + k] = k;
+            if (out_costs) out_costs[r] = cst;
+            if (out_moves) out_moves[r] = 0u;
+        }
+        return TL_OK;
+    }
+    if ((c->flags & TL_FLAG_OR_OPT_FORCE_SCAN) || n > or_opt_lds_max_n(c->lds_bytes, dm_packed != nullptr)) {
+        tl_stats acc{};
+        for (uint32_t r = 0; r < count; ++r) {
+            float cst = 0.0f;
+            tl_stats st1{};
+            if ((rc = or_opt_run(c, xy, n, dm_packed, init_pos + (size_t)r * n, out_pos + (size_t)r * n, &cst, &st1, nullptr, 0, nullptr))) return rc;
+            if (out_costs) out_costs[r] = cst;
+            if (out_moves) out_moves[r] = (uint32_t)st1.moves;
+            acc.sweeps += st1.sweeps;
+            acc.moves += st1.moves;
+            acc.candidates += st1.candidates;
+            acc.kernel_ms += st1.kernel_ms;
+        }
+        if (stats) {
+            *stats = acc;
+            stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return TL_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t words = (size_t)count * n;
+    if ((rc = ensure(c, c->init, words * 4)) || (rc = ensure(c, c->out_pos, words * 4)) || (rc = ensure(c, c->out_cost, (size_t)count * 4)) ||
+        (rc = ensure(c, c->misc, (size_t)count * 16)))
+        return rc;
+    OrOptLdsArgs A{};
+    if ((rc = upload_input(c, xy, dm_packed, n, &A.xy, &A.dm))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->init.p, init_pos, words * 4, hipMemcpyHostToDevice, c->stream));
+    A.init = (const uint32_t *)c->init.p;
+    A.out_pos = (uint32_t *)c->out_pos.p;
+    A.out_cost = (float *)c->out_cost.p;
+    A.out_run = (uint32_t *)c->misc.p;
+    A.n = n;
+    A.max_passes = 64u * n + 1024u;  // scan_descent's cap
+    c->ev_valid = false;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    HIPCHK(c, launch_or_opt_lds(A, count, or_opt_lds_threads(n, count, c->cus, c->lds_bytes, A.dm != nullptr), c->stream));
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    c->ev_valid = true;
+    std::vector<uint32_t> run((size_t)count * 4);
+    std::vector<float> costs(count);
+    HIPCHK(c, hipMemcpyAsync(run.data(), A.out_run, (size_t)count * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(costs.data(), A.out_cost, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t r = 0; r < count; ++r)
+        if (run[4u * r + 2u] != 0u) return fail(c, TL_ERR_NO_CONVERGE, "or_opt: pass cap reached in tour %u", r);
+    HIPCHK(c, hipMemcpyAsync(out_pos, A.out_pos, words * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    uint64_t moves = 0, passes = 0;
+    for (uint32_t r = 0; r < count; ++r) {
+        if (out_costs) out_costs[r] = costs[r];
+        if (out_moves) out_moves[r] = run[4u * r];
+        moves += run[4u * r];
+        passes += run[4u * r + 1u];
+    }
+    if (stats) {
+        stats->moves = moves;
+        stats->sweeps = passes;
+        stats->candidates = passes * or_opt_per_pass(n);
+        stamp_times(c, stats, t0);
+    }
+    return TL_OK;
+}

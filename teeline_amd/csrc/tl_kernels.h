@@ -224,6 +224,22 @@ struct OrOptArgs {
 hipError_t launch_or_opt_pass(const OrOptArgs &A, bool dm, int apply, hipStream_t s, int lds_budget);
 uint32_t or_opt_scan_blocks(uint32_t n);
 
+// or_opt_lds.hip — a population of tours, one workgroup per tour, the whole descent in LDS
+struct OrOptLdsArgs {
+    const float2 *xy;      // n cities, city order (coordinate form)
+    const float *dm;       // packed matrix or nullptr
+    const uint32_t *init;  // [count][n] start tours (permutations: the host checks)
+    uint32_t *out_pos;     // [count][n]
+    float *out_cost;       // [count] tour_length of the result
+    uint32_t *out_run;     // [count][4] moves, passes, status (1: pass cap reached), 0
+    uint32_t n;
+    uint32_t max_passes;   // a descent stops (status 1) when it has run this many passes and still finds a move
+};
+size_t or_opt_lds_bytes(uint32_t n, bool dm);             // LDS of one tour's workgroup
+uint32_t or_opt_lds_max_n(int lds_budget, bool dm);       // largest n whose state fits
+int or_opt_lds_threads(uint32_t n, uint32_t count, int cus, int lds_budget, bool dm);
+hipError_t launch_or_opt_lds(const OrOptLdsArgs &A, uint32_t count, int threads, hipStream_t s);
+
 // lk.hip
 struct LkState {             // device-side state machine of the multi-CU LK variant
     uint32_t key;            // min pair index with a valid chain in the current scan (0xFFFFFFFF: none)

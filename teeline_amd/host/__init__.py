@@ -70,6 +70,9 @@ class Context:
     def two_opt_lds_max_n(self):
         return int(self._lib.tl_two_opt_lds_max_n(self._h))
 
+    def or_opt_lds_max_n(self):
+        return int(self._lib.tl_or_opt_lds_max_n(self._h))
+
     def last_kernel_ms(self):
         ms = C.c_double()
         self.check(self._lib.tl_last_kernel_ms(self._h, C.byref(ms)))

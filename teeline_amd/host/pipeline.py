@@ -72,17 +72,17 @@ class StageOutcome:
         self.name, self.solution, self.duration_ms = name, solution, duration_ms
 
 
-def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact_walk=False):
+def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact_walk=False, init_tour=None):
     """steps: iterable of solver names ("nn", "gec", "sav", "chr", "bhk", "2opt", "3opt", "or_opt", "lk", "shuffle"); opts: {name: options} (optional).
     exact_walk: a `bhk` stage reads its route back by exact equality (bellman_karp.solve) instead of the reference's tolerance walk,
-    whose result can fail validate_tour below."""
+    whose result can fail validate_tour below.  init_tour: the seed of the first stage (city ids; default: that stage's own seeding)."""
     from . import (HeuristicOptions, LKOptions, bellman_karp, christofides, greedy_edge, lin_kernighan, nearest_neighbor, or_opt, savings, three_opt, two_opt,
                    validate_tour)
     mods = {"nearest_neighbor": nearest_neighbor, "two_opt": two_opt, "three_opt": three_opt, "or_opt": or_opt,
             "lin_kernighan": lin_kernighan, "greedy_edge": greedy_edge, "savings": savings, "christofides": christofides,
             "bellman_karp": bellman_karp}
     opts = opts or {}
-    outcomes, seed = [], None
+    outcomes, seed = [], (None if init_tour is None else list(init_tour))
     for step in steps:
         if step not in SOLVER_NAMES:
             raise ValueError(f"unknown solver `{step}` (this build accelerates {sorted(set(SOLVER_NAMES))})")
@@ -105,4 +105,32 @@ def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact
             raise RuntimeError(f"pipeline: stage `{step}` produced an invalid tour")
         outcomes.append(StageOutcome(step, sol, ms))
         seed = sol.route()
+    return outcomes
+
+
+POPULATION_SOLVERS = ("two_opt", "or_opt")  # the solvers with a population entry (tl_two_opt_population, tl_or_opt_population)
+
+
+def run_population(problem, steps, init_tours, *, ctx=None):
+    """run_pipeline_stages for a population of tours: every stage runs through its population entry (one descent per tour, all
+    concurrently) and feeds the next.  steps: drawn from "2opt" / "or_opt" and their long names; any other step is a ValueError
+    that names it, raised before anything runs.  Returns one list of StageOutcome per tour — entry k equals
+    run_pipeline_stages(problem, steps) started from init_tours[k]; a stage's duration_ms is the whole population's."""
+    from . import or_opt, two_opt, validate_tour
+    steps = list(steps)
+    for step in steps:
+        if SOLVER_NAMES.get(step) not in POPULATION_SOLVERS:
+            raise ValueError(f"step `{step}` has no population form (population pipelines take {sorted(k for k, v in SOLVER_NAMES.items() if v in POPULATION_SOLVERS)})")
+    mods = {"two_opt": two_opt, "or_opt": or_opt}
+    tours = [list(t) for t in init_tours]
+    outcomes = [[] for _ in tours]
+    for step in steps:
+        t0 = time.perf_counter()
+        sols = mods[SOLVER_NAMES[step]].solve_population(problem, tours, ctx=ctx)
+        ms = (time.perf_counter() - t0) * 1e3
+        for k, sol in enumerate(sols):
+            if not validate_tour(sol.route(), problem):
+                raise RuntimeError(f"pipeline: stage `{step}` produced an invalid tour for individual {k}")
+            outcomes[k].append(StageOutcome(step, sol, ms))
+        tours = [sol.route() for sol in sols]
     return outcomes
