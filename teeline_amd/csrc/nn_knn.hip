@@ -425,6 +425,7 @@ hipError_t launch_nn_seed(const float2 *xy, uint32_t n, const uint32_t *cand, ui
 // order — what both the k-buffer rule (mod.rs:1848-1855, scan in position order, insert after equals) and the fallback
 // (:50-63; ties -> lowest position, the oracle's rule where the reference iterates a HashSet) pick.  One workgroup, the
 // visited flags in LDS, one row of the matrix per step: argmin of the packed key (sortable distance bits << 32 | position).
+// The reference compares floats, where -0.0 == +0.0 and the lower position wins: the key is formed from value + 0.0f.
 __global__ __launch_bounds__(kLkNT) void k_nn_seed_dm(const float *__restrict__ dm, uint32_t n, uint32_t *__restrict__ path)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char nn_smem[];
@@ -440,7 +441,7 @@ __global__ __launch_bounds__(kLkNT) void k_nn_seed_dm(const float *__restrict__ 
         unsigned long long best = ~0ull;
         for (uint32_t p = tid; p < n; p += kLkNT) {
             if (visited[p]) continue;
-            const uint32_t b = __builtin_bit_cast(uint32_t, dm_lookup(dm, cur, p));
+            const uint32_t b = __builtin_bit_cast(uint32_t, dm_lookup(dm, cur, p) + 0.0f);  // -0.0 -> +0.0
             const uint32_t key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);  // f32 order as u32 order
             const unsigned long long kk = ((unsigned long long)key << 32) | p;
             best = kk < best ? kk : best;
