@@ -44,7 +44,7 @@ extern "C" {
 
 #define TL_ABI_VERSION 5 /* bumped when an existing entry point, struct or code changes meaning; additions (round 5: tl_multistart_shard,
                             tl_two_opt_last_counters, new tl_create flags, k <= 64; later: tl_or_opt_population, tl_or_opt_lds_max_n,
-                            TL_FLAG_OR_OPT_FORCE_SCAN) leave it — a caller built against 5 runs unchanged */
+                            TL_FLAG_OR_OPT_FORCE_SCAN, tl_three_opt_population and its three companions, TL_FLAG_3OPT_POP_*) leave it — a caller built against 5 runs unchanged */
 
 typedef struct tl_ctx tl_ctx;
 
@@ -113,6 +113,9 @@ typedef enum tl_mode {
                                               can leave a result that is no tour — always a permutation while a finite tour exists; the same table and optimum */
 #define TL_FLAG_OR_OPT_FORCE_SCAN (1u << 26) /* tl_or_opt_population: the tours one after the other through the chip-wide descent of tl_or_opt at every n
                                               (default: only beyond the LDS-resident size) */
+#define TL_FLAG_3OPT_POP_FORCE_SCAN (1u << 27) /* tl_three_opt_population: the tours one after the other through the chip-wide descent of tl_three_opt
+                                              (default: tl_three_opt_population_plan chooses); wins over TL_FLAG_3OPT_POP_FORCE_WG */
+#define TL_FLAG_3OPT_POP_FORCE_WG (1u << 28) /* tl_three_opt_population: one workgroup per tour wherever a tour fits the LDS and its Dt the workspace limit */
 #define TL_FLAG_LK_NO_SPECULATION (1u << 22) /* tl_lk, LDS form: the epochs one after the other in one workgroup (default: one workgroup per epoch,
                                               as many consecutive epochs at once as the chip holds, taken in order up to the first accepted one) */
 /* TUNING BUILDS ONLY (libteeline_gpu_tune.so, -DTL_TUNE: `python -m teeline_amd.build --tune`).  Forms that were measured and
@@ -454,6 +457,35 @@ int tl_two_opt_population(tl_ctx *ctx, const float *xy, uint32_t n, const float 
 uint32_t tl_or_opt_lds_max_n(const tl_ctx *ctx);
 int tl_or_opt_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t count,
                          uint32_t *out_pos, float *out_costs, uint32_t *out_moves, tl_stats *stats);
+
+/* 3-opt over a population of `count` explicit tours (init_pos: count x n positions), each by its own three_opt::solve descent
+ * (three_opt.rs:16-51).  Tour r of out_pos / out_costs / out_moves (optional, count entries: the moves that descent applied) is
+ * exactly what tl_three_opt returns for init_pos + r * n alone: the route element for element, the cost bit for bit.  The reference
+ * has no batch form.
+ * n < 4: every output tour is the identity and init_pos is ignored (three_opt.rs:25-28).  count == 0: TL_OK, nothing written.  A row
+ * of init_pos that is not a permutation of 0..n-1: TL_ERR_BADARG, the message names the tour; nothing is launched or written.  A
+ * descent still finding moves after 64 n + 1024 passes (looked at every 16 passes, as tl_three_opt looks: a descent fails here exactly
+ * when tl_three_opt fails on it): TL_ERR_NO_CONVERGE, the message names the tour.
+ * Two forms.  form 1: one persistent workgroup per tour (csrc/three_opt_pop.hip) with the tour, its edges and the move's staging in
+ * that CU's LDS (20 bytes per city) and the tour's own n x (n+1) f32 matrix of distances between tour positions in the context's
+ * workspace, all tours of a batch concurrently; `batch` tours' matrices fit the workspace limit (default 8 GiB,
+ * tl_three_opt_population_work_limit; 0 restores the default), and the entry runs batch after batch.  form 0: the tours one after
+ * the other through tl_three_opt's chip-wide descent.  The results are the same; in form 0 stats->kernel_ms is the sum of the
+ * descents' device times.
+ * tl_three_opt_population_plan (pure: no device, no context) is the rule the entry follows with the context's CU count, LDS and
+ * workspace limit: form 0 where n exceeds the LDS fit (tl_three_opt_pop_max_n; 0 for NULL), where not even one matrix fits
+ * work_bytes (batch 0) or with TL_FLAG_3OPT_POP_FORCE_SCAN; form 1 with TL_FLAG_3OPT_POP_FORCE_WG; otherwise the form its cost model
+ *  estimates faster — few large tours leave most CUs idle in form 1, many small ones pay four launches per move in
+ * form 0.  threads (form 1: a multiple of 64 in 64..1024; form 0: 0) and batch (the matrices that fit, at most count) are outputs,
+ * each optional.  TL_ERR_BADARG for cus < 1 or lds_bytes < 0.
+ * stats (optional): moves and sweeps (passes, each descent's last one finds nothing) summed over the tours, candidates =
+ * sweeps x (C(n,3) - (n-2)), as tl_three_opt counts them. */
+uint32_t tl_three_opt_pop_max_n(const tl_ctx *ctx);
+int tl_three_opt_population_plan(uint32_t n, uint32_t count, int cus, int lds_bytes, uint64_t work_bytes, uint32_t flags, int *form,
+                                 int *threads, uint32_t *batch);
+int tl_three_opt_population_work_limit(tl_ctx *ctx, uint64_t bytes);
+int tl_three_opt_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t count,
+                            uint32_t *out_pos, float *out_costs, uint32_t *out_moves, tl_stats *stats);
 
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts

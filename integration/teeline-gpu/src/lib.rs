@@ -86,6 +86,12 @@ unsafe extern "C" {
     fn tl_or_opt_lds_max_n(ctx: *const TlCtx) -> u32;
     fn tl_or_opt_population(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, count: u32,
                             out_pos: *mut u32, out_costs: *mut f32, out_moves: *mut u32, stats: *mut Stats) -> c_int;
+    fn tl_three_opt_pop_max_n(ctx: *const TlCtx) -> u32;
+    fn tl_three_opt_population_plan(n: u32, count: u32, cus: c_int, lds_bytes: c_int, work_bytes: u64, flags: u32, form: *mut c_int,
+                                    threads: *mut c_int, batch: *mut u32) -> c_int;
+    fn tl_three_opt_population_work_limit(ctx: *mut TlCtx, bytes: u64) -> c_int;
+    fn tl_three_opt_population(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, count: u32,
+                               out_pos: *mut u32, out_costs: *mut f32, out_moves: *mut u32, stats: *mut Stats) -> c_int;
     fn tl_lk(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, opts: *const LkOpts, seed: u64,
              out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats) -> c_int;
     fn tl_nearest_neighbor(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, n_nearest: u32,
@@ -428,6 +434,45 @@ impl Context {
             .collect())
     }
 
+    /// Largest n of the per-workgroup form of `three_opt_population` (either input form).
+    pub fn three_opt_pop_max_n(&self) -> u32 {
+        // SAFETY: a plain query of a live context.
+        unsafe { tl_three_opt_pop_max_n(self.raw) }
+    }
+
+    /// Cap on the workspace of `three_opt_population`'s per-tour matrices (0: the default, 8 GiB).
+    pub fn three_opt_population_work_limit(&self, bytes: u64) -> Result<(), Error> {
+        // SAFETY: a plain setter of a live context.
+        let rc = unsafe { tl_three_opt_population_work_limit(self.raw, bytes) };
+        self.check(rc)
+    }
+
+    /// 3-opt over a population: `init_pos` holds `count` tours of n positions back to back, each refined by its own
+    /// `three_opt::solve` descent (`tl_three_opt_population`).  Tour k of the result is what `three_opt` returns for it alone;
+    /// its `stats` are the call's (sums over the population) with `moves` replaced by that tour's own.
+    pub fn three_opt_population(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: &[u32]) -> Result<Vec<Tour>, Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, None);
+        if n == 0 {
+            return Ok(Vec::new());
+        }
+        assert!(init_pos.len() % n as usize == 0, "init_pos holds whole tours of n positions");
+        let count = init_pos.len() / n as usize;
+        let mut pos = vec![0u32; init_pos.len()];
+        let mut costs = vec![0f32; count];
+        let mut moves = vec![0u32; count];
+        let mut stats = Stats::default();
+        // SAFETY: as in two_opt; every output buffer holds count (x n) entries.
+        let rc = unsafe {
+            tl_three_opt_population(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), init_pos.as_ptr(), count as u32, pos.as_mut_ptr(),
+                                    costs.as_mut_ptr(), moves.as_mut_ptr(), &mut stats)
+        };
+        self.check(rc)?;
+        Ok((0..count)
+            .map(|k| Tour { pos: pos[k * n as usize..(k + 1) * n as usize].to_vec(), cost: costs[k], stats: Stats { moves: moves[k] as u64, ..stats } })
+            .collect())
+    }
+
     /// `lin_kernighan::solve` (lin_kernighan.rs:35-100).  The search is Euclidean over `xy` (the reference rebuilds its own
     /// matrix, :41); `dm_packed` (problem.distances of a GEO / EXPLICIT problem) feeds the NN seed (:47-55) and the total (:99).
     /// `seed` drives the double-bridge kicks (the reference draws them from an unseeded thread RNG, :73).
@@ -513,6 +558,19 @@ pub const SAVINGS_HUB_AUTO: u32 = 0xFFFF_FFFF;
 pub const FLAG_BHK_EXACT_WALK: u32 = 1 << 25;
 /// `tl_create` flag: `or_opt_population` runs its tours one after the other through `or_opt`'s chip-wide descent at every n.
 pub const FLAG_OR_OPT_FORCE_SCAN: u32 = 1 << 26;
+/// The rule `three_opt_population` follows (`tl_three_opt_population_plan`; pure, no device): `(form, threads, batch)` for `count`
+/// tours of n cities on a device of `cus` CUs with `lds_bytes` of LDS and `work_bytes` of workspace; `None` for a device that is none.
+pub fn three_opt_population_plan(n: u32, count: u32, cus: i32, lds_bytes: i32, work_bytes: u64, flags: u32) -> Option<(i32, i32, u32)> {
+    let (mut form, mut threads, mut batch) = (0 as c_int, 0 as c_int, 0u32);
+    // SAFETY: the three outputs are live locals.
+    let rc = unsafe { tl_three_opt_population_plan(n, count, cus, lds_bytes, work_bytes, flags, &mut form, &mut threads, &mut batch) };
+    if rc == 0 { Some((form, threads, batch)) } else { None }
+}
+
+/// `tl_create` flag: `three_opt_population` runs its tours one after the other through `three_opt`'s chip-wide descent.
+pub const FLAG_3OPT_POP_FORCE_SCAN: u32 = 1 << 27;
+/// `tl_create` flag: `three_opt_population` runs one workgroup per tour wherever a tour fits.
+pub const FLAG_3OPT_POP_FORCE_WG: u32 = 1 << 28;
 /// Largest n `bellman_karp` takes (a table of 2^(n-1) rows of 128 bytes).
 pub const BHK_MAX_N: u32 = 26;
 

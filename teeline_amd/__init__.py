@@ -9,7 +9,7 @@ paths are hand-written HIP kernels for gfx950.  There is no CPU fallback: withou
 and a gfx950 device every solver call raises.
 """
 from . import _capi
-from ._capi import (TL_BHK_MAX_N, TL_FLAG_BHK_EXACT_WALK, TL_FLAG_2OPT_FORCE_HBM, TL_FLAG_2OPT_FX, TL_FLAG_2OPT_NL_ALWAYS, TL_FLAG_2OPT_NO_NL, TL_FLAG_2OPT_NT256, TL_FLAG_2OPT_NT512, TL_FLAG_COUNT_WORK, TL_FLAG_KNN_BRUTE, TL_FLAG_KNN_1LANE, TL_FLAG_KNN_4LANES, TL_FLAG_LK_NO_SPLIT,
+from ._capi import (TL_BHK_MAX_N, TL_FLAG_3OPT_POP_FORCE_SCAN, TL_FLAG_3OPT_POP_FORCE_WG, TL_FLAG_BHK_EXACT_WALK, TL_FLAG_2OPT_FORCE_HBM, TL_FLAG_2OPT_FX, TL_FLAG_2OPT_NL_ALWAYS, TL_FLAG_2OPT_NO_NL, TL_FLAG_2OPT_NT256, TL_FLAG_2OPT_NT512, TL_FLAG_COUNT_WORK, TL_FLAG_KNN_BRUTE, TL_FLAG_KNN_1LANE, TL_FLAG_KNN_4LANES, TL_FLAG_LK_NO_SPLIT,
                     TL_FLAG_LK_CHIP_WIDE, TL_FLAG_LK_CLASSIC_VIEW, TL_FLAG_LK_ILS_LDS, TL_FLAG_LK_NO_GRAPH, TL_FLAG_LK_NO_SPECULATION, TL_FLAG_LK_NO_SUBCHAINS, TL_FLAG_LK_ONE_WORKGROUP, TL_FLAG_LK_SCAN_PERSIST, TL_FLAG_LK_SEPARATE_PICK, TL_FLAG_LK_SEPARATE_STEP, TL_FLAG_LK_SMALL, TL_FLAG_LK_SPLIT2, TL_FLAG_MULTISTART_RCCL, TL_FLAG_NONE, TL_FLAG_NO_PRUNE, TL_FLAG_OR_OPT_FORCE_SCAN,
                     TL_MODE_BEST_SWEEP, TL_MODE_REF_ORDER, ReferencePanics, TeelineGpuError)
 from .host import (Context, HeuristicOptions, KDPoint, LKOptions, Solution, TspProblem, default_context,

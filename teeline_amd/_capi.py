@@ -34,6 +34,8 @@ TL_FLAG_LK_CLASSIC_VIEW = 1 << 23  # tl_lk chip-wide: cand -> xy -> next -> xy l
 TL_FLAG_LK_NO_SPECULATION = 1 << 22  # tl_lk, LDS form: epochs one after the other (default: a batch of consecutive epochs at once)
 TL_FLAG_BHK_EXACT_WALK = 1 << 25  # tl_bellman_karp: the route by exact f32 equality instead of the reference's tolerance walk (always a tour)
 TL_FLAG_OR_OPT_FORCE_SCAN = 1 << 26  # tl_or_opt_population: tour after tour through tl_or_opt's chip-wide descent at every n
+TL_FLAG_3OPT_POP_FORCE_SCAN = 1 << 27  # tl_three_opt_population: tour after tour through tl_three_opt's chip-wide descent
+TL_FLAG_3OPT_POP_FORCE_WG = 1 << 28  # tl_three_opt_population: one workgroup per tour wherever it fits
 TL_BHK_MAX_N = 26  # tl_bellman_karp: largest n (a table of 2^(n-1) rows of 128 bytes: 4 GiB)
 TL_FLAG_LK_SMALL = 1 << 9  # tl_lk: the LDS-resident single-workgroup form wherever it fits
 TL_FLAG_COUNT_WORK = 1 << 8  # the LDS 2-opt kernel also counts the work of its cascade (stats words 5..8); ~8 % slower
@@ -52,6 +54,7 @@ SYMBOLS = [
     "tl_lk_live", "tl_two_opt_neighbour_lists", "tl_two_opt_plan", "tl_multistart_shard", "tl_two_opt_last_counters",
     "tl_greedy_edge", "tl_savings_hub", "tl_savings", "tl_christofides", "tl_bellman_karp",
     "tl_or_opt_population", "tl_or_opt_lds_max_n",
+    "tl_three_opt_population", "tl_three_opt_pop_max_n", "tl_three_opt_population_plan", "tl_three_opt_population_work_limit",
 ]
 
 
@@ -147,5 +150,10 @@ def load():
     L.tl_or_opt_lds_max_n.argtypes = [vp]
     L.tl_or_opt_lds_max_n.restype = u32
     L.tl_or_opt_population.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, C.POINTER(TlStats)]
+    L.tl_three_opt_pop_max_n.argtypes = [vp]
+    L.tl_three_opt_pop_max_n.restype = u32
+    L.tl_three_opt_population.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, C.POINTER(TlStats)]
+    L.tl_three_opt_population_plan.argtypes = [u32, u32, C.c_int, C.c_int, C.c_uint64, u32, C.POINTER(i32), C.POINTER(i32), C.POINTER(u32)]
+    L.tl_three_opt_population_work_limit.argtypes = [vp, C.c_uint64]
     _lib = L
     return L

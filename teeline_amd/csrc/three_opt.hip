@@ -103,6 +103,7 @@ __global__ __launch_bounds__(kT3) void k_three_opt_scan(ThreeOptArgs A)
 
     float bs = 0.0f;  // three_opt.rs:61 best_savings = 0.0
     uint32_t bij = 0xFFFFFFFFu, bkc = 0xFFFFFFFFu;
+    // (three_opt_pop.hip carries a copy of this loop for its per-workgroup descent: the two change together.)
     // A lane owns a column k and walks the chunk's j in registers: everything that depends on (i, k) only is loaded
     // once, the row of C = path[j] rolls into the row of the next j (D = path[j+1] is the next j's C), so a triple
     // costs two coalesced loads and the seven sums.  No LDS, no barrier.

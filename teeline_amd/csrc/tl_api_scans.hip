@@ -1,5 +1,5 @@
 // tl_api_scans.hip — C ABI, the best-improvement scans: tl_three_opt* (src/tsp/three_opt.rs:16-218) and tl_or_opt* (src/tsp/or_opt.rs:18-184),
-// tl_or_opt_population included.
+// tl_or_opt_population and tl_three_opt_population included.
 #include "tl_api_common.h"
 
 using namespace tl;
@@ -365,6 +365,166 @@ extern "C" int tl_or_opt_population(tl_ctx *c, const float *xy, uint32_t n, cons
         stats->moves = moves;
         stats->sweeps = passes;
         stats->candidates = passes * or_opt_per_pass(n);
+        stamp_times(c, stats, t0);
+    }
+    return TL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// 3-opt over a population of tours (three_opt_pop.hip)
+// ------------------------------------------------------------------------------------------------
+// The cost model behind tl_three_opt_population_plan: a pass of one tour is triples(n) = C(n,3) - (n-2) triples, and both forms run
+// the same passes, so the forms are compared per pass.
+//   form 1: the tours of a batch run one per CU at kPopRcu triples a second each, in ceil(count / cus) rounds;
+//   form 0: every tour's pass has the whole chip at kPopRchip triples a second plus kPopTpass of launches, the global reduction
+//           and the host's share of a poll every 16 passes.
+// Measured on one MI355X (256 CUs), 2026-10-19, scripts/timing_three_opt_population.py; NOTEBOOK.md, "3-opt for a population".
+//   kPopRcu    the mean tour's triples over the kernel time of 256 random tours at n = 500 (2.02e9) — a round lasts as long as its
+//              longest descent, so that wait is inside the figure.  The rate is not one number: a single tour runs at 2.6e9 at
+//              n = 500 and 1.1e9 at n = 100 (barriers and the Dt rebuild weigh more the smaller n); the figure taken is the one
+//              near the sizes where the two forms meet, which is where the choice matters.
+//   kPopRchip, kPopTpass: least-squares fit of the loop's wall seconds per pass, t = triples / R + T, over n = 52 ... 1 002.
+static constexpr double kPopRcu = 2.0e9;     // triples / s on one CU (form 1)
+static constexpr double kPopRchip = 6.9e11;  // triples / s of the chip-wide scan (form 0)
+static constexpr double kPopTpass = 23e-6;   // s of overhead per chip-wide pass (form 0)
+static constexpr uint64_t kPopWorkDefault = 8ull << 30;  // the precedent of the matrix-form lists
+
+static uint64_t three_opt_per_pass(uint32_t n)
+{
+    const uint64_t nn = n;
+    return nn * (nn - 1) * (nn - 2) / 6 - (nn - 2);  // C(n,3) - (n-2) triples per pass
+}
+
+extern "C" uint32_t tl_three_opt_pop_max_n(const tl_ctx *c) { return c ? three_opt_pop_max_n(c->lds_bytes) : 0u; }
+
+extern "C" int tl_three_opt_population_plan(uint32_t n, uint32_t count, int cus, int lds_bytes, uint64_t work_bytes, uint32_t flags, int *form,
+                                            int *threads, uint32_t *batch)
+{
+    if (cus < 1 || lds_bytes < 0) return TL_ERR_BADARG;
+    const uint64_t dt_bytes = (uint64_t)n * ((uint64_t)n + 1u) * 4u;
+    uint64_t b = dt_bytes ? work_bytes / dt_bytes : count;
+    if (b > count) b = count;
+    int f;
+    if (n < 4 || count == 0 || b == 0 || n > three_opt_pop_max_n(lds_bytes) || (flags & TL_FLAG_3OPT_POP_FORCE_SCAN)) {
+        f = 0;
+    } else if (flags & TL_FLAG_3OPT_POP_FORCE_WG) {
+        f = 1;
+    } else {
+        const double triples = (double)three_opt_per_pass(n);
+        const double rounds = (double)((count + (uint32_t)cus - 1u) / (uint32_t)cus);
+        const double est_wg = rounds * triples / kPopRcu, est_loop = (double)count * (triples / kPopRchip + kPopTpass);
+        f = est_wg <= est_loop ? 1 : 0;
+    }
+    if (form) *form = f;
+    if (threads) *threads = f ? three_opt_pop_threads(n, (uint32_t)b, cus, lds_bytes) : 0;
+    if (batch) *batch = (uint32_t)b;
+    return TL_OK;
+}
+
+extern "C" int tl_three_opt_population_work_limit(tl_ctx *c, uint64_t bytes)
+{
+    TL_ENTER(c);
+    if (!c) return fail(c, TL_ERR_BADARG, "tl_three_opt_population_work_limit: NULL context");
+    c->three_opt_pop_work = bytes;
+    return TL_OK;
+}
+
+// Every tour refined by its own descent; tour r's result is tl_three_opt's for it alone.  Form 1 (tl_three_opt_population_plan): one
+// workgroup per tour, batch after batch; form 0: the tours one after the other through the chip-wide descent.
+extern "C" int tl_three_opt_population(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t count,
+                                       uint32_t *out_pos, float *out_costs, uint32_t *out_moves, tl_stats *stats)
+{
+    TL_ENTER(c);
+    if (!c || (!xy && !dm_packed)) return fail(c, TL_ERR_BADARG, "tl_three_opt_population: NULL argument");
+    if (count == 0) return TL_OK;
+    if (!out_pos || (n >= 4 && !init_pos)) return fail(c, TL_ERR_BADARG, "tl_three_opt_population: NULL argument");
+    if (n >= 4)
+        for (uint32_t r = 0; r < count; ++r)
+            if (!is_permutation(init_pos + (size_t)r * n, n))
+                return fail(c, TL_ERR_BADARG, "tl_three_opt_population: tour %u is not a permutation of 0..n-1", r);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    int rc;
+    if (n < 4) {  // three_opt.rs:25-28: the cities' order, init_tour ignored
+        float cst = 0.0f;
+        for (uint32_t k = 0; k < n; ++k) out_pos[k] = k;
+        if (out_costs && n >= 2 && (rc = tl_tour_length(c, xy, dm_packed, n, out_pos, &cst))) return rc;
+        for (uint32_t r = 0; r < count; ++r) {
+            for (uint32_t k = 0; k < n; ++k) out_pos[(size_t)r * n + k] = k;
+            if (out_costs) out_costs[r] = cst;
+            if (out_moves) out_moves[r] = 0u;
+        }
+        return TL_OK;
+    }
+    int form = 0, threads = 0;
+    uint32_t batch = 0;
+    if ((rc = tl_three_opt_population_plan(n, count, c->cus, c->lds_bytes, c->three_opt_pop_work ? c->three_opt_pop_work : kPopWorkDefault, c->flags,
+                                           &form, &threads, &batch)))
+        return fail(c, rc, "tl_three_opt_population: no plan for this device");
+    if (form == 0) {
+        tl_stats acc{};
+        for (uint32_t r = 0; r < count; ++r) {
+            float cst = 0.0f;
+            tl_stats st1{};
+            if ((rc = three_opt_run(c, xy, n, dm_packed, init_pos + (size_t)r * n, out_pos + (size_t)r * n, &cst, &st1, nullptr, 0, nullptr))) return rc;
+            if (out_costs) out_costs[r] = cst;
+            if (out_moves) out_moves[r] = (uint32_t)st1.moves;
+            acc.sweeps += st1.sweeps;
+            acc.moves += st1.moves;
+            acc.candidates += st1.candidates;
+            acc.kernel_ms += st1.kernel_ms;
+        }
+        if (stats) {
+            *stats = acc;
+            stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return TL_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t words = (size_t)count * n, dt_words = (size_t)n * ((size_t)n + 1u);
+    if ((rc = ensure(c, c->init, words * 4)) || (rc = ensure(c, c->out_pos, words * 4)) || (rc = ensure(c, c->out_cost, (size_t)count * 4)) ||
+        (rc = ensure(c, c->misc, (size_t)count * 16)) || (rc = ensure(c, c->work, (size_t)batch * dt_words * 4)))
+        return rc;
+    ThreeOptPopArgs A{};
+    if ((rc = upload_input(c, xy, dm_packed, n, &A.xy, &A.dm))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->init.p, init_pos, words * 4, hipMemcpyHostToDevice, c->stream));
+    A.Dt = (float *)c->work.p;
+    A.n = n;
+    // scan_descent's cap as scan_descent applies it: it looks once per kScanBatch passes and gives up when the descent is still moving at
+    // the first look beyond 64 n + 1024 passes — so a descent fails here exactly when it fails there
+    A.max_passes = (64u * n + 1024u) / (uint32_t)kScanBatch * (uint32_t)kScanBatch + (uint32_t)kScanBatch;
+    c->ev_valid = false;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    for (uint32_t first = 0; first < count; first += batch) {  // a batch's workgroups own the workspace's matrices; the stream orders the batches
+        const uint32_t cnt = count - first < batch ? count - first : batch;
+        A.init = (const uint32_t *)c->init.p + (size_t)first * n;
+        A.out_pos = (uint32_t *)c->out_pos.p + (size_t)first * n;
+        A.out_cost = (float *)c->out_cost.p + first;
+        A.out_run = (uint32_t *)c->misc.p + 4u * (size_t)first;
+        HIPCHK(c, launch_three_opt_pop(A, cnt, threads, c->stream));
+    }
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    c->ev_valid = true;
+    std::vector<uint32_t> run((size_t)count * 4);
+    std::vector<float> costs(count);
+    HIPCHK(c, hipMemcpyAsync(run.data(), c->misc.p, (size_t)count * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(costs.data(), c->out_cost.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t r = 0; r < count; ++r)
+        if (run[4u * r + 2u] != 0u) return fail(c, TL_ERR_NO_CONVERGE, "three_opt: pass cap reached in tour %u", r);
+    HIPCHK(c, hipMemcpyAsync(out_pos, c->out_pos.p, words * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    uint64_t moves = 0, passes = 0;
+    for (uint32_t r = 0; r < count; ++r) {
+        if (out_costs) out_costs[r] = costs[r];
+        if (out_moves) out_moves[r] = run[4u * r];
+        moves += run[4u * r];
+        passes += run[4u * r + 1u];
+    }
+    if (stats) {
+        stats->moves = moves;
+        stats->sweeps = passes;
+        stats->candidates = passes * three_opt_per_pass(n);
         stamp_times(c, stats, t0);
     }
     return TL_OK;

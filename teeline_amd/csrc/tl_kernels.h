@@ -204,6 +204,23 @@ struct ThreeOptArgs {
 size_t three_opt_scan_lds_bytes(uint32_t n);
 hipError_t launch_three_opt_pass(const ThreeOptArgs &A, uint32_t nblocks, bool dm, int apply, hipStream_t s, int lds_budget);
 
+// three_opt_pop.hip — a population of tours, one workgroup per tour, the whole descent without a launch per move
+struct ThreeOptPopArgs {
+    const float2 *xy;      // n cities, city order (coordinate form)
+    const float *dm;       // packed matrix or nullptr
+    const uint32_t *init;  // [count][n] start tours of this launch (permutations: the host checks)
+    uint32_t *out_pos;     // [count][n]
+    float *out_cost;       // [count] tour_length of the result
+    uint32_t *out_run;     // [count][4] moves, passes, status (1: pass cap reached), 0
+    float *Dt;             // [count][n][n+1] each tour's distances between tour positions (workspace)
+    uint32_t n;
+    uint32_t max_passes;   // a descent stops (status 1) when it has run this many passes and still finds a move
+};
+size_t three_opt_pop_lds_bytes(uint32_t n);          // LDS of one tour's workgroup (either form)
+uint32_t three_opt_pop_max_n(int lds_budget);        // largest n whose state fits
+int three_opt_pop_threads(uint32_t n, uint32_t count, int cus, int lds_budget);
+hipError_t launch_three_opt_pop(const ThreeOptPopArgs &A, uint32_t count, int threads, hipStream_t s);
+
 // or_opt.hip
 struct OrOptBest {
     uint32_t found, delta_bits, i, j, seg_len, reversed;

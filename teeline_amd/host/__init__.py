@@ -73,6 +73,13 @@ class Context:
     def or_opt_lds_max_n(self):
         return int(self._lib.tl_or_opt_lds_max_n(self._h))
 
+    def three_opt_pop_max_n(self):
+        return int(self._lib.tl_three_opt_pop_max_n(self._h))
+
+    def three_opt_population_work_limit(self, nbytes):
+        """Cap on the workspace of tl_three_opt_population's per-tour matrices (0: the default, 8 GiB)."""
+        self.check(self._lib.tl_three_opt_population_work_limit(self._h, int(nbytes)))
+
     def last_kernel_ms(self):
         ms = C.c_double()
         self.check(self._lib.tl_last_kernel_ms(self._h, C.byref(ms)))

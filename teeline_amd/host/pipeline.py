@@ -108,20 +108,20 @@ def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact
     return outcomes
 
 
-POPULATION_SOLVERS = ("two_opt", "or_opt")  # the solvers with a population entry (tl_two_opt_population, tl_or_opt_population)
+POPULATION_SOLVERS = ("two_opt", "three_opt", "or_opt")  # the solvers with a population entry (tl_two_opt_population, tl_three_opt_population, tl_or_opt_population)
 
 
 def run_population(problem, steps, init_tours, *, ctx=None):
     """run_pipeline_stages for a population of tours: every stage runs through its population entry (one descent per tour, all
-    concurrently) and feeds the next.  steps: drawn from "2opt" / "or_opt" and their long names; any other step is a ValueError
+    concurrently) and feeds the next.  steps: drawn from "2opt" / "3opt" / "or_opt" and their long names; any other step is a ValueError
     that names it, raised before anything runs.  Returns one list of StageOutcome per tour — entry k equals
     run_pipeline_stages(problem, steps) started from init_tours[k]; a stage's duration_ms is the whole population's."""
-    from . import or_opt, two_opt, validate_tour
+    from . import or_opt, three_opt, two_opt, validate_tour
     steps = list(steps)
     for step in steps:
         if SOLVER_NAMES.get(step) not in POPULATION_SOLVERS:
             raise ValueError(f"step `{step}` has no population form (population pipelines take {sorted(k for k, v in SOLVER_NAMES.items() if v in POPULATION_SOLVERS)})")
-    mods = {"two_opt": two_opt, "or_opt": or_opt}
+    mods = {"two_opt": two_opt, "three_opt": three_opt, "or_opt": or_opt}
     tours = [list(t) for t in init_tours]
     outcomes = [[] for _ in tours]
     for step in steps:

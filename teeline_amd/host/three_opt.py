@@ -38,6 +38,35 @@ def solve(problem, opts=None, progress_tx=None, init_tour=None, *, ctx=None):
     return Solution(cost.value, problem.ids[out], problem, st.as_dict())
 
 
+def solve_population(problem, init_tours, *, ctx=None):
+    """Refine a population of tours (lists of city ids), each by its own three_opt::solve descent (tl_three_opt_population: one
+    workgroup per tour, all concurrently, or tour after tour through the chip-wide descent — the library picks the faster form).
+    Returns one Solution per tour; Solution k equals solve(problem, None, None, init_tours[k]), and its stats are the call's (sums
+    over the population) with `moves` replaced by that tour's own."""
+    from . import Solution, default_context
+    from .. import _capi
+    n = len(problem)
+    count = len(init_tours)
+    for k, tour in enumerate(init_tours):  # the library reads count x n u32 values: checked before any pointer is taken
+        if len(tour) != n:
+            raise _capi.TeelineGpuError(_capi.TL_ERR_BADARG, f"tour {k} has {len(tour)} cities, the problem {n}")
+    ctx = ctx or default_context()
+    init = np.empty((count, n), dtype=np.uint32)
+    for k, tour in enumerate(init_tours):
+        init[k] = problem.positions_of(tour)
+    packed = problem.explicit_packed()
+    out = np.empty((count, n), dtype=np.uint32)
+    costs = np.empty(count, dtype=np.float32)
+    moves = np.zeros(count, dtype=np.uint32)
+    st = _capi.TlStats()
+    ctx.check(ctx.lib.tl_three_opt_population(ctx.handle, problem.xy.ctypes.data_as(C.c_void_p), n,
+                                              None if packed is None else packed.ctypes.data_as(C.c_void_p),
+                                              init.ctypes.data_as(C.c_void_p), count, out.ctypes.data_as(C.c_void_p),
+                                              costs.ctypes.data_as(C.c_void_p), moves.ctypes.data_as(C.c_void_p), C.byref(st)))
+    stats = st.as_dict()
+    return [Solution(float(costs[k]), problem.ids[out[k]], problem, dict(stats, moves=int(moves[k]))) for k in range(count)]
+
+
 def apply_3opt(path, i, j, k, case):
     """three_opt.rs:186-218 apply_3opt on a numpy path, in place: cases 1-3 reverse segments, 4-7 swap path[i+1..=j] and
     path[j+1..=k] with either reversed."""

@@ -344,6 +344,30 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOp
     (*progress_tx)(ProgressKind::Done, s.route_, cost);
     return s;
 }
+
+// A population of tours, each refined by its own descent (tl_three_opt_population: one workgroup per tour or tour after tour, the
+// library picks); element k equals solve(ctx, problem, {}, nullptr, &init_tours[k]).  moves (optional): the moves each descent applied.
+inline std::vector<Solution> solve_population(Context &ctx, const TspProblem &problem, const std::vector<std::vector<size_t>> &init_tours,
+                                              std::vector<uint32_t> *moves = nullptr)
+{
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size(), count = (uint32_t)init_tours.size();
+    std::vector<uint32_t> init((size_t)count * n), out((size_t)count * n), mv(count);
+    for (uint32_t k = 0; k < count; ++k) {
+        const auto pos = problem.positions_of(init_tours[k]);
+        std::copy(pos.begin(), pos.end(), init.begin() + (size_t)k * n);
+    }
+    std::vector<float> costs(count);
+    tl_stats st{};
+    ctx.check(tl_three_opt_population(ctx.get(), xy.data(), n, problem.explicit_packed(), init.data(), count, out.data(), costs.data(), mv.data(), &st));
+    std::vector<Solution> res;
+    for (uint32_t k = 0; k < count; ++k) {
+        std::vector<uint32_t> one(out.begin() + (size_t)k * n, out.begin() + (size_t)(k + 1) * n);
+        res.push_back(detail::finish(problem, one, costs[k], st, nullptr));
+    }
+    if (moves) *moves = mv;
+    return res;
+}
 }  // namespace three_opt
 
 namespace or_opt {  // or_opt.rs:18-74
