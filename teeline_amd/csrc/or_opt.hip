@@ -34,25 +34,13 @@ static uint32_t or_opt_chunks(uint32_t n)  // 63-wide chunks of insertion points
 }
 static uint32_t or_opt_grid_y(uint32_t n) { return ((n + 62u) / 63u + or_opt_chunks(n) - 1u) / or_opt_chunks(n); }
 
-template <bool DM>
-struct Dist {
-    const float2 *Pt;
-    const float *dm;
-    const uint32_t *perm;
-    __device__ __forceinline__ float operator()(uint32_t kp, uint32_t kq) const  // tour positions
-    {
-        if (DM) return dm_lookup(dm, perm[kp], perm[kq]);
-        return dist(Pt[kp], Pt[kq]);
-    }
-};
-
 }  // namespace
 
 // One wave = kOrIR consecutive segment starts i0..i0+kOrIR-1 x a slab of insertion points (`chunks` chunks of 63): or_scan_rows, or_opt_scan.h
 template <bool DM>
 __global__ __launch_bounds__(kOrWaves * 64) void k_or_scan(OrOptArgs A, uint32_t chunks)
 {
-    __shared__ unsigned long long s_key[kOrWaves][2];
+    __shared__ unsigned long long s_key[kOrWaves * 2];
     if (A.run && A.run->done) return;  // a later pass of a batch whose descent is over
     const uint32_t n = A.n;
     const int lane = threadIdx.x & 63;
@@ -65,18 +53,8 @@ __global__ __launch_bounds__(kOrWaves * 64) void k_or_scan(OrOptArgs A, uint32_t
         const Dist<DM> D{A.Pt, A.dm, A.perm};
         or_scan_rows(D, A.E, n, i0, jlo, chunks, lane, best, bestd);
     }
-    best = wave_min_key(best);
-    if (lane == 0) {
-        s_key[wave][0] = (unsigned long long)(best >> 64);
-        s_key[wave][1] = (unsigned long long)best;
-    }
-    TL_SYNC();
+    const key_t k = block_min_key(best, s_key, lane, (uint32_t)wave, kOrWaves);
     if (threadIdx.x == 0) {
-        key_t k = make_key(s_key[0][0], s_key[0][1]);
-        for (int w = 1; w < kOrWaves; ++w) {
-            const key_t o = make_key(s_key[w][0], s_key[w][1]);
-            k = o < k ? o : k;
-        }
         unsigned long long *out = A.partials + 2u * (size_t)(blockIdx.y * gridDim.x + blockIdx.x);
         out[0] = (unsigned long long)(k >> 64);
         out[1] = (unsigned long long)k;
@@ -101,7 +79,7 @@ __global__ __launch_bounds__(1024) void k_or_pick(OrOptArgs A, uint32_t nblocks,
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // the pre-move tour: in LDS where n entries fit, else in the workspace (one workgroup: its own barrier orders the copy)
     uint32_t *old = stage_lds ? reinterpret_cast<uint32_t *>(smem) : A.scratch;
-    __shared__ unsigned long long s_key[16][2];
+    __shared__ unsigned long long s_key[16 * 2];
     const uint32_t tid = threadIdx.x, n = A.n;
     const int lane = tid & 63, wave = tid >> 6;
     if (A.run && A.run->done) return;
@@ -110,22 +88,10 @@ __global__ __launch_bounds__(1024) void k_or_pick(OrOptArgs A, uint32_t nblocks,
         const key_t k = make_key(A.partials[2u * (size_t)b], A.partials[2u * (size_t)b + 1u]);
         best = k < best ? k : best;
     }
-    best = wave_min_key(best);
-    if (lane == 0) {
-        s_key[wave][0] = (unsigned long long)(best >> 64);
-        s_key[wave][1] = (unsigned long long)best;
-    }
-    TL_SYNC();
-    best = make_key(s_key[0][0], s_key[0][1]);
-    for (int w = 1; w < 16; ++w) {
-        const key_t o = make_key(s_key[w][0], s_key[w][1]);
-        best = o < best ? o : best;
-    }
+    best = block_min_key(best, s_key, lane, (uint32_t)wave, 16u);
     const bool found = best != no_key();
-    const unsigned long long order = (unsigned long long)best;
-    const uint32_t reversed = (uint32_t)(order & 1ull), j = (uint32_t)((order >> 1) % n);
-    const unsigned long long row = (order >> 1) / n;
-    const uint32_t seg_len = (uint32_t)(row / n) + 1u, i = (uint32_t)(row % n);
+    const OrMove mv = or_decode(best, n);
+    const uint32_t i = mv.i, j = mv.j, seg_len = mv.seg_len, reversed = mv.reversed;
     if (tid == 0) {
         A.best->found = found ? 1u : 0u;
         A.best->delta_bits = ~(uint32_t)(unsigned long long)(best >> 64);
@@ -133,21 +99,7 @@ __global__ __launch_bounds__(1024) void k_or_pick(OrOptArgs A, uint32_t nblocks,
         A.best->j = j;
         A.best->seg_len = seg_len;
         A.best->reversed = reversed;
-        if (A.run) {  // or_opt.rs:45 `while let Some(best) = find_best_move(..)`: count the pass, file the move or end the descent
-            A.run->passes += 1u;
-            if (!found) {
-                A.run->done = 1u;
-            } else {
-                const uint32_t m = A.run->moves;
-                if (m < A.run->log_cap) {
-                    A.log[4u * m + 0u] = i;
-                    A.log[4u * m + 1u] = j;
-                    A.log[4u * m + 2u] = seg_len;
-                    A.log[4u * m + 3u] = reversed;
-                }
-                A.run->moves = m + 1u;
-            }
-        }
+        scan_file_pass(A.run, A.log, found, i, j, seg_len, reversed);  // or_opt.rs:45
     }
     if (!found || !apply) return;
     uint32_t *path = A.perm;

@@ -20,22 +20,10 @@ namespace {
 constexpr int kOrLdsMaxWaves = 16;
 constexpr size_t kOrLdsSlotBytes = (size_t)kOrLdsMaxWaves * 16;  // the waves' key slots
 
-template <bool DM>
-struct DistLds {
-    const float2 *Pt;  // LDS
-    const uint32_t *perm;  // LDS
-    const float *dm;   // HBM, packed lower triangle
-    __device__ __forceinline__ float operator()(uint32_t kp, uint32_t kq) const  // tour positions
-    {
-        if (DM) return dm_lookup(dm, perm[kp], perm[kq]);
-        return dist(Pt[kp], Pt[kq]);
-    }
-};
-
 }  // namespace
 
 template <bool DM>
-__global__ __launch_bounds__(kOrLdsMaxWaves * 64) void k_or_lds(OrOptLdsArgs A)
+__global__ __launch_bounds__(kOrLdsMaxWaves * 64) void k_or_lds(PopArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t n = A.n, tid = threadIdx.x, nt = blockDim.x, tour = blockIdx.x;
@@ -45,7 +33,7 @@ __global__ __launch_bounds__(kOrLdsMaxWaves * 64) void k_or_lds(OrOptLdsArgs A)
     uint32_t *perm = reinterpret_cast<uint32_t *>(smem + (DM ? 0 : (size_t)n * 8));
     float *E = reinterpret_cast<float *>(perm + n);
     unsigned long long *s_key = reinterpret_cast<unsigned long long *>(smem + (DM ? 0 : (size_t)n * 8) + (size_t)n * 8);
-    const DistLds<DM> D{Pt, perm, A.dm};
+    const Dist<DM> D{Pt, A.dm, perm};  // Pt and perm in LDS, the packed matrix in HBM
 
     const uint32_t *init = A.init + (size_t)tour * n;
     for (uint32_t k = tid; k < n; k += nt) {
@@ -63,17 +51,7 @@ __global__ __launch_bounds__(kOrLdsMaxWaves * 64) void k_or_lds(OrOptLdsArgs A)
         key_t best = no_key();
         float bestd = __builtin_inff();
         for (uint32_t g = wave; g < groups; g += nwaves) or_scan_rows(D, E, n, g * kOrIR, 0u, chunks, lane, best, bestd);
-        best = wave_min_key(best);
-        if (lane == 0) {
-            s_key[2u * wave] = (unsigned long long)(best >> 64);
-            s_key[2u * wave + 1u] = (unsigned long long)best;
-        }
-        TL_SYNC();
-        best = make_key(s_key[0], s_key[1]);
-        for (uint32_t w = 1; w < nwaves; ++w) {
-            const key_t o = make_key(s_key[2u * w], s_key[2u * w + 1u]);
-            best = o < best ? o : best;
-        }
+        best = block_min_key(best, s_key, lane, wave, nwaves);
         ++passes;  // or_opt.rs:45 `while let Some(best) = find_best_move(..)`: the last pass finds nothing
         if (best == no_key()) break;
         if (passes >= A.max_passes) {
@@ -127,18 +105,7 @@ __global__ __launch_bounds__(kOrLdsMaxWaves * 64) void k_or_lds(OrOptLdsArgs A)
         TL_SYNC();
     }
 
-    uint32_t *out = A.out_pos + (size_t)tour * n;
-    for (uint32_t k = tid; k < n; k += nt) out[k] = perm[k];
-    if (tid == 0) {
-        // tour_length (distance_matrix.rs:235-245): the closing edge first, then the n - 1 edges in order, sequential f32
-        float total = E[n - 1u];
-        for (uint32_t k = 0; k + 1u < n; ++k) total += E[k];
-        A.out_cost[tour] = total;
-        A.out_run[4u * tour + 0u] = moves;
-        A.out_run[4u * tour + 1u] = passes;
-        A.out_run[4u * tour + 2u] = status;
-        A.out_run[4u * tour + 3u] = 0u;
-    }
+    pop_finish(A, perm, E, moves, passes, status);
 }
 
 size_t or_opt_lds_bytes(uint32_t n, bool dm) { return (size_t)n * (dm ? 8 : 16) + kOrLdsSlotBytes; }
@@ -150,30 +117,15 @@ uint32_t or_opt_lds_max_n(int lds_budget, bool dm)
     return m > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)m;
 }
 
-// Threads per tour.  A pass is (n / kOrIR) wave-sized units of work, so a tour cannot use more waves than that; beyond it the
-// widest workgroup of which the CU still holds its share of the batch (count / cus tours, 32 waves, the LDS) at once.
+// Threads per tour (pop_threads, tl_kernels.h): a pass is (n / kOrIR) wave-sized units of work
 int or_opt_lds_threads(uint32_t n, uint32_t count, int cus, int lds_budget, bool dm)
 {
-    const uint32_t groups = (n + kOrIR - 1) / kOrIR;
-    const uint32_t per_cu = cus > 0 ? (count + (uint32_t)cus - 1u) / (uint32_t)cus : 1u;
-    const size_t fit = (size_t)lds_budget / or_opt_lds_bytes(n, dm);  // tours whose state one CU's LDS holds
-    uint32_t share = per_cu < fit ? per_cu : (uint32_t)fit;
-    if (share < 1u) share = 1u;
-    int nt = 1024;
-    while (nt > 64 && ((uint32_t)nt / 64u > groups || (uint32_t)nt * share > 2048u)) nt >>= 1;
-    return nt;
+    return pop_threads((n + kOrIR - 1) / kOrIR, or_opt_lds_bytes(n, dm), count, cus, lds_budget);
 }
 
-hipError_t launch_or_opt_lds(const OrOptLdsArgs &A, uint32_t count, int threads, hipStream_t s)
+hipError_t launch_or_opt_lds(const PopArgs &A, uint32_t count, int threads, hipStream_t s)
 {
-    const bool dm = A.dm != nullptr;
-    const void *kern = dm ? reinterpret_cast<const void *>(k_or_lds<true>) : reinterpret_cast<const void *>(k_or_lds<false>);
-    hipError_t e = allow_max_lds(kern);
-    if (e != hipSuccess) return e;
-    const size_t lds = or_opt_lds_bytes(A.n, dm);
-    if (dm) hipLaunchKernelGGL(k_or_lds<true>, dim3(count), dim3(threads), lds, s, A);
-    else hipLaunchKernelGGL(k_or_lds<false>, dim3(count), dim3(threads), lds, s, A);
-    return hipGetLastError();
+    return launch_pop(k_or_lds<true>, k_or_lds<false>, A, count, threads, or_opt_lds_bytes(A.n, A.dm != nullptr), s);
 }
 
 }  // namespace tl

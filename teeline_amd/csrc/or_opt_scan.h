@@ -26,6 +26,38 @@ __device__ __forceinline__ key_t wave_min_key(key_t v)
     return make_key(__shfl((unsigned long long)(v >> 64), 0), __shfl((unsigned long long)v, 0));
 }
 
+// every wave's minimum into its slot (two words per wave), a barrier, then the minimum of the nwaves slots — in every thread, so the
+// whole workgroup goes the same way on it.  The caller's next write to the slots lies behind a barrier of its own.
+__device__ __forceinline__ key_t block_min_key(key_t best, unsigned long long *slots, int lane, uint32_t wave, uint32_t nwaves)
+{
+    best = wave_min_key(best);
+    if (lane == 0) {
+        slots[2u * wave] = (unsigned long long)(best >> 64);
+        slots[2u * wave + 1u] = (unsigned long long)best;
+    }
+    TL_SYNC();
+    best = make_key(slots[0], slots[1]);
+    for (uint32_t w = 1; w < nwaves; ++w) {
+        const key_t o = make_key(slots[2u * w], slots[2u * w + 1u]);
+        best = o < best ? o : best;
+    }
+    return best;
+}
+
+// The distance between two tour positions: tour-ordered coordinates Pt, or the packed matrix dm through the tour perm.  Pt and
+// perm in HBM (or_opt.hip) or in LDS (or_opt_lds.hip).
+template <bool DM>
+struct Dist {
+    const float2 *Pt;
+    const float *dm;
+    const uint32_t *perm;
+    __device__ __forceinline__ float operator()(uint32_t kp, uint32_t kq) const  // tour positions
+    {
+        if (DM) return dm_lookup(dm, perm[kp], perm[kq]);
+        return dist(Pt[kp], Pt[kq]);
+    }
+};
+
 // One wave (all 64 lanes, converged) = kOrIR consecutive segment starts i0..i0+kOrIR-1 (i0 < n) x the insertion points of `chunks`
 // chunks of 63 from jlo on.  D(kp, kq): the distance between two tour positions; E[k]: the tour edge (k, k+1).
 // Every placement of the five kinds (len 1 fwd; len 2, 3 fwd and reversed) of a pair (i, j) is a sum of the row constant,

@@ -19,7 +19,7 @@
 //                         strict `>` in loop order) and applies the move (apply_3opt) in place.
 // Roofline: VALU (one correctly rounded sqrt + 7 three-term sums per triple); algorithmic bytes in matrix form
 // would be 48 B/triple — served here from LDS rows.
-#include "tl_kernels.h"
+#include "three_opt_scan.h"
 
 #pragma clang fp contract(off)
 
@@ -28,11 +28,6 @@ namespace tl {
 namespace {
 
 constexpr int kT3 = 256;  // threads per scan workgroup
-
-__device__ __forceinline__ bool better(float sa, uint32_t ija, uint32_t kca, float sb, uint32_t ijb, uint32_t kcb)
-{
-    return sa > sb || (sa == sb && (ija < ijb || (ija == ijb && kca < kcb)));
-}
 
 template <bool DM>
 __device__ __forceinline__ float Dpos(const float2 *__restrict__ Pt, const float *__restrict__ dm,
@@ -78,8 +73,6 @@ __global__ __launch_bounds__(kT3) void k_three_opt_scan(ThreeOptArgs A)
     __shared__ float r_s[kT3 / 64];
     __shared__ uint32_t r_ij[kT3 / 64], r_kc[kT3 / 64];
     const uint32_t tid = threadIdx.x;
-    const float *__restrict__ Dt = A.Dt;
-    const float *__restrict__ E = A.E;
     const size_t rs = (size_t)n + 1u;  // row stride of Dt; column n == column 0 (F = path[(k+1) % n], :85)
 
     // block -> (i, chunk): prefix[i] = number of chunks of rows < i
@@ -98,77 +91,13 @@ __global__ __launch_bounds__(kT3) void k_three_opt_scan(ThreeOptArgs A)
     const uint32_t jlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(i + 1u + (blockIdx.x - A.chunk_prefix[i]) * A.jc));
     uint32_t jhi = jlo + A.jc;
     if (jhi > n - 1u) jhi = n - 1u;  // j in [i+1, n-1)
-    const float *__restrict__ Ra = Dt + i * rs, *__restrict__ Rb = Ra + rs;  // rows of a = path[i], b = path[i+1]
-    const float d_ab = E[i];
 
     float bs = 0.0f;  // three_opt.rs:61 best_savings = 0.0
     uint32_t bij = 0xFFFFFFFFu, bkc = 0xFFFFFFFFu;
-    // (three_opt_pop.hip carries a copy of this loop for its per-workgroup descent: the two change together.)
-    // A lane owns a column k and walks the chunk's j in registers: everything that depends on (i, k) only is loaded
-    // once, the row of C = path[j] rolls into the row of the next j (D = path[j+1] is the next j's C), so a triple
-    // costs two coalesced loads and the seven sums.  No LDS, no barrier.
-    for (uint32_t k = jlo + 1u + tid; k < n; k += kT3) {
-        if (i == 0u && k == n - 1u) continue;  // :81-83
-        const float d_ef = E[k], d_ae = Ra[k], d_be = Rb[k], d_bf = Rb[k + 1u];
-        const float *__restrict__ Rc = Dt + jlo * rs;
-        float d_ce = Rc[k], d_cf = Rc[k + 1u];
-        // software pipeline: the row of D = path[j+1] and the j terms of the NEXT iteration are in flight during this one
-        float n_de = Rc[rs + k], n_dtf = Rc[rs + k + 1u];
-        float n_c_dt = E[jlo], n_ac = Ra[jlo], n_a_dt = Ra[jlo + 1u], n_b_dt = Rb[jlo + 1u];
-        for (uint32_t j = jlo; j < jhi; ++j) {  // wave-uniform trip count (scalar loads for the j terms); j >= k is masked below
-            const float d_de = n_de, d_dt_f = n_dtf;
-            const float d_c_dt = n_c_dt, d_ac = n_ac, d_a_dt = n_a_dt, d_b_dt = n_b_dt;
-            {   // rows up to jhi+1 <= n exist (row n-1 is the last; jhi <= n-1, so j+2 <= n needs a clamp at the very end)
-                const uint32_t jn = j + 1u < jhi ? j + 1u : j;  // last iteration: reload the same (unused) values
-                const float *__restrict__ Rn = Dt + (jn + 1u) * rs;
-                n_de = Rn[k];
-                n_dtf = Rn[k + 1u];
-                n_c_dt = E[jn];
-                n_ac = Ra[jn];
-                n_a_dt = Ra[jn + 1u];
-                n_b_dt = Rb[jn + 1u];
-            }
-            const float orig = (d_ab + d_c_dt) + d_ef;
-            const float c0 = (d_ac + d_b_dt) + d_ef;   // case 1
-            const float c1 = (d_ab + d_ce) + d_dt_f;   // case 2
-            const float c2 = (d_ac + d_be) + d_dt_f;   // case 3
-            const float c3 = (d_a_dt + d_be) + d_cf;   // case 4
-            const float c4 = (d_a_dt + d_ce) + d_bf;   // case 5
-            const float c5 = (d_ae + d_b_dt) + d_cf;   // case 6
-            const float c6 = (d_ae + d_c_dt) + d_bf;   // case 7
-            // :113-117 leaves cmin = min(orig, c0..c6) (NaN costs never pass `c < cmin`; fminf drops them the same way),
-            // and a triple matters only if it beats this thread's best so far — rare, so the case index is worked out
-            // under a wave-uniform branch
-            const float cm = fminf(fminf(fminf(orig, c0), fminf(c1, c2)), fminf(fminf(c3, c4), fminf(c5, c6)));
-            const float sav = orig - cm;  // :120
-            if (__builtin_amdgcn_ballot_w64((sav >= bs) & (sav > 0.0f) & (j < k))) {
-                float cmin = orig;
-                int ci = -1;
-                if (c0 < cmin) { cmin = c0; ci = 0; }
-                if (c1 < cmin) { cmin = c1; ci = 1; }
-                if (c2 < cmin) { cmin = c2; ci = 2; }
-                if (c3 < cmin) { cmin = c3; ci = 3; }
-                if (c4 < cmin) { cmin = c4; ci = 4; }
-                if (c5 < cmin) { cmin = c5; ci = 5; }
-                if (c6 < cmin) { cmin = c6; ci = 6; }
-                // :119-125 strict `>` in (i, j, k) loop order; this thread meets its triples k-major, so order by key
-                if (ci >= 0 && j < k && better(orig - cmin, (i << 16) | j, (k << 3) | (uint32_t)(ci + 1), bs, bij, bkc)) {
-                    bs = orig - cmin;
-                    bij = (i << 16) | j;
-                    bkc = (k << 3) | (uint32_t)(ci + 1);
-                }
-            }
-            d_ce = d_de;
-            d_cf = d_dt_f;
-        }
-    }
+    three_opt_scan_lane(A.Dt, rs, A.E, n, i, jlo, jhi, jlo + 1u + tid, kT3, bs, bij, bkc);  // lanes along k (three_opt_scan.h)
 
     // workgroup reduction: wave (shuffles) then LDS
-    for (int off = 32; off > 0; off >>= 1) {
-        const float os = __shfl_down(bs, off);
-        const uint32_t oij = __shfl_down(bij, off), okc = __shfl_down(bkc, off);
-        if (better(os, oij, okc, bs, bij, bkc)) { bs = os; bij = oij; bkc = okc; }
-    }
+    wave_best(bs, bij, bkc);
     if ((tid & 63u) == 0u) { r_s[tid >> 6] = bs; r_ij[tid >> 6] = bij; r_kc[tid >> 6] = bkc; }
     TL_SYNC();
     if (tid == 0) {
@@ -197,11 +126,7 @@ __global__ __launch_bounds__(1024) void k_three_opt_pick(ThreeOptArgs A, uint32_
         const ThreeOptBest p = A.partials[b];
         if (better(p.sav, p.ij, p.kc, bs, bij, bkc)) { bs = p.sav; bij = p.ij; bkc = p.kc; }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        const float os = __shfl_down(bs, off);
-        const uint32_t oij = __shfl_down(bij, off), okc = __shfl_down(bkc, off);
-        if (better(os, oij, okc, bs, bij, bkc)) { bs = os; bij = oij; bkc = okc; }
-    }
+    wave_best(bs, bij, bkc);
     if ((tid & 63u) == 0u) { r_s[tid >> 6] = bs; r_ij[tid >> 6] = bij; r_kc[tid >> 6] = bkc; }
     TL_SYNC();
     bs = r_s[0]; bij = r_ij[0]; bkc = r_kc[0];
@@ -217,21 +142,7 @@ __global__ __launch_bounds__(1024) void k_three_opt_pick(ThreeOptArgs A, uint32_
             A.counters[0] += 1;                  // passes
             if (found) A.counters[1] += 1;       // moves
         }
-        if (A.run) {  // three_opt.rs:36-45: count the pass, file the move or end the descent
-            A.run->passes += 1u;
-            if (!found) {
-                A.run->done = 1u;
-            } else {
-                const uint32_t m = A.run->moves;
-                if (m < A.run->log_cap) {
-                    A.log[4u * m + 0u] = bij >> 16;
-                    A.log[4u * m + 1u] = bij & 0xFFFFu;
-                    A.log[4u * m + 2u] = bkc >> 3;
-                    A.log[4u * m + 3u] = bkc & 7u;
-                }
-                A.run->moves = m + 1u;
-            }
-        }
+        scan_file_pass(A.run, A.log, found, bij >> 16, bij & 0xFFFFu, bkc >> 3, bkc & 7u);  // three_opt.rs:36-45
     }
     if (!found || !apply) return;
     const uint32_t i = bij >> 16, j = bij & 0xFFFFu, k = bkc >> 3, kase = bkc & 7u;
@@ -239,19 +150,7 @@ __global__ __launch_bounds__(1024) void k_three_opt_pick(ThreeOptArgs A, uint32_
     const uint32_t l1 = j - i, l2 = k - j, L = l1 + l2;  // seg1 = path[i+1..=j], seg2 = path[j+1..=k]
     for (uint32_t t = tid; t < L; t += 1024u) tmp[t] = path[i + 1u + t];
     TL_SYNC();
-    for (uint32_t t = tid; t < L; t += 1024u) {
-        uint32_t src;  // index into tmp (0..l1-1 = seg1, l1.. = seg2)
-        switch (kase) {
-        case 1: src = t < l1 ? (l1 - 1u - t) : t; break;                                  // rev(s1) + s2
-        case 2: src = t < l1 ? t : (l1 + (L - 1u - t)); break;                            // s1 + rev(s2)
-        case 3: src = t < l1 ? (l1 - 1u - t) : (l1 + (L - 1u - t)); break;                // rev(s1) + rev(s2)
-        case 4: src = t < l2 ? (l1 + t) : (t - l2); break;                                // s2 + s1
-        case 5: src = t < l2 ? (l1 + t) : (l1 - 1u - (t - l2)); break;                    // s2 + rev(s1)
-        case 6: src = t < l2 ? (l1 + (l2 - 1u - t)) : (t - l2); break;                    // rev(s2) + s1
-        default: src = t < l2 ? (l1 + (l2 - 1u - t)) : (l1 - 1u - (t - l2)); break;       // 7: rev(s2) + rev(s1)
-        }
-        path[i + 1u + t] = tmp[src];
-    }
+    for (uint32_t t = tid; t < L; t += 1024u) path[i + 1u + t] = tmp[three_opt_src(kase, t, l1, l2)];
 }
 
 size_t three_opt_scan_lds_bytes(uint32_t) { return 0; }  // the scan keeps its rows in registers

@@ -75,6 +75,113 @@ static int scan_descent(tl_ctx *c, const char *who, const float *xy, uint32_t n,
     return TL_OK;
 }
 
+// The descent of every tour of a population, which tl_or_opt_population and tl_three_opt_population share; tour r's result is the
+// single-tour entry's for it alone.  who: "or_opt" / "three_opt", the name in the messages.  run1(init, out, &cost, &stats): the
+// chip-wide descent of one tour (or_opt_run / three_opt_run).  plan(P) fills a PopPlan: resident — one workgroup per tour (`threads`
+// wide), batch after batch of `batch` tours, each with tour_work bytes of c->work (0: none, and the batch is the whole population) —
+// or else the tours one after the other through run1.  launch(A, cnt, threads) enqueues a batch's kernel.  per_pass: the candidates
+// a pass evaluates; max_passes: a resident descent still moving after that many passes is TL_ERR_NO_CONVERGE.
+struct PopPlan {
+    bool resident;
+    int threads;
+    uint32_t batch;
+    size_t tour_work;
+};
+template <class Run, class Plan, class Launch>
+static int population_descent(tl_ctx *c, const char *who, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t count,
+                              uint32_t *out_pos, float *out_costs, uint32_t *out_moves, tl_stats *stats, uint64_t per_pass, uint32_t max_passes, Run run1,
+                              Plan plan, Launch launch)
+{
+    if (!c || (!xy && !dm_packed)) return fail(c, TL_ERR_BADARG, "tl_%s_population: NULL argument", who);
+    if (count == 0) return TL_OK;
+    if (!out_pos || (n >= 4 && !init_pos)) return fail(c, TL_ERR_BADARG, "tl_%s_population: NULL argument", who);
+    if (n >= 4)
+        for (uint32_t r = 0; r < count; ++r)
+            if (!is_permutation(init_pos + (size_t)r * n, n))
+                return fail(c, TL_ERR_BADARG, "tl_%s_population: tour %u is not a permutation of 0..n-1", who, r);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    int rc;
+    if (n < 4) {  // three_opt.rs:25-28, or_opt.rs:31-34: the cities' order, init_tour ignored
+        float cst = 0.0f;
+        for (uint32_t k = 0; k < n; ++k) out_pos[k] = k;
+        if (out_costs && n >= 2 && (rc = tl_tour_length(c, xy, dm_packed, n, out_pos, &cst))) return rc;
+        for (uint32_t r = 0; r < count; ++r) {
+            for (uint32_t k = 0; k < n; ++k) out_pos[(size_t)r * n + k] = k;
+            if (out_costs) out_costs[r] = cst;
+            if (out_moves) out_moves[r] = 0u;
+        }
+        return TL_OK;
+    }
+    PopPlan P{};
+    if ((rc = plan(P))) return rc;
+    if (!P.resident) {
+        tl_stats acc{};
+        for (uint32_t r = 0; r < count; ++r) {
+            float cst = 0.0f;
+            tl_stats st1{};
+            if ((rc = run1(init_pos + (size_t)r * n, out_pos + (size_t)r * n, &cst, &st1))) return rc;
+            if (out_costs) out_costs[r] = cst;
+            if (out_moves) out_moves[r] = (uint32_t)st1.moves;
+            acc.sweeps += st1.sweeps;
+            acc.moves += st1.moves;
+            acc.candidates += st1.candidates;
+            acc.kernel_ms += st1.kernel_ms;
+        }
+        if (stats) {
+            *stats = acc;
+            stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return TL_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t words = (size_t)count * n;
+    if ((rc = ensure(c, c->init, words * 4)) || (rc = ensure(c, c->out_pos, words * 4)) || (rc = ensure(c, c->out_cost, (size_t)count * 4)) ||
+        (rc = ensure(c, c->misc, (size_t)count * 16)) || (P.tour_work && (rc = ensure(c, c->work, (size_t)P.batch * P.tour_work))))
+        return rc;
+    PopArgs A{};
+    if ((rc = upload_input(c, xy, dm_packed, n, &A.xy, &A.dm))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->init.p, init_pos, words * 4, hipMemcpyHostToDevice, c->stream));
+    A.Dt = P.tour_work ? (float *)c->work.p : nullptr;
+    A.n = n;
+    A.max_passes = max_passes;
+    c->ev_valid = false;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    for (uint32_t first = 0; first < count; first += P.batch) {  // a batch's workgroups own the workspace; the stream orders the batches
+        const uint32_t cnt = count - first < P.batch ? count - first : P.batch;
+        A.init = (const uint32_t *)c->init.p + (size_t)first * n;
+        A.out_pos = (uint32_t *)c->out_pos.p + (size_t)first * n;
+        A.out_cost = (float *)c->out_cost.p + first;
+        A.out_run = (uint32_t *)c->misc.p + 4u * (size_t)first;
+        HIPCHK(c, launch(A, cnt, P.threads));
+    }
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    c->ev_valid = true;
+    std::vector<uint32_t> run((size_t)count * 4);
+    std::vector<float> costs(count);
+    HIPCHK(c, hipMemcpyAsync(run.data(), c->misc.p, (size_t)count * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(costs.data(), c->out_cost.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t r = 0; r < count; ++r)
+        if (run[4u * r + 2u] != 0u) return fail(c, TL_ERR_NO_CONVERGE, "%s: pass cap reached in tour %u", who, r);
+    HIPCHK(c, hipMemcpyAsync(out_pos, c->out_pos.p, words * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    uint64_t moves = 0, passes = 0;
+    for (uint32_t r = 0; r < count; ++r) {
+        if (out_costs) out_costs[r] = costs[r];
+        if (out_moves) out_moves[r] = run[4u * r];
+        moves += run[4u * r];
+        passes += run[4u * r + 1u];
+    }
+    if (stats) {
+        stats->moves = moves;
+        stats->sweeps = passes;
+        stats->candidates = passes * per_pass;
+        stamp_times(c, stats, t0);
+    }
+    return TL_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // 3-opt
 // ------------------------------------------------------------------------------------------------
@@ -153,15 +260,19 @@ extern "C" int tl_three_opt_find_best_move(tl_ctx *c, const float *xy, uint32_t 
     return TL_OK;
 }
 
+static uint64_t three_opt_per_pass(uint32_t n)
+{
+    const uint64_t nn = n;
+    return nn * (nn - 1) * (nn - 2) / 6 - (nn - 2);  // C(n,3) - (n-2) triples per pass
+}
+
 // the log's 4 words per move: i, j, k, case of three_opt.rs:36-45
 static int three_opt_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos,
                          uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *move_log, uint32_t log_cap, uint32_t *log_len)
 {
-    const uint64_t nn = n;
     uint32_t nblocks = 0;
     return scan_descent<ThreeOptArgs>(
-        c, "three_opt", xy, n, dm_packed, init_pos, out_pos, out_cost, stats, move_log, log_cap, log_len,
-        nn * (nn - 1) * (nn - 2) / 6 - (nn - 2),  // C(n,3) - (n-2) triples per pass
+        c, "three_opt", xy, n, dm_packed, init_pos, out_pos, out_cost, stats, move_log, log_cap, log_len, three_opt_per_pass(n),
         [&](ThreeOptArgs &A) { return three_opt_setup(c, xy, n, dm_packed, init_pos, A, &nblocks); },
         [&](const ThreeOptArgs &A) { return launch_three_opt_pass(A, nblocks, A.dm != nullptr, 1, c->stream, c->lds_bytes); });
 }
@@ -286,88 +397,19 @@ extern "C" int tl_or_opt_population(tl_ctx *c, const float *xy, uint32_t n, cons
                                     uint32_t *out_pos, float *out_costs, uint32_t *out_moves, tl_stats *stats)
 {
     TL_ENTER(c);
-    if (!c || (!xy && !dm_packed)) return fail(c, TL_ERR_BADARG, "tl_or_opt_population: NULL argument");
-    if (count == 0) return TL_OK;
-    if (!out_pos || (n >= 4 && !init_pos)) return fail(c, TL_ERR_BADARG, "tl_or_opt_population: NULL argument");
-    if (n >= 4)
-        for (uint32_t r = 0; r < count; ++r)
-            if (!is_permutation(init_pos + (size_t)r * n, n))
-                return fail(c, TL_ERR_BADARG, "tl_or_opt_population: tour %u is not a permutation of 0..n-1", r);
-    const auto t0 = std::chrono::steady_clock::now();
-    if (stats) memset(stats, 0, sizeof(*stats));
-    int rc;
-    if (n < 4) {  // or_opt.rs:31-34: the cities' order, init_tour ignored
-        float cst = 0.0f;
-        for (uint32_t k = 0; k < n; ++k) out_pos[k] = k;
-        if (out_costs && n >= 2 && (rc = tl_tour_length(c, xy, dm_packed, n, out_pos, &cst))) return rc;
-        for (uint32_t r = 0; r < count; ++r) {
-            for (uint32_t k = 0; k < n; ++k) out_pos[(size_t)r * n + k] = k;
-            if (out_costs) out_costs[r] = cst;
-            if (out_moves) out_moves[r] = 0u;
-        }
-        return TL_OK;
-    }
-    if ((c->flags & TL_FLAG_OR_OPT_FORCE_SCAN) || n > or_opt_lds_max_n(c->lds_bytes, dm_packed != nullptr)) {
-        tl_stats acc{};
-        for (uint32_t r = 0; r < count; ++r) {
-            float cst = 0.0f;
-            tl_stats st1{};
-            if ((rc = or_opt_run(c, xy, n, dm_packed, init_pos + (size_t)r * n, out_pos + (size_t)r * n, &cst, &st1, nullptr, 0, nullptr))) return rc;
-            if (out_costs) out_costs[r] = cst;
-            if (out_moves) out_moves[r] = (uint32_t)st1.moves;
-            acc.sweeps += st1.sweeps;
-            acc.moves += st1.moves;
-            acc.candidates += st1.candidates;
-            acc.kernel_ms += st1.kernel_ms;
-        }
-        if (stats) {
-            *stats = acc;
-            stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        }
-        return TL_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t words = (size_t)count * n;
-    if ((rc = ensure(c, c->init, words * 4)) || (rc = ensure(c, c->out_pos, words * 4)) || (rc = ensure(c, c->out_cost, (size_t)count * 4)) ||
-        (rc = ensure(c, c->misc, (size_t)count * 16)))
-        return rc;
-    OrOptLdsArgs A{};
-    if ((rc = upload_input(c, xy, dm_packed, n, &A.xy, &A.dm))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->init.p, init_pos, words * 4, hipMemcpyHostToDevice, c->stream));
-    A.init = (const uint32_t *)c->init.p;
-    A.out_pos = (uint32_t *)c->out_pos.p;
-    A.out_cost = (float *)c->out_cost.p;
-    A.out_run = (uint32_t *)c->misc.p;
-    A.n = n;
-    A.max_passes = 64u * n + 1024u;  // scan_descent's cap
-    c->ev_valid = false;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    HIPCHK(c, launch_or_opt_lds(A, count, or_opt_lds_threads(n, count, c->cus, c->lds_bytes, A.dm != nullptr), c->stream));
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    c->ev_valid = true;
-    std::vector<uint32_t> run((size_t)count * 4);
-    std::vector<float> costs(count);
-    HIPCHK(c, hipMemcpyAsync(run.data(), A.out_run, (size_t)count * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(costs.data(), A.out_cost, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (uint32_t r = 0; r < count; ++r)
-        if (run[4u * r + 2u] != 0u) return fail(c, TL_ERR_NO_CONVERGE, "or_opt: pass cap reached in tour %u", r);
-    HIPCHK(c, hipMemcpyAsync(out_pos, A.out_pos, words * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    uint64_t moves = 0, passes = 0;
-    for (uint32_t r = 0; r < count; ++r) {
-        if (out_costs) out_costs[r] = costs[r];
-        if (out_moves) out_moves[r] = run[4u * r];
-        moves += run[4u * r];
-        passes += run[4u * r + 1u];
-    }
-    if (stats) {
-        stats->moves = moves;
-        stats->sweeps = passes;
-        stats->candidates = passes * or_opt_per_pass(n);
-        stamp_times(c, stats, t0);
-    }
-    return TL_OK;
+    const bool dm = dm_packed != nullptr;
+    return population_descent(
+        c, "or_opt", xy, n, dm_packed, init_pos, count, out_pos, out_costs, out_moves, stats, or_opt_per_pass(n),
+        64u * n + 1024u,  // scan_descent's cap as a count of passes.  (tl_three_opt_population rounds it up to scan_descent's next look,
+                          // so the two differ; making them alike would change when a descent fails, and is left alone)
+        [&](const uint32_t *init, uint32_t *out, float *cost, tl_stats *st) { return or_opt_run(c, xy, n, dm_packed, init, out, cost, st, nullptr, 0, nullptr); },
+        [&](PopPlan &P) -> int {
+            P.resident = !(c->flags & TL_FLAG_OR_OPT_FORCE_SCAN) && n <= or_opt_lds_max_n(c->lds_bytes, dm);
+            if (P.resident) P.threads = or_opt_lds_threads(n, count, c->cus, c->lds_bytes, dm);
+            P.batch = count;
+            return TL_OK;
+        },
+        [&](const PopArgs &A, uint32_t cnt, int threads) { return launch_or_opt_lds(A, cnt, threads, c->stream); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -388,12 +430,6 @@ static constexpr double kPopRcu = 2.0e9;     // triples / s on one CU (form 1)
 static constexpr double kPopRchip = 6.9e11;  // triples / s of the chip-wide scan (form 0)
 static constexpr double kPopTpass = 23e-6;   // s of overhead per chip-wide pass (form 0)
 static constexpr uint64_t kPopWorkDefault = 8ull << 30;  // the precedent of the matrix-form lists
-
-static uint64_t three_opt_per_pass(uint32_t n)
-{
-    const uint64_t nn = n;
-    return nn * (nn - 1) * (nn - 2) / 6 - (nn - 2);  // C(n,3) - (n-2) triples per pass
-}
 
 extern "C" uint32_t tl_three_opt_pop_max_n(const tl_ctx *c) { return c ? three_opt_pop_max_n(c->lds_bytes) : 0u; }
 
@@ -435,97 +471,21 @@ extern "C" int tl_three_opt_population(tl_ctx *c, const float *xy, uint32_t n, c
                                        uint32_t *out_pos, float *out_costs, uint32_t *out_moves, tl_stats *stats)
 {
     TL_ENTER(c);
-    if (!c || (!xy && !dm_packed)) return fail(c, TL_ERR_BADARG, "tl_three_opt_population: NULL argument");
-    if (count == 0) return TL_OK;
-    if (!out_pos || (n >= 4 && !init_pos)) return fail(c, TL_ERR_BADARG, "tl_three_opt_population: NULL argument");
-    if (n >= 4)
-        for (uint32_t r = 0; r < count; ++r)
-            if (!is_permutation(init_pos + (size_t)r * n, n))
-                return fail(c, TL_ERR_BADARG, "tl_three_opt_population: tour %u is not a permutation of 0..n-1", r);
-    const auto t0 = std::chrono::steady_clock::now();
-    if (stats) memset(stats, 0, sizeof(*stats));
-    int rc;
-    if (n < 4) {  // three_opt.rs:25-28: the cities' order, init_tour ignored
-        float cst = 0.0f;
-        for (uint32_t k = 0; k < n; ++k) out_pos[k] = k;
-        if (out_costs && n >= 2 && (rc = tl_tour_length(c, xy, dm_packed, n, out_pos, &cst))) return rc;
-        for (uint32_t r = 0; r < count; ++r) {
-            for (uint32_t k = 0; k < n; ++k) out_pos[(size_t)r * n + k] = k;
-            if (out_costs) out_costs[r] = cst;
-            if (out_moves) out_moves[r] = 0u;
-        }
-        return TL_OK;
-    }
-    int form = 0, threads = 0;
-    uint32_t batch = 0;
-    if ((rc = tl_three_opt_population_plan(n, count, c->cus, c->lds_bytes, c->three_opt_pop_work ? c->three_opt_pop_work : kPopWorkDefault, c->flags,
-                                           &form, &threads, &batch)))
-        return fail(c, rc, "tl_three_opt_population: no plan for this device");
-    if (form == 0) {
-        tl_stats acc{};
-        for (uint32_t r = 0; r < count; ++r) {
-            float cst = 0.0f;
-            tl_stats st1{};
-            if ((rc = three_opt_run(c, xy, n, dm_packed, init_pos + (size_t)r * n, out_pos + (size_t)r * n, &cst, &st1, nullptr, 0, nullptr))) return rc;
-            if (out_costs) out_costs[r] = cst;
-            if (out_moves) out_moves[r] = (uint32_t)st1.moves;
-            acc.sweeps += st1.sweeps;
-            acc.moves += st1.moves;
-            acc.candidates += st1.candidates;
-            acc.kernel_ms += st1.kernel_ms;
-        }
-        if (stats) {
-            *stats = acc;
-            stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        }
-        return TL_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t words = (size_t)count * n, dt_words = (size_t)n * ((size_t)n + 1u);
-    if ((rc = ensure(c, c->init, words * 4)) || (rc = ensure(c, c->out_pos, words * 4)) || (rc = ensure(c, c->out_cost, (size_t)count * 4)) ||
-        (rc = ensure(c, c->misc, (size_t)count * 16)) || (rc = ensure(c, c->work, (size_t)batch * dt_words * 4)))
-        return rc;
-    ThreeOptPopArgs A{};
-    if ((rc = upload_input(c, xy, dm_packed, n, &A.xy, &A.dm))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->init.p, init_pos, words * 4, hipMemcpyHostToDevice, c->stream));
-    A.Dt = (float *)c->work.p;
-    A.n = n;
-    // scan_descent's cap as scan_descent applies it: it looks once per kScanBatch passes and gives up when the descent is still moving at
-    // the first look beyond 64 n + 1024 passes — so a descent fails here exactly when it fails there
-    A.max_passes = (64u * n + 1024u) / (uint32_t)kScanBatch * (uint32_t)kScanBatch + (uint32_t)kScanBatch;
-    c->ev_valid = false;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    for (uint32_t first = 0; first < count; first += batch) {  // a batch's workgroups own the workspace's matrices; the stream orders the batches
-        const uint32_t cnt = count - first < batch ? count - first : batch;
-        A.init = (const uint32_t *)c->init.p + (size_t)first * n;
-        A.out_pos = (uint32_t *)c->out_pos.p + (size_t)first * n;
-        A.out_cost = (float *)c->out_cost.p + first;
-        A.out_run = (uint32_t *)c->misc.p + 4u * (size_t)first;
-        HIPCHK(c, launch_three_opt_pop(A, cnt, threads, c->stream));
-    }
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    c->ev_valid = true;
-    std::vector<uint32_t> run((size_t)count * 4);
-    std::vector<float> costs(count);
-    HIPCHK(c, hipMemcpyAsync(run.data(), c->misc.p, (size_t)count * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(costs.data(), c->out_cost.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (uint32_t r = 0; r < count; ++r)
-        if (run[4u * r + 2u] != 0u) return fail(c, TL_ERR_NO_CONVERGE, "three_opt: pass cap reached in tour %u", r);
-    HIPCHK(c, hipMemcpyAsync(out_pos, c->out_pos.p, words * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    uint64_t moves = 0, passes = 0;
-    for (uint32_t r = 0; r < count; ++r) {
-        if (out_costs) out_costs[r] = costs[r];
-        if (out_moves) out_moves[r] = run[4u * r];
-        moves += run[4u * r];
-        passes += run[4u * r + 1u];
-    }
-    if (stats) {
-        stats->moves = moves;
-        stats->sweeps = passes;
-        stats->candidates = passes * three_opt_per_pass(n);
-        stamp_times(c, stats, t0);
-    }
-    return TL_OK;
+    return population_descent(
+        c, "three_opt", xy, n, dm_packed, init_pos, count, out_pos, out_costs, out_moves, stats, three_opt_per_pass(n),
+        // scan_descent's cap as scan_descent applies it: it looks once per kScanBatch passes and gives up when the descent is still moving at
+        // the first look beyond 64 n + 1024 passes — so a descent fails here exactly when it fails there.  (tl_or_opt_population passes the
+        // plain 64 n + 1024; making the two alike would change when a descent fails, and is left alone.)
+        (64u * n + 1024u) / (uint32_t)kScanBatch * (uint32_t)kScanBatch + (uint32_t)kScanBatch,
+        [&](const uint32_t *init, uint32_t *out, float *cost, tl_stats *st) { return three_opt_run(c, xy, n, dm_packed, init, out, cost, st, nullptr, 0, nullptr); },
+        [&](PopPlan &P) -> int {
+            int form = 0;
+            const int rc = tl_three_opt_population_plan(n, count, c->cus, c->lds_bytes, c->three_opt_pop_work ? c->three_opt_pop_work : kPopWorkDefault,
+                                                        c->flags, &form, &P.threads, &P.batch);
+            if (rc) return fail(c, rc, "tl_three_opt_population: no plan for this device");
+            P.resident = form != 0;
+            P.tour_work = (size_t)n * ((size_t)n + 1u) * 4;  // a tour's Dt
+            return TL_OK;
+        },
+        [&](const PopArgs &A, uint32_t cnt, int threads) { return launch_three_opt_pop(A, cnt, threads, c->stream); });
 }

@@ -176,6 +176,25 @@ struct ScanRunState {
     uint32_t moves;    // moves applied; also the number of log entries offered
     uint32_t log_cap;  // entries (4 words each) the move log holds
 };
+// What one thread of a pick kernel does with its pass (three_opt.rs:36-45, or_opt.rs:45 `while let Some(best) = find_best_move(..)`):
+// count the pass, file the move's four words or end the descent.  run == nullptr: a single find_best_move, nothing to file.
+__device__ __forceinline__ void scan_file_pass(ScanRunState *run, uint32_t *log, bool found, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3)
+{
+    if (!run) return;
+    run->passes += 1u;
+    if (!found) {
+        run->done = 1u;
+        return;
+    }
+    const uint32_t m = run->moves;
+    if (m < run->log_cap) {
+        log[4u * m + 0u] = w0;
+        log[4u * m + 1u] = w1;
+        log[4u * m + 2u] = w2;
+        log[4u * m + 3u] = w3;
+    }
+    run->moves = m + 1u;
+}
 
 // three_opt.hip
 struct ThreeOptBest {
@@ -204,22 +223,64 @@ struct ThreeOptArgs {
 size_t three_opt_scan_lds_bytes(uint32_t n);
 hipError_t launch_three_opt_pass(const ThreeOptArgs &A, uint32_t nblocks, bool dm, int apply, hipStream_t s, int lds_budget);
 
-// three_opt_pop.hip — a population of tours, one workgroup per tour, the whole descent without a launch per move
-struct ThreeOptPopArgs {
+// A population of tours, one persistent workgroup per tour running the whole descent without a launch per move: what
+// three_opt_pop.hip and or_opt_lds.hip share
+struct PopArgs {
     const float2 *xy;      // n cities, city order (coordinate form)
     const float *dm;       // packed matrix or nullptr
     const uint32_t *init;  // [count][n] start tours of this launch (permutations: the host checks)
     uint32_t *out_pos;     // [count][n]
     float *out_cost;       // [count] tour_length of the result
     uint32_t *out_run;     // [count][4] moves, passes, status (1: pass cap reached), 0
-    float *Dt;             // [count][n][n+1] each tour's distances between tour positions (workspace)
+    float *Dt;             // 3-opt: [count][n][n+1] each tour's distances between tour positions (workspace); Or-opt: nullptr
     uint32_t n;
     uint32_t max_passes;   // a descent stops (status 1) when it has run this many passes and still finds a move
 };
+// The end of a tour's descent, by the whole workgroup: the tour out, its length from the tour edges E and the run words
+__device__ __forceinline__ void pop_finish(const PopArgs &A, const uint32_t *perm, const float *E, uint32_t moves, uint32_t passes, uint32_t status)
+{
+    const uint32_t n = A.n, tour = blockIdx.x;
+    uint32_t *out = A.out_pos + (size_t)tour * n;
+    for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) out[k] = perm[k];
+    if (threadIdx.x == 0) {
+        // tour_length (distance_matrix.rs:235-245): the closing edge first, then the n - 1 edges in order, sequential f32
+        float total = E[n - 1u];
+        for (uint32_t k = 0; k + 1u < n; ++k) total += E[k];
+        A.out_cost[tour] = total;
+        A.out_run[4u * tour + 0u] = moves;
+        A.out_run[4u * tour + 1u] = passes;
+        A.out_run[4u * tour + 2u] = status;
+        A.out_run[4u * tour + 3u] = 0u;
+    }
+}
+// Threads per tour.  A pass has `units` wave-sized units of work (the caller may stop counting at 16), so a tour cannot use more
+// waves than that; beyond it the widest workgroup of which the CU still holds its share of the batch (count / cus tours, 32 waves,
+// the LDS at tour_lds bytes a tour) at once.
+inline int pop_threads(uint64_t units, size_t tour_lds, uint32_t count, int cus, int lds_budget)
+{
+    const uint32_t per_cu = cus > 0 ? (count + (uint32_t)cus - 1u) / (uint32_t)cus : 1u;
+    const size_t fit = (size_t)(lds_budget > 0 ? lds_budget : 0) / tour_lds;  // tours whose state one CU's LDS holds
+    uint32_t share = per_cu < fit ? per_cu : (uint32_t)fit;
+    if (share < 1u) share = 1u;
+    int nt = 1024;
+    while (nt > 64 && ((uint64_t)nt / 64u > units || (uint32_t)nt * share > 2048u)) nt >>= 1;
+    return nt;
+}
+// one workgroup of `threads` per tour with tour_lds bytes of LDS; k_dm / k_xy: the kernel's matrix and coordinate forms
+inline hipError_t launch_pop(void (*k_dm)(PopArgs), void (*k_xy)(PopArgs), const PopArgs &A, uint32_t count, int threads, size_t tour_lds, hipStream_t s)
+{
+    void (*const kern)(PopArgs) = A.dm ? k_dm : k_xy;
+    hipError_t e = allow_max_lds(reinterpret_cast<const void *>(kern));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(count), dim3(threads), tour_lds, s, A);
+    return hipGetLastError();
+}
+
+// three_opt_pop.hip
 size_t three_opt_pop_lds_bytes(uint32_t n);          // LDS of one tour's workgroup (either form)
 uint32_t three_opt_pop_max_n(int lds_budget);        // largest n whose state fits
 int three_opt_pop_threads(uint32_t n, uint32_t count, int cus, int lds_budget);
-hipError_t launch_three_opt_pop(const ThreeOptPopArgs &A, uint32_t count, int threads, hipStream_t s);
+hipError_t launch_three_opt_pop(const PopArgs &A, uint32_t count, int threads, hipStream_t s);
 
 // or_opt.hip
 struct OrOptBest {
@@ -241,21 +302,11 @@ struct OrOptArgs {
 hipError_t launch_or_opt_pass(const OrOptArgs &A, bool dm, int apply, hipStream_t s, int lds_budget);
 uint32_t or_opt_scan_blocks(uint32_t n);
 
-// or_opt_lds.hip — a population of tours, one workgroup per tour, the whole descent in LDS
-struct OrOptLdsArgs {
-    const float2 *xy;      // n cities, city order (coordinate form)
-    const float *dm;       // packed matrix or nullptr
-    const uint32_t *init;  // [count][n] start tours (permutations: the host checks)
-    uint32_t *out_pos;     // [count][n]
-    float *out_cost;       // [count] tour_length of the result
-    uint32_t *out_run;     // [count][4] moves, passes, status (1: pass cap reached), 0
-    uint32_t n;
-    uint32_t max_passes;   // a descent stops (status 1) when it has run this many passes and still finds a move
-};
+// or_opt_lds.hip — a population of tours (PopArgs, Dt unused), the whole descent in LDS
 size_t or_opt_lds_bytes(uint32_t n, bool dm);             // LDS of one tour's workgroup
 uint32_t or_opt_lds_max_n(int lds_budget, bool dm);       // largest n whose state fits
 int or_opt_lds_threads(uint32_t n, uint32_t count, int cus, int lds_budget, bool dm);
-hipError_t launch_or_opt_lds(const OrOptLdsArgs &A, uint32_t count, int threads, hipStream_t s);
+hipError_t launch_or_opt_lds(const PopArgs &A, uint32_t count, int threads, hipStream_t s);
 
 // lk.hip
 struct LkState {             // device-side state machine of the multi-CU LK variant
