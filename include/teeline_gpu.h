@@ -44,7 +44,8 @@ extern "C" {
 
 #define TL_ABI_VERSION 5 /* bumped when an existing entry point, struct or code changes meaning; additions (round 5: tl_multistart_shard,
                             tl_two_opt_last_counters, new tl_create flags, k <= 64; later: tl_or_opt_population, tl_or_opt_lds_max_n,
-                            TL_FLAG_OR_OPT_FORCE_SCAN, tl_three_opt_population and its three companions, TL_FLAG_3OPT_POP_*) leave it — a caller built against 5 runs unchanged */
+                            TL_FLAG_OR_OPT_FORCE_SCAN, tl_three_opt_population and its three companions, TL_FLAG_3OPT_POP_*, tl_sim_anneal and its companions,
+                            TL_FLAG_SA_NO_SPECULATION) leave it — a caller built against 5 runs unchanged */
 
 typedef struct tl_ctx tl_ctx;
 
@@ -118,6 +119,8 @@ typedef enum tl_mode {
 #define TL_FLAG_3OPT_POP_FORCE_WG (1u << 28) /* tl_three_opt_population: one workgroup per tour wherever a tour fits the LDS and its Dt the workspace limit */
 #define TL_FLAG_LK_NO_SPECULATION (1u << 22) /* tl_lk, LDS form: the epochs one after the other in one workgroup (default: one workgroup per epoch,
                                               as many consecutive epochs at once as the chip holds, taken in order up to the first accepted one) */
+#define TL_FLAG_SA_NO_SPECULATION (1u << 29) /* tl_sim_anneal*: the same kernel with a window of one epoch — the chain epoch after epoch (default: a window of
+                                              consecutive epochs evaluated at once against the same tour, the first accepted one committed) */
 /* TUNING BUILDS ONLY (libteeline_gpu_tune.so, -DTL_TUNE: `python -m teeline_amd.build --tune`).  Forms that were measured and
  * rejected and stay as cross-checks for development; the product library does not carry them and tl_create
  * returns TL_ERR_UNSUPPORTED if one of these bits is set. */
@@ -486,6 +489,69 @@ int tl_three_opt_population_plan(uint32_t n, uint32_t count, int cus, int lds_by
 int tl_three_opt_population_work_limit(tl_ctx *ctx, uint64_t bytes);
 int tl_three_opt_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t count,
                             uint32_t *out_pos, float *out_costs, uint32_t *out_moves, tl_stats *stats);
+
+/* ---- simulated annealing: replaces simulated_annealing::solve (simulated_annealing.rs:10-83) ---------- */
+/* The reference's chain with its quirks kept: "best_route" is the current state and the LAST state is returned; the schedule is
+ * `while epoch < epochs || temperature > min_temperature`, T <- T - cooling_rate * T (f32, two roundings: 138 149 epochs with the
+ * defaults); an epoch reverses positions from..=to of the open path (route.rs:48-113; after 10 redraws the last pair is used even
+ * when equal or adjacent), costs the whole candidate with tour_length (closing edge first, sequential f32) and accepts it when it
+ * is shorter, never when |new - old| < FLT_EPSILON, else when p < exp(-(new - old) / T).
+ * TWO THINGS ARE THIS PROJECT'S SPECIFICATION, NOT THE REFERENCE'S (tests/_sa_oracle.py is the statement):
+ *   draws   the reference's unseeded thread RNG cannot be reproduced.  Here u(seed, chain, epoch, slot) =
+ *           mix(mix(seed + G (chain + 1)) + G (32 epoch + slot + 1)), mix = splitmix64's output function, G = 0x9E3779B97F4A7C15
+ *           (tl_sa_draw); pair attempt a uses slots 2a, 2a + 1, a position is ((u >> 32) n) >> 32, p = float(u >> 40) 2^-24 from
+ *           slot 22.  A draw never depends on an earlier one;
+ *   exp     a fixed f64 operation sequence without FMA instead of the platform's exp: 0 for x < -87, else k = rint(x log2 e),
+ *           r = (x - k ln2_hi) - k ln2_lo, the Horner sum of r^i / i! up to i = 13, (float) ldexp(q, k).
+ * One workgroup per chain with the chain in that CU's LDS (12 bytes per city; csrc/sim_anneal.hip), a window of consecutive
+ * epochs evaluated at once; with TL_FLAG_SA_NO_SPECULATION the window is one epoch.  Same tours, costs and accepted epochs.
+ * opts NULL: the defaults (10 000 / 1e-4 / 1e-3 / 1000; mod.rs:598-608, 697-705).  Options that SAOptions::validate (mod.rs:707-741)
+ * refuses are TL_ERR_BADARG — except where the schedule is empty (epochs = 0 and not max_temperature > min_temperature): solve itself
+ * never validates, and the reference's own test runs epochs 0, max 0, min 1e6 and gets its start tour back; so does this.  A schedule
+ * of more than 2^32 - 1 epochs (or one that never ends: T stops falling above min_temperature): TL_ERR_UNSUPPORTED.  n < 2 with a
+ * non-empty schedule: TL_ERR_REF_PANICS (route.rs:87-89).  n > tl_sim_anneal_lds_max_n: TL_ERR_UNSUPPORTED, before anything of size
+ * n is read or allocated.  init_pos NULL: city order; not a permutation: TL_ERR_BADARG.  dm_packed as in tl_two_opt (expanded on
+ * the device to a row-major n x n copy; the matrix must be what the packed triangle is: symmetric).
+ * tl_sim_anneal runs chain 0.  stats (optional): sweeps = candidates = epochs run, moves = accepted epochs, reversed = elements
+ * moved by their reversals.
+ * tl_sim_anneal_trace: the same plus the accepted epochs in order, 4 words each: epoch, from, to, the bits of the new cost — what
+ * a caller replays the reference's PathUpdate messages from.  *log_len counts them all; the log holds the first log_cap.
+ * tl_sim_anneal_trace_chain: the same for chain `chain` of the seed (what a caller replays the best chain of a population from).
+ * tl_sim_anneal_population: chains first_chain .. first_chain + count - 1, each its own stream of draws, all concurrently (more
+ * chains than the device holds at once — tl_sim_anneal_plan's per_launch — run in further launches).  init_count 0: every chain
+ * from city order (init_pos ignored); 1: every chain from init_pos; count: chain r from init_pos + r * n; anything else
+ * TL_ERR_BADARG.  out_pos count x n, out_costs / out_moves (optional) count entries, *best_index (optional) the chain (0-based
+ * within the call) of minimum tl_pack_cost_key(cost, index): equal costs go to the lower chain.  Chain c of any population equals
+ * first_chain = c, count = 1.  count == 0: TL_OK, nothing written.  stats: sums over the chains.
+ * Host-only queries (no context, no device): tl_sa_draw — the u64 above; tl_sa_schedule_epochs — the length of the schedule
+ * (TL_ERR_UNSUPPORTED as above; the options are not validated); tl_sim_anneal_plan — the window (epochs at once), the threads of a
+ * chain's workgroup and the chains one launch holds, for n cities and count chains on a device with cus compute units and lds_bytes
+ * of LDS per workgroup (outputs optional; window and threads 0 where n exceeds the LDS-resident limit).
+ * tl_sa_selftest_accept: the acceptance rule evaluated on the device for count given (T, old, new, p): out_accept 0 / 1,
+ * out_criteria the criterion's value (computed for every entry, also where the rule does not consult it). */
+typedef struct tl_sa_opts { /* SAOptions, src/tsp/mod.rs:689-706 */
+    uint32_t epochs;        /* default 10 000 */
+    float cooling_rate;     /* default 1e-4   */
+    float min_temperature;  /* default 1e-3   */
+    float max_temperature;  /* default 1000   */
+} tl_sa_opts;
+uint32_t tl_sim_anneal_lds_max_n(const tl_ctx *ctx);
+int tl_sim_anneal(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_sa_opts *opts,
+                  uint64_t seed, uint32_t *out_pos, float *out_cost, tl_stats *stats);
+int tl_sim_anneal_trace(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_sa_opts *opts,
+                        uint64_t seed, uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *move_log, uint32_t log_cap,
+                        uint32_t *log_len);
+int tl_sim_anneal_trace_chain(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_sa_opts *opts,
+                              uint64_t seed, uint32_t chain, uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *move_log, uint32_t log_cap,
+                              uint32_t *log_len);
+int tl_sim_anneal_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
+                             uint32_t first_chain, uint32_t count, const tl_sa_opts *opts, uint64_t seed, uint32_t *out_pos, float *out_costs,
+                             uint32_t *out_moves, uint32_t *best_index, tl_stats *stats);
+uint64_t tl_sa_draw(uint64_t seed, uint32_t chain, uint32_t epoch, uint32_t slot);
+int tl_sa_schedule_epochs(const tl_sa_opts *opts, uint64_t *epochs);
+int tl_sim_anneal_plan(uint32_t n, uint32_t count, int cus, int lds_bytes, uint32_t flags, uint32_t *window, int *threads, uint32_t *per_launch);
+int tl_sa_selftest_accept(tl_ctx *ctx, const float *T, const float *old_cost, const float *new_cost, const float *p, uint32_t count,
+                          uint32_t *out_accept, float *out_criteria);
 
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts

@@ -94,6 +94,17 @@ unsafe extern "C" {
                                out_pos: *mut u32, out_costs: *mut f32, out_moves: *mut u32, stats: *mut Stats) -> c_int;
     fn tl_lk(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, opts: *const LkOpts, seed: u64,
              out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats) -> c_int;
+    fn tl_sim_anneal_lds_max_n(ctx: *const TlCtx) -> u32;
+    fn tl_sim_anneal(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, opts: *const SaOpts, seed: u64,
+                     out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats) -> c_int;
+    fn tl_sim_anneal_trace_chain(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, opts: *const SaOpts, seed: u64,
+                                 chain: u32, out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats, move_log: *mut u32, log_cap: u32,
+                                 log_len: *mut u32) -> c_int;
+    fn tl_sim_anneal_population(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, init_count: u32,
+                                first_chain: u32, count: u32, opts: *const SaOpts, seed: u64, out_pos: *mut u32, out_costs: *mut f32,
+                                out_moves: *mut u32, best_index: *mut u32, stats: *mut Stats) -> c_int;
+    fn tl_sa_draw(seed: u64, chain: u32, epoch: u32, slot: u32) -> u64;
+    fn tl_sa_schedule_epochs(opts: *const SaOpts, epochs: *mut u64) -> c_int;
     fn tl_nearest_neighbor(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, n_nearest: u32,
                            out_pos: *mut u32, out_cost: *mut f32) -> c_int;
     fn tl_greedy_edge(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
@@ -108,6 +119,35 @@ unsafe extern "C" {
     fn tl_two_opt_multistart_devices(ctxs: *const *mut TlCtx, n_ctxs: c_int, xy: *const f32, n: u32, seed: u64, first: u32, count: u32,
                                      mode: c_int, out_best_pos: *mut u32, out_best_cost: *mut f32, out_best_restart: *mut u32,
                                      out_costs: *mut f32, stats: *mut Stats) -> c_int;
+}
+
+/// `tl_sa_opts` (SAOptions, mod.rs:689-706)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SaOpts {
+    pub epochs: u32,
+    pub cooling_rate: f32,
+    pub min_temperature: f32,
+    pub max_temperature: f32,
+}
+
+impl Default for SaOpts {
+    fn default() -> Self {
+        SaOpts { epochs: 10_000, cooling_rate: 1e-4, min_temperature: 1e-3, max_temperature: 1000.0 }
+    }
+}
+
+/// u(seed, chain, epoch, slot) of the library's seeded stream (host only).
+pub fn sa_draw(seed: u64, chain: u32, epoch: u32, slot: u32) -> u64 {
+    // SAFETY: a pure function of its arguments.
+    unsafe { tl_sa_draw(seed, chain, epoch, slot) }
+}
+
+/// The epochs `while epoch < epochs || temperature > min_temperature` runs (138 149 with the defaults); None beyond 2^32 - 1.
+pub fn sa_schedule_epochs(opts: SaOpts) -> Option<u64> {
+    let mut e = 0u64;
+    // SAFETY: both pointers are to live locals.
+    if unsafe { tl_sa_schedule_epochs(&opts, &mut e) } == 0 { Some(e) } else { None }
 }
 
 /// `tl_status` (include/teeline_gpu.h)
@@ -390,6 +430,71 @@ impl Context {
         // SAFETY: as in two_opt.
         let rc = unsafe { tl_three_opt(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats) };
         self.check(rc).map(|_| t)
+    }
+
+    /// `simulated_annealing::solve` (simulated_annealing.rs:10-83), chain 0 of `seed`.  The chain is the reference's; its random draws
+    /// and the evaluation of exp are the library's own specification (include/teeline_gpu.h).  (Written against the header; not
+    /// compiled here: no Rust toolchain on the build machine, see scripts/check_rust.sh.)
+    pub fn sim_anneal(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, opts: SaOpts, seed: u64) -> Result<Tour, Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        // SAFETY: as in two_opt; opts is a plain struct that lives across the call.
+        let rc = unsafe { tl_sim_anneal(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), &opts, seed, t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats) };
+        self.check(rc).map(|_| t)
+    }
+
+    /// Chain `chain` of `seed` with its accepted epochs `[epoch, from, to, cost bits]`, from which the reference's PathUpdate
+    /// messages are replayed.
+    pub fn sim_anneal_trace(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, opts: SaOpts, seed: u64, chain: u32)
+                            -> Result<(Tour, Vec<[u32; 4]>), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        let mut cap: u32 = 1 << 14;
+        loop {
+            let mut log = vec![[0u32; 4]; cap as usize];
+            let mut len: u32 = 0;
+            // SAFETY: as in two_opt; log holds cap entries of 4 words.
+            let rc = unsafe {
+                tl_sim_anneal_trace_chain(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), &opts, seed, chain, t.pos.as_mut_ptr(), &mut t.cost,
+                                          &mut t.stats, log.as_mut_ptr() as *mut u32, cap, &mut len)
+            };
+            self.check(rc)?;
+            if len <= cap {
+                log.truncate(len as usize);
+                return Ok((t, log));
+            }
+            cap = len;
+        }
+    }
+
+    /// Chains `first_chain .. first_chain + count` of `seed` at once, every chain from `init_pos` (or city order); the tours and the
+    /// index of the best one (lowest cost, then lowest chain).
+    pub fn sim_anneal_population(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, first_chain: u32, count: u32, opts: SaOpts,
+                                 seed: u64) -> Result<(Vec<Tour>, u32), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let mut pos = vec![0u32; n as usize * count as usize];
+        let mut costs = vec![0f32; count as usize];
+        let mut moves = vec![0u32; count as usize];
+        let (mut best, mut st) = (0u32, Stats::default());
+        // SAFETY: as in two_opt; the output arrays hold count x n, count and count entries.
+        let rc = unsafe {
+            tl_sim_anneal_population(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), if init_pos.is_some() { 1 } else { 0 }, first_chain,
+                                     count, &opts, seed, pos.as_mut_ptr(), costs.as_mut_ptr(), moves.as_mut_ptr(), &mut best, &mut st)
+        };
+        self.check(rc)?;
+        let tours = (0..count as usize)
+            .map(|k| Tour { pos: pos[k * n as usize..(k + 1) * n as usize].to_vec(), cost: costs[k], stats: Stats { moves: moves[k] as u64, ..st } })
+            .collect();
+        Ok((tours, best))
+    }
+
+    /// Largest n of `sim_anneal` (the chain lives in one CU's LDS, 12 bytes per city).
+    pub fn sim_anneal_lds_max_n(&self) -> u32 {
+        // SAFETY: a plain query of a live context.
+        unsafe { tl_sim_anneal_lds_max_n(self.raw) }
     }
 
     /// `or_opt::solve` (or_opt.rs:18-74).

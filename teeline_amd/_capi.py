@@ -36,6 +36,7 @@ TL_FLAG_BHK_EXACT_WALK = 1 << 25  # tl_bellman_karp: the route by exact f32 equa
 TL_FLAG_OR_OPT_FORCE_SCAN = 1 << 26  # tl_or_opt_population: tour after tour through tl_or_opt's chip-wide descent at every n
 TL_FLAG_3OPT_POP_FORCE_SCAN = 1 << 27  # tl_three_opt_population: tour after tour through tl_three_opt's chip-wide descent
 TL_FLAG_3OPT_POP_FORCE_WG = 1 << 28  # tl_three_opt_population: one workgroup per tour wherever it fits
+TL_FLAG_SA_NO_SPECULATION = 1 << 29  # tl_sim_anneal*: a window of one epoch (the chain epoch after epoch) instead of speculative windows
 TL_BHK_MAX_N = 26  # tl_bellman_karp: largest n (a table of 2^(n-1) rows of 128 bytes: 4 GiB)
 TL_FLAG_LK_SMALL = 1 << 9  # tl_lk: the LDS-resident single-workgroup form wherever it fits
 TL_FLAG_COUNT_WORK = 1 << 8  # the LDS 2-opt kernel also counts the work of its cascade (stats words 5..8); ~8 % slower
@@ -55,6 +56,8 @@ SYMBOLS = [
     "tl_greedy_edge", "tl_savings_hub", "tl_savings", "tl_christofides", "tl_bellman_karp",
     "tl_or_opt_population", "tl_or_opt_lds_max_n",
     "tl_three_opt_population", "tl_three_opt_pop_max_n", "tl_three_opt_population_plan", "tl_three_opt_population_work_limit",
+    "tl_sim_anneal", "tl_sim_anneal_trace", "tl_sim_anneal_trace_chain", "tl_sim_anneal_population", "tl_sim_anneal_lds_max_n", "tl_sim_anneal_plan",
+    "tl_sa_draw", "tl_sa_schedule_epochs", "tl_sa_selftest_accept",
 ]
 
 
@@ -69,6 +72,11 @@ class TlStats(C.Structure):
 class TlLkOpts(C.Structure):
     _fields_ = [("epochs", C.c_uint32), ("platoo_epochs", C.c_uint32), ("n_nearest", C.c_uint32),
                 ("max_depth", C.c_uint32)]
+
+
+class TlSaOpts(C.Structure):
+    """tl_sa_opts: SAOptions (src/tsp/mod.rs:689-706)"""
+    _fields_ = [("epochs", C.c_uint32), ("cooling_rate", C.c_float), ("min_temperature", C.c_float), ("max_temperature", C.c_float)]
 
 
 # tl_lk_progress_fn: void (*)(void *user, const uint32_t *best_pos, uint32_t n, float best_dist)
@@ -155,5 +163,16 @@ def load():
     L.tl_three_opt_population.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, C.POINTER(TlStats)]
     L.tl_three_opt_population_plan.argtypes = [u32, u32, C.c_int, C.c_int, C.c_uint64, u32, C.POINTER(i32), C.POINTER(i32), C.POINTER(u32)]
     L.tl_three_opt_population_work_limit.argtypes = [vp, C.c_uint64]
+    L.tl_sim_anneal_lds_max_n.argtypes = [vp]
+    L.tl_sim_anneal_lds_max_n.restype = u32
+    L.tl_sim_anneal.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlSaOpts), u64, vp, f32p, C.POINTER(TlStats)]
+    L.tl_sim_anneal_trace.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlSaOpts), u64, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32)]
+    L.tl_sim_anneal_trace_chain.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlSaOpts), u64, u32, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32)]
+    L.tl_sim_anneal_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, C.POINTER(TlSaOpts), u64, vp, vp, vp, C.POINTER(u32), C.POINTER(TlStats)]
+    L.tl_sa_draw.argtypes = [u64, u32, u32, u32]
+    L.tl_sa_draw.restype = u64
+    L.tl_sa_schedule_epochs.argtypes = [C.POINTER(TlSaOpts), C.POINTER(u64)]
+    L.tl_sim_anneal_plan.argtypes = [u32, u32, i32, i32, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
+    L.tl_sa_selftest_accept.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp]
     _lib = L
     return L

@@ -308,6 +308,30 @@ uint32_t or_opt_lds_max_n(int lds_budget, bool dm);       // largest n whose sta
 int or_opt_lds_threads(uint32_t n, uint32_t count, int cus, int lds_budget, bool dm);
 hipError_t launch_or_opt_lds(const PopArgs &A, uint32_t count, int threads, hipStream_t s);
 
+// sim_anneal.hip — simulated annealing, one workgroup per chain
+struct SaArgs {
+    const float2 *xy;       // n cities, city order (coordinate form)
+    const float *dm_full;   // the matrix expanded to row-major n x n, or nullptr
+    const uint32_t *init;   // chain b of the launch starts from init + b * init_stride (0: every chain from the same tour)
+    uint32_t *out_pos;      // [count][n] the chains' last states
+    float *out_cost;        // [count] their tour_length
+    uint32_t *out_run;      // [count][4] accepted epochs, elements moved (64 bits), unused: added to by every launch of a schedule
+    const float *temps;     // [e_end - e_begin] the temperatures of this launch's epochs
+    uint32_t *log;          // optional: [log_cap][4] epoch, from, to, cost bits of every accepted epoch of the launch's chain 0
+    uint64_t seed;
+    uint32_t log_cap;
+    uint32_t first_chain;   // stream id of the launch's chain 0
+    uint32_t n;
+    uint32_t init_stride;
+    uint32_t e_begin, e_end;  // the epochs this launch runs
+    uint32_t window;        // epochs evaluated at once (1 .. threads)
+};
+size_t sim_anneal_lds_bytes(uint32_t n);     // LDS of one chain's workgroup (either form)
+uint32_t sim_anneal_lds_max_n(int lds_budget);
+hipError_t launch_sim_anneal(const SaArgs &A, uint32_t count, int threads, hipStream_t s);
+hipError_t launch_sa_selftest(const float *T, const float *oldc, const float *newc, const float *p, uint32_t count, uint32_t *out_accept,
+                              float *out_criteria, hipStream_t s);
+
 // lk.hip
 struct LkState {             // device-side state machine of the multi-CU LK variant
     uint32_t key;            // min pair index with a valid chain in the current scan (0xFFFFFFFF: none)

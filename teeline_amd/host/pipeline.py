@@ -12,9 +12,19 @@ SOLVER_NAMES = {"nn": "nearest_neighbor", "nearest_neighbor": "nearest_neighbor"
                 "3opt": "three_opt", "three_opt": "three_opt", "oropt": "or_opt", "or_opt": "or_opt", "or-opt": "or_opt",
                 "lk": "lin_kernighan", "lin_kernighan": "lin_kernighan", "shuffle": "random_shuffle",
                 "random_shuffle": "random_shuffle", "greedy_edge": "greedy_edge", "gec": "greedy_edge", "savings": "savings", "sav": "savings",
-                "christofides": "christofides", "chr": "christofides", "bhk": "bellman_karp", "bellman_karp": "bellman_karp"}
-PRESETS = {"fast": ["nn", "2opt"]}  # resolve_preset (main.rs:354-369); classic / thorough end in SA (not accelerated)
+                "christofides": "christofides", "chr": "christofides", "bhk": "bellman_karp", "bellman_karp": "bellman_karp",
+                "simulated_annealing": "simulated_annealing"}  # (the alias `sa` stays refused: below)
+PRESETS = {"fast": ["nn", "2opt"], "classic": ["nn", "2opt", "simulated_annealing"], "thorough": ["nn", "3opt", "simulated_annealing"]}  # resolve_preset (main.rs:354-369)
+# The reference's short alias `sa` is NOT taken: callers of earlier versions rely on `sa` being refused (it named the reference's unseeded,
+# unreproducible chain), and this build's annealing is a seeded chain of its own specification.  Ask for it by its long name.
+REFUSED_ALIASES = {"sa": "simulated_annealing"}
+AUTO_EXPAND_WITH_SHUFFLE = {"simulated_annealing"}  # mod.rs:144-157: `solve simulated_annealing` alone is shuffle -> simulated_annealing
 AUTO_EXPAND_WITH_NN = {"two_opt", "three_opt", "or_opt", "lin_kernighan"}  # mod.rs:129-139 (greedy_edge, savings and christofides are seeds: `solve gec` / `solve sav` / `solve chr` run alone; so does the exact solver `solve bhk`, mod.rs:2137)
+
+
+def _unknown(name):
+    hint = f"; the seeded annealing of this build is `{REFUSED_ALIASES[name.lower()]}`" if name.lower() in REFUSED_ALIASES else ""
+    return f"unknown solver `{name}` (this build accelerates {sorted(set(SOLVER_NAMES))}){hint}"
 
 
 def steps_for_solve(solver, no_seed=False):
@@ -23,9 +33,11 @@ def steps_for_solve(solver, no_seed=False):
     if s in PRESETS:
         return list(PRESETS[s])
     if s not in SOLVER_NAMES:
-        raise ValueError(f"unknown solver `{solver}` (this build accelerates {sorted(set(SOLVER_NAMES))})")
+        raise ValueError(_unknown(solver))
     if not no_seed and SOLVER_NAMES[s] in AUTO_EXPAND_WITH_NN:
         return ["nn", s]
+    if not no_seed and SOLVER_NAMES[s] in AUTO_EXPAND_WITH_SHUFFLE:
+        return ["shuffle", s]
     return [s]
 
 
@@ -72,12 +84,13 @@ class StageOutcome:
         self.name, self.solution, self.duration_ms = name, solution, duration_ms
 
 
-def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact_walk=False, init_tour=None):
-    """steps: iterable of solver names ("nn", "gec", "sav", "chr", "bhk", "2opt", "3opt", "or_opt", "lk", "shuffle"); opts: {name: options} (optional).
+def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact_walk=False, init_tour=None, sa_chains=1):
+    """steps: iterable of solver names ("nn", "gec", "sav", "chr", "bhk", "2opt", "3opt", "or_opt", "lk", "simulated_annealing", "shuffle"); opts: {name: options} (optional).
+    A `simulated_annealing` stage draws from the stream of lk_seed (the pipeline's one seed) and runs sa_chains chains, keeping the best.
     exact_walk: a `bhk` stage reads its route back by exact equality (bellman_karp.solve) instead of the reference's tolerance walk,
     whose result can fail validate_tour below.  init_tour: the seed of the first stage (city ids; default: that stage's own seeding)."""
-    from . import (HeuristicOptions, LKOptions, bellman_karp, christofides, greedy_edge, lin_kernighan, nearest_neighbor, or_opt, savings, three_opt, two_opt,
-                   validate_tour)
+    from . import (HeuristicOptions, LKOptions, bellman_karp, christofides, greedy_edge, lin_kernighan, nearest_neighbor, or_opt, savings, simulated_annealing,
+                   three_opt, two_opt, validate_tour)
     mods = {"nearest_neighbor": nearest_neighbor, "two_opt": two_opt, "three_opt": three_opt, "or_opt": or_opt,
             "lin_kernighan": lin_kernighan, "greedy_edge": greedy_edge, "savings": savings, "christofides": christofides,
             "bellman_karp": bellman_karp}
@@ -85,7 +98,7 @@ def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact
     outcomes, seed = [], (None if init_tour is None else list(init_tour))
     for step in steps:
         if step not in SOLVER_NAMES:
-            raise ValueError(f"unknown solver `{step}` (this build accelerates {sorted(set(SOLVER_NAMES))})")
+            raise ValueError(_unknown(step))
         name = SOLVER_NAMES[step]
         init = seed
         if init is not None and not validate_tour(init, problem):
@@ -96,6 +109,8 @@ def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact
             sol = random_shuffle(problem, lk_seed, ctx=ctx)
         elif name == "lin_kernighan":
             sol = lin_kernighan.solve(problem, opts.get(step) or LKOptions(), None, init, ctx=ctx, seed=lk_seed)
+        elif name == "simulated_annealing":
+            sol = simulated_annealing.solve(problem, opts.get(step) or simulated_annealing.SAOptions(), None, init, ctx=ctx, seed=lk_seed, chains=sa_chains)
         elif name == "bellman_karp":
             sol = mods[name].solve(problem, opts.get(step) or HeuristicOptions(), None, init, ctx=ctx, exact_walk=exact_walk)
         else:

@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <exception>
 #include <fstream>
 #include <functional>
@@ -884,8 +885,85 @@ inline Solution solve(Context &ctx, const TspProblem &problem, uint64_t seed)
 }
 }  // namespace random_shuffle
 
+namespace simulated_annealing {  // simulated_annealing.rs:10-83
+struct SAOptions {  // mod.rs:689-706
+    HeuristicOptions heuristic;
+    float cooling_rate = 0.0001f, min_temperature = 0.001f, max_temperature = 1000.0f;
+    // SAOptions::validate (mod.rs:708-742): the message, or empty
+    std::string validate() const
+    {
+        char b[128] = "";
+        if (heuristic.n_nearest == 0) return "n_nearest must be >= 1";
+        if (cooling_rate <= 0.0f) std::snprintf(b, sizeof b, "cooling_rate must be > 0 (got %g)", cooling_rate);
+        else if (cooling_rate >= 1.0f) std::snprintf(b, sizeof b, "cooling_rate must be < 1 (got %g)", cooling_rate);
+        else if (max_temperature <= 0.0f) std::snprintf(b, sizeof b, "max_temperature must be > 0 (got %g)", max_temperature);
+        else if (min_temperature < 0.0f) std::snprintf(b, sizeof b, "min_temperature must be >= 0 (got %g)", min_temperature);
+        else if (min_temperature >= max_temperature)
+            std::snprintf(b, sizeof b, "min_temperature (%g) must be < max_temperature (%g)", min_temperature, max_temperature);
+        return b;
+    }
+};
+
+// The chain is the reference's; its random draws (a pure function of seed, chain, epoch and slot) and the evaluation of exp are this
+// project's specification (include/teeline_gpu.h).  chains > 1: chains 0 .. chains-1 of the seed at once, the best one returned
+// (lowest cost, then lowest chain).  With a progress callback the reference's messages — PathUpdate(route, distance) for the start
+// route and after every accepted epoch, then Done (simulated_annealing.rs:33-38,49-54,63-65) — are replayed from the accepted
+// epochs of that chain (tl_sim_anneal_trace_chain).
+inline Solution solve(Context &ctx, const TspProblem &problem, const SAOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
+                      uint64_t seed = 1, uint32_t chains = 1)
+{
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size();
+    std::vector<uint32_t> init, out(n);
+    if (init_tour) init = problem.positions_of(*init_tour);
+    const uint32_t *ip = init_tour ? init.data() : nullptr;
+    const tl_sa_opts o{(uint32_t)opts.heuristic.epochs, opts.cooling_rate, opts.min_temperature, opts.max_temperature};
+    float cost = 0.f;
+    tl_stats st{};
+    uint32_t chain = 0;
+    if (chains > 1) {
+        std::vector<uint32_t> outs((size_t)chains * n), moves(chains);
+        std::vector<float> costs(chains);
+        ctx.check(tl_sim_anneal_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, chains, &o, seed, outs.data(), costs.data(),
+                                           moves.data(), &chain, &st));
+        std::copy(outs.begin() + (size_t)chain * n, outs.begin() + (size_t)(chain + 1) * n, out.begin());
+        cost = costs[chain];
+        st.moves = moves[chain];
+        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
+    } else if (!(progress_tx && *progress_tx)) {
+        ctx.check(tl_sim_anneal(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, out.data(), &cost, &st));
+        return detail::finish(problem, out, cost, st, nullptr);
+    }
+    uint32_t cap = 1u << 14, len = 0;
+    std::vector<uint32_t> log;
+    for (;;) {
+        log.assign((size_t)cap * 4, 0u);
+        ctx.check(tl_sim_anneal_trace_chain(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, chain, out.data(), &cost, &st, log.data(), cap, &len));
+        if (len <= cap) break;
+        cap = len;  // deterministic: once more with room for every accepted epoch
+    }
+    std::vector<uint32_t> pos(n);
+    for (uint32_t q = 0; q < n; ++q) pos[q] = init_tour ? init[q] : q;
+    std::vector<size_t> route(n);
+    auto send = [&](float d) {
+        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[pos[q]].id;
+        (*progress_tx)(ProgressKind::PathUpdate, route, d);
+    };
+    send(or_opt::tour_length_f32(problem, xy, pos));
+    for (uint32_t m = 0; m < len; ++m) {
+        std::reverse(pos.begin() + log[4 * m + 1], pos.begin() + log[4 * m + 2] + 1);  // swap_cities (route.rs:102-113)
+        float d;
+        std::memcpy(&d, &log[4 * m + 3], 4);
+        send(d);
+    }
+    Solution s = detail::finish(problem, out, cost, st, nullptr);
+    (*progress_tx)(ProgressKind::Done, s.route_, cost);
+    return s;
+}
+}  // namespace simulated_annealing
+
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
-enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp };
+enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing };
 
 inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
 {
@@ -900,14 +978,16 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
     else if (s == "sav" || s == "savings") out = Solvers::Savings;
     else if (s == "chr" || s == "christofides") out = Solvers::Christofides;
     else if (s == "bhk" || s == "bellman_karp") out = Solvers::BellmanKarp;
+    else if (s == "simulated_annealing") out = Solvers::SimulatedAnnealing;  // (the alias `sa` stays refused, below: this build's annealing is a
+                                                                              // seeded chain of its own specification, asked for by its long name)
     else {
         static const char *cpu_only[] = {"aco", "ant_colony", "branch_bound",
                                          "cs", "cuckoo_search", "fpa", "flower_pollination", "fourier", "ga", "genetic_algorithm", "gsa",
-                                         "gravitational_search", "pso", "particle_swarm", "sa", "simulated_annealing",
+                                         "gravitational_search", "pso", "particle_swarm", "sa",
                                          "som", "kohonen", "kohonen_som", "stochastic_hill", "tabu", "tabu_search"};
         for (const char *c : cpu_only)
             if (s == c) {
-                why = "solver `" + s + "` is not accelerated by this build (nn, gec, sav, chr, bhk, 2opt, 3opt, or_opt, lk, shuffle are)";
+                why = "solver `" + s + "` is not accelerated by this build (nn, gec, sav, chr, bhk, 2opt, 3opt, or_opt, lk, shuffle are, and simulated_annealing under its long name)";
                 return false;
             }
         why = "unknown solver";  // FromStr's Err (mod.rs:588)
@@ -928,6 +1008,7 @@ inline const char *solver_name(Solvers s)
         case Solvers::Savings: return "savings";
         case Solvers::Christofides: return "christofides";
         case Solvers::BellmanKarp: return "bellman_karp";
+        case Solvers::SimulatedAnnealing: return "simulated_annealing";
         default: return "shuffle";
     }
 }
@@ -937,7 +1018,9 @@ struct StageOptions {
     HeuristicOptions heuristic;
     LKOptions lk;
     int two_opt_mode = TL_MODE_REF_ORDER;
-    uint64_t seed = 1;  // LK kicks, shuffle
+    simulated_annealing::SAOptions sa;
+    uint32_t sa_chains = 1;  // an sa stage runs this many chains and keeps the best
+    uint64_t seed = 1;  // LK kicks, shuffle, SA draws
     const ProgressFn *progress = nullptr;  // handed to every stage's solve() (the reference's CLI passes None; teeline-qt a sender)
 };
 struct StageOutcome {  // :11-14
@@ -998,6 +1081,7 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             case Solvers::Savings: sol = savings::solve(ctx, problem, o.heuristic, o.progress, init); break;
             case Solvers::Christofides: sol = christofides::solve(ctx, problem, o.heuristic, o.progress, init); break;
             case Solvers::BellmanKarp: sol = bellman_karp::solve(ctx, problem, o.heuristic, o.progress, init); break;
+            case Solvers::SimulatedAnnealing: sol = simulated_annealing::solve(ctx, problem, o.sa, o.progress, init, o.seed, o.sa_chains); break;
         }
         const auto t1 = std::chrono::steady_clock::now();
         const uint64_t ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();

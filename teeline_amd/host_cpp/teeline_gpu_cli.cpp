@@ -5,7 +5,10 @@
 //                                     [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P] [--n_nearest K] [--max-depth D]
 //   teeline-gpu pipeline --steps=nn,2opt,... [-i FILE] [same options]
 //   teeline-gpu solvers [--short]
-//     solver  : nn, gec, sav, chr, bhk, 2opt, 3opt, or_opt, lk, shuffle (and their long names, mod.rs:559-590); preset: fast = nn,2opt (main.rs:354-369)
+//     solver  : nn, gec, sav, chr, bhk, 2opt, 3opt, or_opt, lk, shuffle (and their long names), simulated_annealing (long name only: `sa` stays refused, mod.rs:559-590); presets (main.rs:354-369):
+//               fast = nn,2opt; classic = nn,2opt,simulated_annealing; thorough = nn,3opt,simulated_annealing
+//     annealing: --cooling-rate C --min-temperature LO --max-temperature HI (SAOptions, mod.rs:689-706; --epochs is the shared one),
+//               --chains K (own flag: K chains of the seed at once, the best kept); `solve simulated_annealing` alone is pipeline(shuffle, simulated_annealing) (mod.rs:144-157)
 //     solve   : 2opt / 3opt / or_opt / lk auto-expand to pipeline(nn, solver) unless --no-seed (main.rs:387-397, mod.rs:129-139);
 //               gec (greedy_edge), sav (savings) and chr (christofides) are constructions and run alone; so does bhk (bellman_karp),
 //               the exact solver (n <= 26, mod.rs:2137) — as a later pipeline stage it ignores its seed
@@ -43,10 +46,11 @@ struct Args {
 {
     if (why) std::fprintf(stderr, "error: %s\n", why);
     std::fprintf(stderr,
-                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|shuffle|fast> [-i FILE] [--no-seed] [--output-format text|json]\n"
+                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
                  "                         [--optimal-tour FILE] [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P]\n"
                  "                         [--n_nearest K] [--max-depth D] [--seed S] [--best-sweep] [--device N] [--stats]\n"
                  "                         [--progress-digest] [--exact-walk]\n"
+                 "                         [--cooling-rate C] [--min-temperature LO] [--max-temperature HI] [--chains K]\n"
                  "       teeline-gpu pipeline --steps=nn,2opt,... | --steps=greedy_edge,2opt,... | --steps=savings,2opt,... | --steps=christofides,lk,... [-i FILE] [options as above]\n"
                  "       teeline-gpu solvers [--short]\n");
     std::exit(2);  // clap's usage-error exit code
@@ -99,7 +103,11 @@ Args parse(int argc, char **argv)
         else if (s == "--output-format") a.output_format = val();
         else if (s == "--optimal-tour") a.optimal_tour = val();
         else if (s == "--distance-type") a.distance_type = val();
-        else if (s == "--epochs") a.opt.heuristic.epochs = a.opt.lk.heuristic.epochs = parse_usize(s, val());
+        else if (s == "--epochs") a.opt.heuristic.epochs = a.opt.lk.heuristic.epochs = a.opt.sa.heuristic.epochs = parse_usize(s, val());
+        else if (s == "--cooling-rate" || s == "--cooling_rate") a.opt.sa.cooling_rate = std::stof(val());
+        else if (s == "--min-temperature" || s == "--min_temperature") a.opt.sa.min_temperature = std::stof(val());
+        else if (s == "--max-temperature" || s == "--max_temperature") a.opt.sa.max_temperature = std::stof(val());
+        else if (s == "--chains") a.opt.sa_chains = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--platoo_epochs" || s == "--platoo-epochs") a.opt.heuristic.platoo_epochs = a.opt.lk.heuristic.platoo_epochs = parse_usize(s, val());
         else if (s == "--n_nearest" || s == "--n-nearest") a.opt.heuristic.n_nearest = a.opt.lk.heuristic.n_nearest = parse_usize(s, val());
         else if (s == "--max-depth") a.opt.lk.max_depth = parse_usize(s, val());
@@ -124,6 +132,13 @@ Args parse(int argc, char **argv)
     if (a.opt.lk.max_depth == 0) {
         std::fprintf(stderr, "error: max_depth must be >= 1\n");
         std::exit(1);
+    }
+    {   // SAOptions::from_cli validates (mod.rs:708-742)
+        const std::string why = a.opt.sa.validate();
+        if (!why.empty()) {
+            std::fprintf(stderr, "error: %s\n", why.c_str());
+            std::exit(1);
+        }
     }
     a.opt.two_opt_mode = a.best ? TL_MODE_BEST_SWEEP : TL_MODE_REF_ORDER;
     return a;
@@ -208,10 +223,9 @@ int run(int argc, char **argv)
             std::string name = a.solver;
             for (auto &ch : name) ch = (char)std::tolower((unsigned char)ch);
             if (name == "fast") stages = {Solvers::NearestNeighbor, Solvers::TwoOpt};  // resolve_preset (main.rs:354-369)
-            else if (name == "classic" || name == "thorough") {
-                std::fprintf(stderr, "error: preset `%s` ends in simulated annealing, which this build does not accelerate\n", name.c_str());
-                return 1;
-            } else {
+            else if (name == "classic") stages = {Solvers::NearestNeighbor, Solvers::TwoOpt, Solvers::SimulatedAnnealing};
+            else if (name == "thorough") stages = {Solvers::NearestNeighbor, Solvers::ThreeOpt, Solvers::SimulatedAnnealing};
+            else {
                 Solvers s;
                 std::string why;
                 if (!solver_from_str(name, s, why)) {
@@ -221,6 +235,7 @@ int run(int argc, char **argv)
                 // auto_expand_with_nn (mod.rs:129-139): deterministic local searches are seeded with a nearest-neighbour stage
                 const bool expand = s == Solvers::TwoOpt || s == Solvers::ThreeOpt || s == Solvers::LinKernighan || s == Solvers::OrOpt;
                 if (!a.no_seed && expand) stages = {Solvers::NearestNeighbor, s};
+                else if (!a.no_seed && s == Solvers::SimulatedAnnealing) stages = {Solvers::RandomShuffle, s};  // mod.rs:144-157
                 else stages = {s};
             }
         } else {
