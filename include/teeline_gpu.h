@@ -45,7 +45,8 @@ extern "C" {
 #define TL_ABI_VERSION 5 /* bumped when an existing entry point, struct or code changes meaning; additions (round 5: tl_multistart_shard,
                             tl_two_opt_last_counters, new tl_create flags, k <= 64; later: tl_or_opt_population, tl_or_opt_lds_max_n,
                             TL_FLAG_OR_OPT_FORCE_SCAN, tl_three_opt_population and its three companions, TL_FLAG_3OPT_POP_*, tl_sim_anneal and its companions,
-                            TL_FLAG_SA_NO_SPECULATION) leave it — a caller built against 5 runs unchanged */
+                            TL_FLAG_SA_NO_SPECULATION, tl_tabu_search and its companions,
+                            TL_FLAG_TABU_FULL_COMPARE) leave it — a caller built against 5 runs unchanged */
 
 typedef struct tl_ctx tl_ctx;
 
@@ -121,6 +122,8 @@ typedef enum tl_mode {
                                               as many consecutive epochs at once as the chip holds, taken in order up to the first accepted one) */
 #define TL_FLAG_SA_NO_SPECULATION (1u << 29) /* tl_sim_anneal*: the same kernel with a window of one epoch — the chain epoch after epoch (default: a window of
                                               consecutive epochs evaluated at once against the same tour, the first accepted one committed) */
+#define TL_FLAG_TABU_FULL_COMPARE (1u << 30) /* tl_tabu_search*: every tabu-list membership test compares the candidate with every listed route element for
+                                              element (default: only with the listed routes whose hash equals the candidate's).  Same results: the cross-check form */
 /* TUNING BUILDS ONLY (libteeline_gpu_tune.so, -DTL_TUNE: `python -m teeline_amd.build --tune`).  Forms that were measured and
  * rejected and stay as cross-checks for development; the product library does not carry them and tl_create
  * returns TL_ERR_UNSUPPORTED if one of these bits is set. */
@@ -552,6 +555,55 @@ int tl_sa_schedule_epochs(const tl_sa_opts *opts, uint64_t *epochs);
 int tl_sim_anneal_plan(uint32_t n, uint32_t count, int cus, int lds_bytes, uint32_t flags, uint32_t *window, int *threads, uint32_t *per_launch);
 int tl_sa_selftest_accept(tl_ctx *ctx, const float *T, const float *old_cost, const float *new_cost, const float *p, uint32_t count,
                           uint32_t *out_accept, float *out_criteria);
+
+/* ---- tabu search: replaces tabu_search::solve (tabu_search.rs:9-110) ---------------------------------- */
+/* The reference's chain with its quirks kept: best = u = the start tour, which the list (capacity n routes, FIFO: a full list drops
+ * its oldest) receives.  Epoch e = 0, 1, ...: up to n + 1 candidates of u are drawn, each u with positions from..=to of the open path
+ * reversed (route.rs:48-113; after 10 redraws the last pair is used even when equal or adjacent) and costed with tour_length of the
+ * whole candidate (closing edge first, sequential f32).  The first of candidates 0 .. n-1 that is shorter than u AND equal to no
+ * listed route is taken; failing that, candidate n is taken with no check at all (it may be longer, equal to u, or listed).  A taken
+ * candidate shorter than the best so far becomes the best; the OLD u goes into the list (so the start tour is listed twice after
+ * epoch 0); u <- the taken candidate.  The loop ends when `epoch > epochs` after the increment: epochs + 1 epochs run.  The BEST
+ * route is returned.
+ * THE RANDOM STREAM IS THIS PROJECT'S SPECIFICATION, NOT THE REFERENCE'S (tests/_tabu_oracle.py is the
+ * statement): tl_sim_anneal's stream indexed by a 64-bit event, event = epoch (n + 1) + attempt,
+ *   u(seed, chain, event, slot) = mix(mix(seed + G (chain + 1)) + G (32 event + slot + 1))      (tl_tabu_draw)
+ * pair attempt t uses slots 2t, 2t + 1, a position is ((u >> 32) n) >> 32.  No draw depends on an earlier one, so the candidates of
+ * an epoch are evaluated at once, a round of `window` per step (csrc/tabu_search.hip: one workgroup per chain, the tour in that CU's
+ * LDS, 12 bytes per city; the list a ring of n routes of 16-bit entries in the context's workspace, 2 n^2 bytes per chain, with one
+ * hash per route — a hash match is always followed by an element-for-element comparison, and with TL_FLAG_TABU_FULL_COMPARE every
+ * listed route is compared).
+ * epochs = 0 (the reference never ends) and epochs = 2^32 - 1: TL_ERR_UNSUPPORTED.  n < 2: TL_ERR_REF_PANICS (route.rs:87-89).
+ * n > tl_tabu_search_lds_max_n: TL_ERR_UNSUPPORTED, before anything of size n is read or allocated (no HBM form).  init_pos NULL:
+ * city order; not a permutation: TL_ERR_BADARG.  A context whose flags hold a bit no flag has: TL_ERR_UNSUPPORTED.  dm_packed as in
+ * tl_sim_anneal.
+ * tl_tabu_search runs chain 0.  stats (optional): sweeps = epochs run, candidates = the candidates the reference would have drawn
+ * (the sum of taken attempt + 1), moves = new bests, reversed = elements moved by the taken reversals.
+ * tl_tabu_search_trace: the same plus EVERY epoch in order, 4 words each: taken attempt (n: the unchecked one), from, to, the bits
+ * of the taken candidate's cost — what a caller replays the reference's PathUpdate messages from (one per new best).  *log_len
+ * counts them all; the log holds the first log_cap.  tl_tabu_search_trace_chain: the same for chain `chain` of the seed.
+ * tl_tabu_search_population: chains first_chain .. first_chain + count - 1, each its own stream of draws, concurrently (more
+ * chains than the LDS and the workspace limit hold at once — tl_tabu_search_plan's per_launch — run in further launches).
+ * init_count, out_pos / out_costs / out_moves (new bests per chain), *best_index and its tie rule, count == 0: as
+ * tl_sim_anneal_population.  Chain c of any population equals first_chain = c, count = 1.
+ * Host-only queries (no context, no device): tl_tabu_draw — the u64 above for candidate `attempt` of `epoch` on n cities;
+ * tl_tabu_search_plan — the window (candidates per round), the threads of a chain's workgroup and the chains one launch holds, for
+ * n cities and count chains on a device with cus compute units, lds_bytes of LDS per workgroup and workspace_bytes for the lists
+ * (outputs optional; all 0 where n is outside 2 .. the LDS-resident limit; the entries plan with 8 GiB). */
+uint32_t tl_tabu_search_lds_max_n(const tl_ctx *ctx);
+int tl_tabu_search(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t epochs, uint64_t seed,
+                   uint32_t *out_pos, float *out_cost, tl_stats *stats);
+int tl_tabu_search_trace(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t epochs, uint64_t seed,
+                         uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *move_log, uint32_t log_cap, uint32_t *log_len);
+int tl_tabu_search_trace_chain(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t epochs,
+                               uint64_t seed, uint32_t chain, uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *move_log,
+                               uint32_t log_cap, uint32_t *log_len);
+int tl_tabu_search_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
+                              uint32_t first_chain, uint32_t count, uint32_t epochs, uint64_t seed, uint32_t *out_pos, float *out_costs,
+                              uint32_t *out_moves, uint32_t *best_index, tl_stats *stats);
+uint64_t tl_tabu_draw(uint64_t seed, uint32_t chain, uint32_t n, uint32_t epoch, uint32_t attempt, uint32_t slot);
+int tl_tabu_search_plan(uint32_t n, uint32_t count, int cus, int lds_bytes, uint64_t workspace_bytes, uint32_t flags, uint32_t *window, int *threads,
+                        uint32_t *per_launch);
 
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts

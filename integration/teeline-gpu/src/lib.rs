@@ -105,6 +105,16 @@ unsafe extern "C" {
                                 out_moves: *mut u32, best_index: *mut u32, stats: *mut Stats) -> c_int;
     fn tl_sa_draw(seed: u64, chain: u32, epoch: u32, slot: u32) -> u64;
     fn tl_sa_schedule_epochs(opts: *const SaOpts, epochs: *mut u64) -> c_int;
+    fn tl_tabu_search_lds_max_n(ctx: *const TlCtx) -> u32;
+    fn tl_tabu_search(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, epochs: u32, seed: u64,
+                      out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats) -> c_int;
+    fn tl_tabu_search_trace_chain(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, epochs: u32, seed: u64,
+                                  chain: u32, out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats, move_log: *mut u32, log_cap: u32,
+                                  log_len: *mut u32) -> c_int;
+    fn tl_tabu_search_population(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, init_count: u32,
+                                 first_chain: u32, count: u32, epochs: u32, seed: u64, out_pos: *mut u32, out_costs: *mut f32,
+                                 out_moves: *mut u32, best_index: *mut u32, stats: *mut Stats) -> c_int;
+    fn tl_tabu_draw(seed: u64, chain: u32, n: u32, epoch: u32, attempt: u32, slot: u32) -> u64;
     fn tl_nearest_neighbor(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, n_nearest: u32,
                            out_pos: *mut u32, out_cost: *mut f32) -> c_int;
     fn tl_greedy_edge(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
@@ -141,6 +151,12 @@ impl Default for SaOpts {
 pub fn sa_draw(seed: u64, chain: u32, epoch: u32, slot: u32) -> u64 {
     // SAFETY: a pure function of its arguments.
     unsafe { tl_sa_draw(seed, chain, epoch, slot) }
+}
+
+/// u(seed, chain, epoch (n + 1) + attempt, slot): the draw of candidate `attempt` of a tabu-search epoch on n cities (host only).
+pub fn tabu_draw(seed: u64, chain: u32, n: u32, epoch: u32, attempt: u32, slot: u32) -> u64 {
+    // SAFETY: a pure function of its arguments.
+    unsafe { tl_tabu_draw(seed, chain, n, epoch, attempt, slot) }
 }
 
 /// The epochs `while epoch < epochs || temperature > min_temperature` runs (138 149 with the defaults); None beyond 2^32 - 1.
@@ -495,6 +511,66 @@ impl Context {
     pub fn sim_anneal_lds_max_n(&self) -> u32 {
         // SAFETY: a plain query of a live context.
         unsafe { tl_sim_anneal_lds_max_n(self.raw) }
+    }
+
+    /// `tabu_search::solve` (tabu_search.rs:9-110), chain 0 of `seed`: `epochs + 1` epochs, the best route seen.  The chain is the
+    /// reference's; its random draws are the library's own specification (include/teeline_gpu.h).  (Written against the header; not
+    /// compiled here: no Rust toolchain on the build machine, see scripts/check_rust.sh.)
+    pub fn tabu_search(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, epochs: u32, seed: u64) -> Result<Tour, Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        // SAFETY: as in two_opt.
+        let rc = unsafe { tl_tabu_search(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), epochs, seed, t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats) };
+        self.check(rc).map(|_| t)
+    }
+
+    /// Chain `chain` of `seed` with every epoch `[taken attempt, from, to, cost bits]`, from which the reference's PathUpdate messages
+    /// (one per new best) are replayed.
+    pub fn tabu_search_trace(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, epochs: u32, seed: u64, chain: u32)
+                             -> Result<(Tour, Vec<[u32; 4]>), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        let cap: u32 = epochs.saturating_add(1);
+        let mut log = vec![[0u32; 4]; cap as usize];
+        let mut len: u32 = 0;
+        // SAFETY: as in two_opt; log holds cap entries of 4 words.
+        let rc = unsafe {
+            tl_tabu_search_trace_chain(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), epochs, seed, chain, t.pos.as_mut_ptr(), &mut t.cost,
+                                       &mut t.stats, log.as_mut_ptr() as *mut u32, cap, &mut len)
+        };
+        self.check(rc)?;
+        log.truncate(len.min(cap) as usize);
+        Ok((t, log))
+    }
+
+    /// Chains `first_chain .. first_chain + count` of `seed` at once, every chain from `init_pos` (or city order); the best routes and
+    /// the index of the best one (lowest cost, then lowest chain).
+    pub fn tabu_search_population(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, first_chain: u32, count: u32, epochs: u32,
+                                  seed: u64) -> Result<(Vec<Tour>, u32), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let mut pos = vec![0u32; n as usize * count as usize];
+        let mut costs = vec![0f32; count as usize];
+        let mut moves = vec![0u32; count as usize];
+        let (mut best, mut st) = (0u32, Stats::default());
+        // SAFETY: as in two_opt; the output arrays hold count x n, count and count entries.
+        let rc = unsafe {
+            tl_tabu_search_population(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), if init_pos.is_some() { 1 } else { 0 }, first_chain,
+                                      count, epochs, seed, pos.as_mut_ptr(), costs.as_mut_ptr(), moves.as_mut_ptr(), &mut best, &mut st)
+        };
+        self.check(rc)?;
+        let tours = (0..count as usize)
+            .map(|k| Tour { pos: pos[k * n as usize..(k + 1) * n as usize].to_vec(), cost: costs[k], stats: Stats { moves: moves[k] as u64, ..st } })
+            .collect();
+        Ok((tours, best))
+    }
+
+    /// Largest n of `tabu_search` (the current tour lives in one CU's LDS, 12 bytes per city; the list's entries are 16 bits wide).
+    pub fn tabu_search_lds_max_n(&self) -> u32 {
+        // SAFETY: a plain query of a live context.
+        unsafe { tl_tabu_search_lds_max_n(self.raw) }
     }
 
     /// `or_opt::solve` (or_opt.rs:18-74).

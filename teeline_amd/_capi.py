@@ -37,6 +37,7 @@ TL_FLAG_OR_OPT_FORCE_SCAN = 1 << 26  # tl_or_opt_population: tour after tour thr
 TL_FLAG_3OPT_POP_FORCE_SCAN = 1 << 27  # tl_three_opt_population: tour after tour through tl_three_opt's chip-wide descent
 TL_FLAG_3OPT_POP_FORCE_WG = 1 << 28  # tl_three_opt_population: one workgroup per tour wherever it fits
 TL_FLAG_SA_NO_SPECULATION = 1 << 29  # tl_sim_anneal*: a window of one epoch (the chain epoch after epoch) instead of speculative windows
+TL_FLAG_TABU_FULL_COMPARE = 1 << 30  # tl_tabu_search*: every tabu-list membership test compares whole routes (the cross-check form)
 TL_BHK_MAX_N = 26  # tl_bellman_karp: largest n (a table of 2^(n-1) rows of 128 bytes: 4 GiB)
 TL_FLAG_LK_SMALL = 1 << 9  # tl_lk: the LDS-resident single-workgroup form wherever it fits
 TL_FLAG_COUNT_WORK = 1 << 8  # the LDS 2-opt kernel also counts the work of its cascade (stats words 5..8); ~8 % slower
@@ -58,6 +59,8 @@ SYMBOLS = [
     "tl_three_opt_population", "tl_three_opt_pop_max_n", "tl_three_opt_population_plan", "tl_three_opt_population_work_limit",
     "tl_sim_anneal", "tl_sim_anneal_trace", "tl_sim_anneal_trace_chain", "tl_sim_anneal_population", "tl_sim_anneal_lds_max_n", "tl_sim_anneal_plan",
     "tl_sa_draw", "tl_sa_schedule_epochs", "tl_sa_selftest_accept",
+    "tl_tabu_search", "tl_tabu_search_trace", "tl_tabu_search_trace_chain", "tl_tabu_search_population", "tl_tabu_search_lds_max_n", "tl_tabu_search_plan",
+    "tl_tabu_draw",
 ]
 
 
@@ -174,5 +177,14 @@ def load():
     L.tl_sa_schedule_epochs.argtypes = [C.POINTER(TlSaOpts), C.POINTER(u64)]
     L.tl_sim_anneal_plan.argtypes = [u32, u32, i32, i32, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
     L.tl_sa_selftest_accept.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp]
+    L.tl_tabu_search_lds_max_n.argtypes = [vp]
+    L.tl_tabu_search_lds_max_n.restype = u32
+    L.tl_tabu_search.argtypes = [vp, vp, u32, vp, vp, u32, u64, vp, f32p, C.POINTER(TlStats)]
+    L.tl_tabu_search_trace.argtypes = [vp, vp, u32, vp, vp, u32, u64, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32)]
+    L.tl_tabu_search_trace_chain.argtypes = [vp, vp, u32, vp, vp, u32, u64, u32, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32)]
+    L.tl_tabu_search_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, u32, u64, vp, vp, vp, C.POINTER(u32), C.POINTER(TlStats)]
+    L.tl_tabu_draw.argtypes = [u64, u32, u32, u32, u32, u32]
+    L.tl_tabu_draw.restype = u64
+    L.tl_tabu_search_plan.argtypes = [u32, u32, i32, i32, u64, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
     _lib = L
     return L

@@ -12,7 +12,16 @@
 // r = (x - k ln2_hi) - k ln2_lo, q = the Horner sum of r^i / i! up to i = 13, (float) ldexp(q, k).  No library exp: the
 // same operations on the device, on the host and in the oracle.
 #pragma once
+#if defined(__HIPCC__) || defined(__HIP__)
 #include <hip/hip_runtime.h>
+#else  // a plain host compiler (the stand-alone CPU restatements under tests/probes): the same text without the qualifiers
+#ifndef __host__
+#define __host__
+#endif
+#ifndef __device__
+#define __device__
+#endif
+#endif
 #include <math.h>
 #include <stdint.h>
 

@@ -332,6 +332,30 @@ hipError_t launch_sim_anneal(const SaArgs &A, uint32_t count, int threads, hipSt
 hipError_t launch_sa_selftest(const float *T, const float *oldc, const float *newc, const float *p, uint32_t count, uint32_t *out_accept,
                               float *out_criteria, hipStream_t s);
 
+// tabu_search.hip — tabu search, one workgroup per chain
+struct TabuArgs {
+    const float2 *xy;       // n cities, city order (coordinate form)
+    const float *dm_full;   // the matrix expanded to row-major n x n, or nullptr
+    const uint32_t *init;   // chain b of the launch starts from init + b * init_stride (0: every chain from the same tour)
+    uint32_t *out_pos;      // [count][n] the chains' best routes
+    float *out_cost;        // [count] their tour_length
+    uint32_t *out_run;      // [count][8] new bests, candidates (64 bits), elements moved (64 bits), unused
+    uint16_t *ring;         // [count][ring_stride] the tabu lists: n routes of n positions each
+    uint32_t *hashes;       // [count][n] one hash per listed route
+    uint32_t *log;          // optional: [log_cap][4] taken attempt, from, to, cost bits of every epoch of the launch's chain 0
+    uint64_t seed;
+    uint64_t ring_stride;   // elements between two chains' rings (>= n * n)
+    uint32_t log_cap;
+    uint32_t first_chain;   // stream id of the launch's chain 0
+    uint32_t n;
+    uint32_t init_stride;
+    uint32_t epochs;        // the epochs to run (the reference's `epochs` + 1)
+    uint32_t full_compare;  // every membership test compares whole routes (TL_FLAG_TABU_FULL_COMPARE)
+};
+size_t tabu_search_lds_bytes(uint32_t n);    // LDS of one chain's workgroup (either form)
+uint32_t tabu_search_lds_max_n(int lds_budget);
+hipError_t launch_tabu_search(const TabuArgs &A, uint32_t count, int threads, hipStream_t s);
+
 // lk.hip
 struct LkState {             // device-side state machine of the multi-CU LK variant
     uint32_t key;            // min pair index with a valid chain in the current scan (0xFFFFFFFF: none)

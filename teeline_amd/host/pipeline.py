@@ -13,17 +13,19 @@ SOLVER_NAMES = {"nn": "nearest_neighbor", "nearest_neighbor": "nearest_neighbor"
                 "lk": "lin_kernighan", "lin_kernighan": "lin_kernighan", "shuffle": "random_shuffle",
                 "random_shuffle": "random_shuffle", "greedy_edge": "greedy_edge", "gec": "greedy_edge", "savings": "savings", "sav": "savings",
                 "christofides": "christofides", "chr": "christofides", "bhk": "bellman_karp", "bellman_karp": "bellman_karp",
-                "simulated_annealing": "simulated_annealing"}  # (the alias `sa` stays refused: below)
+                "simulated_annealing": "simulated_annealing", "tabu_search": "tabu_search"}  # (the aliases `sa` and `tabu` stay refused: below)
 PRESETS = {"fast": ["nn", "2opt"], "classic": ["nn", "2opt", "simulated_annealing"], "thorough": ["nn", "3opt", "simulated_annealing"]}  # resolve_preset (main.rs:354-369)
 # The reference's short alias `sa` is NOT taken: callers of earlier versions rely on `sa` being refused (it named the reference's unseeded,
 # unreproducible chain), and this build's annealing is a seeded chain of its own specification.  Ask for it by its long name.
-REFUSED_ALIASES = {"sa": "simulated_annealing"}
+# `tabu` likewise: tabu search goes by its long name only.
+REFUSED_ALIASES = {"sa": "simulated_annealing", "tabu": "tabu_search"}
+REFUSED_HINTS = {"sa": "the seeded annealing of this build is", "tabu": "the seeded tabu search of this build is"}
 AUTO_EXPAND_WITH_SHUFFLE = {"simulated_annealing"}  # mod.rs:144-157: `solve simulated_annealing` alone is shuffle -> simulated_annealing
-AUTO_EXPAND_WITH_NN = {"two_opt", "three_opt", "or_opt", "lin_kernighan"}  # mod.rs:129-139 (greedy_edge, savings and christofides are seeds: `solve gec` / `solve sav` / `solve chr` run alone; so does the exact solver `solve bhk`, mod.rs:2137)
+AUTO_EXPAND_WITH_NN = {"two_opt", "three_opt", "or_opt", "lin_kernighan", "tabu_search"}  # mod.rs:129-139 (greedy_edge, savings and christofides are seeds: `solve gec` / `solve sav` / `solve chr` run alone; so does the exact solver `solve bhk`, mod.rs:2137)
 
 
 def _unknown(name):
-    hint = f"; the seeded annealing of this build is `{REFUSED_ALIASES[name.lower()]}`" if name.lower() in REFUSED_ALIASES else ""
+    hint = f"; {REFUSED_HINTS[name.lower()]} `{REFUSED_ALIASES[name.lower()]}`" if name.lower() in REFUSED_ALIASES else ""
     return f"unknown solver `{name}` (this build accelerates {sorted(set(SOLVER_NAMES))}){hint}"
 
 
@@ -84,13 +86,14 @@ class StageOutcome:
         self.name, self.solution, self.duration_ms = name, solution, duration_ms
 
 
-def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact_walk=False, init_tour=None, sa_chains=1):
-    """steps: iterable of solver names ("nn", "gec", "sav", "chr", "bhk", "2opt", "3opt", "or_opt", "lk", "simulated_annealing", "shuffle"); opts: {name: options} (optional).
-    A `simulated_annealing` stage draws from the stream of lk_seed (the pipeline's one seed) and runs sa_chains chains, keeping the best.
+def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact_walk=False, init_tour=None, sa_chains=1, tabu_chains=1):
+    """steps: iterable of solver names ("nn", "gec", "sav", "chr", "bhk", "2opt", "3opt", "or_opt", "lk", "simulated_annealing", "tabu_search", "shuffle"); opts: {name: options} (optional).
+    A `simulated_annealing` stage draws from the stream of lk_seed (the pipeline's one seed) and runs sa_chains chains, keeping the best;
+    a `tabu_search` stage likewise, with tabu_chains chains.
     exact_walk: a `bhk` stage reads its route back by exact equality (bellman_karp.solve) instead of the reference's tolerance walk,
     whose result can fail validate_tour below.  init_tour: the seed of the first stage (city ids; default: that stage's own seeding)."""
     from . import (HeuristicOptions, LKOptions, bellman_karp, christofides, greedy_edge, lin_kernighan, nearest_neighbor, or_opt, savings, simulated_annealing,
-                   three_opt, two_opt, validate_tour)
+                   tabu_search, three_opt, two_opt, validate_tour)
     mods = {"nearest_neighbor": nearest_neighbor, "two_opt": two_opt, "three_opt": three_opt, "or_opt": or_opt,
             "lin_kernighan": lin_kernighan, "greedy_edge": greedy_edge, "savings": savings, "christofides": christofides,
             "bellman_karp": bellman_karp}
@@ -111,6 +114,8 @@ def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact
             sol = lin_kernighan.solve(problem, opts.get(step) or LKOptions(), None, init, ctx=ctx, seed=lk_seed)
         elif name == "simulated_annealing":
             sol = simulated_annealing.solve(problem, opts.get(step) or simulated_annealing.SAOptions(), None, init, ctx=ctx, seed=lk_seed, chains=sa_chains)
+        elif name == "tabu_search":
+            sol = tabu_search.solve(problem, opts.get(step) or HeuristicOptions(), None, init, ctx=ctx, seed=lk_seed, chains=tabu_chains)
         elif name == "bellman_karp":
             sol = mods[name].solve(problem, opts.get(step) or HeuristicOptions(), None, init, ctx=ctx, exact_walk=exact_walk)
         else:

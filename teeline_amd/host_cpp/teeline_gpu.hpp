@@ -962,8 +962,66 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const SAOptions &
 }
 }  // namespace simulated_annealing
 
+namespace tabu_search {  // tabu_search.rs:9-110
+// The chain is the reference's; its random draws (a pure function of seed, chain, epoch, attempt and slot) are this project's
+// specification (include/teeline_gpu.h).  chains > 1: chains 0 .. chains-1 of the seed at once, the best one returned (lowest cost,
+// then lowest chain).  With a progress callback the reference's messages — PathUpdate(start route, 0.0), PathUpdate(route, distance)
+// per new best, then Done (tabu_search.rs:28-30,42-47,59-61) — are replayed from the epochs of that chain (tl_tabu_search_trace_chain).
+inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
+                      uint64_t seed = 1, uint32_t chains = 1)
+{
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size();
+    const uint32_t epochs = (uint32_t)opts.epochs;
+    std::vector<uint32_t> init, out(n);
+    if (init_tour) init = problem.positions_of(*init_tour);
+    const uint32_t *ip = init_tour ? init.data() : nullptr;
+    float cost = 0.f;
+    tl_stats st{};
+    uint32_t chain = 0;
+    if (chains > 1) {
+        std::vector<uint32_t> outs((size_t)chains * n), moves(chains);
+        std::vector<float> costs(chains);
+        ctx.check(tl_tabu_search_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, chains, epochs, seed, outs.data(),
+                                            costs.data(), moves.data(), &chain, &st));
+        std::copy(outs.begin() + (size_t)chain * n, outs.begin() + (size_t)(chain + 1) * n, out.begin());
+        cost = costs[chain];
+        st.moves = moves[chain];
+        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
+    } else if (!(progress_tx && *progress_tx)) {
+        ctx.check(tl_tabu_search(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, epochs, seed, out.data(), &cost, &st));
+        return detail::finish(problem, out, cost, st, nullptr);
+    }
+    const uint32_t cap = epochs + 1u;
+    uint32_t len = 0;
+    std::vector<uint32_t> log((size_t)cap * 4, 0u);
+    ctx.check(tl_tabu_search_trace_chain(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, epochs, seed, chain, out.data(), &cost, &st, log.data(), cap, &len));
+    std::vector<uint32_t> pos(n);
+    for (uint32_t q = 0; q < n; ++q) pos[q] = init_tour ? init[q] : q;
+    std::vector<size_t> route(n);
+    auto send = [&](float d) {
+        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[pos[q]].id;
+        (*progress_tx)(ProgressKind::PathUpdate, route, d);
+    };
+    float best = or_opt::tour_length_f32(problem, xy, pos);
+    send(0.0f);
+    for (uint32_t m = 0; m < len && m < cap; ++m) {
+        std::reverse(pos.begin() + log[4 * m + 1], pos.begin() + log[4 * m + 2] + 1);  // swap_cities (route.rs:102-113)
+        float d;
+        std::memcpy(&d, &log[4 * m + 3], 4);
+        if (d < best) {
+            best = d;
+            send(d);
+        }
+    }
+    Solution s = detail::finish(problem, out, cost, st, nullptr);
+    (*progress_tx)(ProgressKind::Done, s.route_, cost);
+    return s;
+}
+}  // namespace tabu_search
+
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
-enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing };
+enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch };
 
 inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
 {
@@ -980,14 +1038,16 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
     else if (s == "bhk" || s == "bellman_karp") out = Solvers::BellmanKarp;
     else if (s == "simulated_annealing") out = Solvers::SimulatedAnnealing;  // (the alias `sa` stays refused, below: this build's annealing is a
                                                                               // seeded chain of its own specification, asked for by its long name)
+    else if (s == "tabu_search") out = Solvers::TabuSearch;  // (the alias `tabu` stays refused, below, as `sa` does)
     else {
         static const char *cpu_only[] = {"aco", "ant_colony", "branch_bound",
                                          "cs", "cuckoo_search", "fpa", "flower_pollination", "fourier", "ga", "genetic_algorithm", "gsa",
                                          "gravitational_search", "pso", "particle_swarm", "sa",
-                                         "som", "kohonen", "kohonen_som", "stochastic_hill", "tabu", "tabu_search"};
+                                         "som", "kohonen", "kohonen_som", "stochastic_hill", "tabu"};
         for (const char *c : cpu_only)
             if (s == c) {
                 why = "solver `" + s + "` is not accelerated by this build (nn, gec, sav, chr, bhk, 2opt, 3opt, or_opt, lk, shuffle are, and simulated_annealing under its long name)";
+                if (s == "tabu") why += "; the seeded tabu search of this build is `tabu_search`";
                 return false;
             }
         why = "unknown solver";  // FromStr's Err (mod.rs:588)
@@ -1009,6 +1069,7 @@ inline const char *solver_name(Solvers s)
         case Solvers::Christofides: return "christofides";
         case Solvers::BellmanKarp: return "bellman_karp";
         case Solvers::SimulatedAnnealing: return "simulated_annealing";
+        case Solvers::TabuSearch: return "tabu_search";
         default: return "shuffle";
     }
 }
@@ -1020,7 +1081,8 @@ struct StageOptions {
     int two_opt_mode = TL_MODE_REF_ORDER;
     simulated_annealing::SAOptions sa;
     uint32_t sa_chains = 1;  // an sa stage runs this many chains and keeps the best
-    uint64_t seed = 1;  // LK kicks, shuffle, SA draws
+    uint32_t tabu_chains = 1;  // a tabu_search stage likewise
+    uint64_t seed = 1;  // LK kicks, shuffle, SA and tabu draws
     const ProgressFn *progress = nullptr;  // handed to every stage's solve() (the reference's CLI passes None; teeline-qt a sender)
 };
 struct StageOutcome {  // :11-14
@@ -1082,6 +1144,7 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             case Solvers::Christofides: sol = christofides::solve(ctx, problem, o.heuristic, o.progress, init); break;
             case Solvers::BellmanKarp: sol = bellman_karp::solve(ctx, problem, o.heuristic, o.progress, init); break;
             case Solvers::SimulatedAnnealing: sol = simulated_annealing::solve(ctx, problem, o.sa, o.progress, init, o.seed, o.sa_chains); break;
+            case Solvers::TabuSearch: sol = tabu_search::solve(ctx, problem, o.heuristic, o.progress, init, o.seed, o.tabu_chains); break;
         }
         const auto t1 = std::chrono::steady_clock::now();
         const uint64_t ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();
