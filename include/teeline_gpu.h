@@ -605,6 +605,72 @@ uint64_t tl_tabu_draw(uint64_t seed, uint32_t chain, uint32_t n, uint32_t epoch,
 int tl_tabu_search_plan(uint32_t n, uint32_t count, int cus, int lds_bytes, uint64_t workspace_bytes, uint32_t flags, uint32_t *window, int *threads,
                         uint32_t *per_launch);
 
+/* ---- the genetic algorithm (src/tsp/genetic_algorithm.rs:16-336) ------------------------------ */
+/* The reference's algorithm with its quirks kept.  The population size is n.  fitness = 1 / tour_length in f32 (0 where the length
+ * is 0), tour_length as everywhere here (closing edge first, sequential f32).  Start population: with init_pos, individual 0 is that
+ * tour, individuals 1 .. max(n / 5, 1) - 1 are the tour after 2, 3 or 4 mutations, the rest are shuffles of city order; init_pos
+ * NULL: n shuffles.  A generation: stable sort by fitness, descending; the first min(n_elite, length) individuals are copied; then
+ * n / 2 - n_elite times two roulette selections over the SORTED population (r in [0, total), total and the running sum sequential
+ * f32 sums; the first i with r < up_to + f_i, else the last), one ordered crossover (child 1 has PARENT 2's segment from..=to, the
+ * other positions are filled from to + 1 on, wrapping, with parent 1's cities in the order met from to + 1; child 2 symmetrically),
+ * and each child mutated with probability mutation_probability — a reversal of from..=to that does NOT recompute the fitness.  So the
+ * population has n individuals in generation 0 and min(n_elite, length) + 2 max(0, n / 2 - n_elite) afterwards.  The result is the
+ * individual of maximum fitness, the LAST of equals; *out_cost is tour_length of its route, recomputed (it can differ from
+ * 1 / fitness after a mutation).  epochs = 0 returns the best of the start population.
+ * THE RANDOM STREAM IS THIS PROJECT'S SPECIFICATION, NOT THE REFERENCE'S (tests/_ga_oracle.py is the
+ * statement; csrc/ga_spec.h the text): tl_sim_anneal's stream indexed by a 64-bit event,
+ *   u(seed, run, event, slot) = mix(mix(seed + G (run + 1)) + G (32 event + slot + 1))              (tl_ga_draw)
+ * Pair p of generation g owns the events 4 (g n + p) + part: part 0 holds the crossover pair (slots 0 .. 21, attempt t on 2t,
+ * 2t + 1), the two roulette draws (22, 23) and the two mutation trials (24, 25: p > float(u >> 40) 2^-24); parts 1 and 2 hold the
+ * mutation pairs of child 1 and child 2.  Individual i of the start population owns the events 2^58 + i n + j: j = 0, slot 27 its
+ * mutation count 2 + position(u, 3); j = 1 + m, slots 0 .. 21 its mutation m; slot 26 of event j step j = n - 1 .. 1 of its
+ * Fisher-Yates pass, swap(a[j], a[position(u, j + 1)]).  No draw depends on an earlier one, so a generation's pairs are bred at once
+ * (csrc/genetic.hip: a rank launch and a breed launch per generation, one workgroup per pair, the populations 16-bit in the
+ * context's workspace, 4 n^2 bytes per run).
+ * Small n, as the reference's code behaves: n = 0: TL_ERR_REF_PANICS (best() of an empty population).  n = 1: there is no pair, so
+ * a generation keeps min(n_elite, 1) individuals — epochs = 0 or n_elite >= 1 return the one city at cost 0, epochs >= 1 with
+ * n_elite = 0 is TL_ERR_REF_PANICS (the population empties).  n = 2 and n = 3 run as any n does (one pair; the population of n = 3
+ * has 2 individuals after generation 0).  A population whose total fitness is not > 0 or not finite when a roulette is due (all
+ * cities in one place): TL_ERR_REF_PANICS (random_range on an empty range).
+ * n > tl_genetic_algorithm_max_n: TL_ERR_UNSUPPORTED, before anything of size n is read or allocated.  init_pos not a permutation:
+ * TL_ERR_BADARG.  mutation_probability not finite or outside [0, 1]: TL_ERR_BADARG (GAOptions::validate).  A context whose flags
+ * hold a bit no flag has: TL_ERR_UNSUPPORTED.  dm_packed as in tl_sim_anneal.
+ * tl_genetic_algorithm runs run 0.  stats (optional): sweeps = generations, candidates = children bred, moves = generations whose
+ * best fitness exceeds that of the population before, reversed = mutations applied.
+ * tl_genetic_algorithm_trace: the same plus 4 words per generation: the best individual's index in the new population, its fitness
+ * bits, the bits of its recomputed tour_length, the population's length.  *log_len counts the generations; the log holds the first
+ * log_cap.  route_log (optional, route_cap x n): the best route of the first route_cap generations — what a caller replays the
+ * reference's PathUpdate messages from (one per generation, then one more, then Done).  tl_genetic_algorithm_trace_run: the same
+ * for run `run` of the seed.
+ * tl_genetic_algorithm_population: runs first_run .. first_run + count - 1, each its own stream of draws, in one launch sequence
+ * (more runs than the workspace limit holds — tl_genetic_algorithm_plan's per_launch — go in further sequences).  init_pos: NULL or
+ * ONE tour, the initial tour of every run.  out_pos count x n, out_costs (optional) count entries, *best_index (optional) and its
+ * tie rule, count == 0: as tl_tabu_search_population.  Run c of any batch equals first_run = c, count = 1.
+ * Host-only queries (no context, no device): tl_ga_draw — the u64 above; tl_genetic_algorithm_plan — the runs one launch sequence
+ * holds, the threads of a breeding workgroup and the workspace bytes of min(count, per_launch) runs, for n cities on a device with
+ * cus compute units, lds_bytes of LDS per workgroup and workspace_bytes of workspace (outputs optional; all 0 where n is outside
+ * 1 .. the limit; the entries plan with 8 GiB).  tl_genetic_algorithm_max_n: the largest n (the breeding workgroup keeps 14 bytes
+ * per city in LDS).
+ * tl_ga_selftest_crossover: the DEVICE's ordered crossover on two given parents (permutations of 0..n-1, 2 <= n <= the limit,
+ * from <= to < n; else TL_ERR_BADARG): out1, out2 receive child 1 and child 2. */
+uint32_t tl_genetic_algorithm_max_n(const tl_ctx *ctx);
+int tl_genetic_algorithm(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t epochs,
+                         float mutation_probability, uint32_t n_elite, uint64_t seed, uint32_t *out_pos, float *out_cost, tl_stats *stats);
+int tl_genetic_algorithm_trace(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t epochs,
+                               float mutation_probability, uint32_t n_elite, uint64_t seed, uint32_t *out_pos, float *out_cost, tl_stats *stats,
+                               uint32_t *log, uint32_t log_cap, uint32_t *log_len, uint32_t *route_log, uint32_t route_cap);
+int tl_genetic_algorithm_trace_run(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t epochs,
+                                   float mutation_probability, uint32_t n_elite, uint64_t seed, uint32_t run, uint32_t *out_pos, float *out_cost,
+                                   tl_stats *stats, uint32_t *log, uint32_t log_cap, uint32_t *log_len, uint32_t *route_log, uint32_t route_cap);
+int tl_genetic_algorithm_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t first_run,
+                                    uint32_t count, uint32_t epochs, float mutation_probability, uint32_t n_elite, uint64_t seed, uint32_t *out_pos,
+                                    float *out_costs, uint32_t *best_index, tl_stats *stats);
+uint64_t tl_ga_draw(uint64_t seed, uint32_t run, uint64_t event, uint32_t slot);
+int tl_genetic_algorithm_plan(uint32_t n, uint32_t count, int cus, int lds_bytes, uint64_t workspace_bytes, uint32_t *per_launch, int *threads,
+                              uint64_t *workspace_needed);
+int tl_ga_selftest_crossover(tl_ctx *ctx, const uint32_t *p1, const uint32_t *p2, uint32_t n, uint32_t from, uint32_t to, uint32_t *out1,
+                             uint32_t *out2);
+
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts
  * first..first+count as above; seed ignored otherwise).  d_out_pos: count x n u32, d_out_cost: count f32,

@@ -115,6 +115,16 @@ unsafe extern "C" {
                                  first_chain: u32, count: u32, epochs: u32, seed: u64, out_pos: *mut u32, out_costs: *mut f32,
                                  out_moves: *mut u32, best_index: *mut u32, stats: *mut Stats) -> c_int;
     fn tl_tabu_draw(seed: u64, chain: u32, n: u32, epoch: u32, attempt: u32, slot: u32) -> u64;
+    fn tl_genetic_algorithm_max_n(ctx: *const TlCtx) -> u32;
+    fn tl_genetic_algorithm(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, epochs: u32, mutation_probability: f32,
+                            n_elite: u32, seed: u64, out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats) -> i32;
+    fn tl_genetic_algorithm_trace_run(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, epochs: u32,
+                                      mutation_probability: f32, n_elite: u32, seed: u64, run: u32, out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats,
+                                      log: *mut u32, log_cap: u32, log_len: *mut u32, route_log: *mut u32, route_cap: u32) -> i32;
+    fn tl_genetic_algorithm_population(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, first_run: u32, count: u32,
+                                       epochs: u32, mutation_probability: f32, n_elite: u32, seed: u64, out_pos: *mut u32, out_costs: *mut f32,
+                                       best_index: *mut u32, stats: *mut Stats) -> i32;
+    fn tl_ga_draw(seed: u64, run: u32, event: u64, slot: u32) -> u64;
     fn tl_nearest_neighbor(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, n_nearest: u32,
                            out_pos: *mut u32, out_cost: *mut f32) -> c_int;
     fn tl_greedy_edge(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
@@ -157,6 +167,12 @@ pub fn sa_draw(seed: u64, chain: u32, epoch: u32, slot: u32) -> u64 {
 pub fn tabu_draw(seed: u64, chain: u32, n: u32, epoch: u32, attempt: u32, slot: u32) -> u64 {
     // SAFETY: a pure function of its arguments.
     unsafe { tl_tabu_draw(seed, chain, n, epoch, attempt, slot) }
+}
+
+/// u(seed, run, event, slot): a draw of the genetic algorithm's stream (host only; the events are laid out in include/teeline_gpu.h).
+pub fn ga_draw(seed: u64, run: u32, event: u64, slot: u32) -> u64 {
+    // SAFETY: a pure function of its arguments.
+    unsafe { tl_ga_draw(seed, run, event, slot) }
 }
 
 /// The epochs `while epoch < epochs || temperature > min_temperature` runs (138 149 with the defaults); None beyond 2^32 - 1.
@@ -571,6 +587,69 @@ impl Context {
     pub fn tabu_search_lds_max_n(&self) -> u32 {
         // SAFETY: a plain query of a live context.
         unsafe { tl_tabu_search_lds_max_n(self.raw) }
+    }
+
+    /// `genetic_algorithm::solve` (genetic_algorithm.rs:16-336), run 0 of `seed`.  The algorithm is the reference's; its random draws are
+    /// the library's own specification (include/teeline_gpu.h).  (Written against the header; not compiled here: no Rust toolchain on
+    /// the build machine, see scripts/check_rust.sh.)
+    pub fn genetic_algorithm(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, epochs: u32, mutation_probability: f32, n_elite: u32,
+                             seed: u64) -> Result<Tour, Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        // SAFETY: as in two_opt.
+        let rc = unsafe {
+            tl_genetic_algorithm(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), epochs, mutation_probability, n_elite, seed, t.pos.as_mut_ptr(),
+                                 &mut t.cost, &mut t.stats)
+        };
+        self.check(rc).map(|_| t)
+    }
+
+    /// Run `run` of `seed` with every generation `[best index, fitness bits, cost bits, population length]` and its best route, from which
+    /// the reference's PathUpdate messages (one per generation, then one more) are replayed.
+    pub fn genetic_algorithm_trace(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, epochs: u32, mutation_probability: f32,
+                                   n_elite: u32, seed: u64, run: u32) -> Result<(Tour, Vec<[u32; 4]>, Vec<u32>), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        let mut log = vec![[0u32; 4]; epochs.max(1) as usize];
+        let mut routes = vec![0u32; epochs.max(1) as usize * n as usize];
+        let mut len: u32 = 0;
+        // SAFETY: as in two_opt; log holds `epochs` entries of 4 words, routes `epochs` x n.
+        let rc = unsafe {
+            tl_genetic_algorithm_trace_run(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), epochs, mutation_probability, n_elite, seed, run,
+                                           t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats, log.as_mut_ptr() as *mut u32, epochs, &mut len, routes.as_mut_ptr(),
+                                           epochs)
+        };
+        self.check(rc)?;
+        log.truncate(len.min(epochs) as usize);
+        routes.truncate(len.min(epochs) as usize * n as usize);
+        Ok((t, log, routes))
+    }
+
+    /// Runs `first_run .. first_run + count` of `seed` at once, every run with `init_pos` as its initial tour (or none); the best routes
+    /// and the index of the best one (lowest cost, then lowest run).
+    pub fn genetic_algorithm_population(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, first_run: u32, count: u32, epochs: u32,
+                                        mutation_probability: f32, n_elite: u32, seed: u64) -> Result<(Vec<Tour>, u32), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let mut pos = vec![0u32; n as usize * count as usize];
+        let mut costs = vec![0f32; count as usize];
+        let (mut best, mut st) = (0u32, Stats::default());
+        // SAFETY: as in two_opt; the output arrays hold count x n and count entries.
+        let rc = unsafe {
+            tl_genetic_algorithm_population(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), first_run, count, epochs, mutation_probability,
+                                            n_elite, seed, pos.as_mut_ptr(), costs.as_mut_ptr(), &mut best, &mut st)
+        };
+        self.check(rc)?;
+        let tours = (0..count as usize).map(|k| Tour { pos: pos[k * n as usize..(k + 1) * n as usize].to_vec(), cost: costs[k], stats: st }).collect();
+        Ok((tours, best))
+    }
+
+    /// Largest n of `genetic_algorithm` (a breeding workgroup keeps 14 bytes per city in LDS).
+    pub fn genetic_algorithm_max_n(&self) -> u32 {
+        // SAFETY: a plain query of a live context.
+        unsafe { tl_genetic_algorithm_max_n(self.raw) }
     }
 
     /// `or_opt::solve` (or_opt.rs:18-74).

@@ -61,6 +61,8 @@ SYMBOLS = [
     "tl_sa_draw", "tl_sa_schedule_epochs", "tl_sa_selftest_accept",
     "tl_tabu_search", "tl_tabu_search_trace", "tl_tabu_search_trace_chain", "tl_tabu_search_population", "tl_tabu_search_lds_max_n", "tl_tabu_search_plan",
     "tl_tabu_draw",
+    "tl_genetic_algorithm", "tl_genetic_algorithm_trace", "tl_genetic_algorithm_trace_run", "tl_genetic_algorithm_population", "tl_genetic_algorithm_max_n",
+    "tl_genetic_algorithm_plan", "tl_ga_draw", "tl_ga_selftest_crossover",
 ]
 
 
@@ -186,5 +188,16 @@ def load():
     L.tl_tabu_draw.argtypes = [u64, u32, u32, u32, u32, u32]
     L.tl_tabu_draw.restype = u64
     L.tl_tabu_search_plan.argtypes = [u32, u32, i32, i32, u64, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
+    L.tl_genetic_algorithm_max_n.argtypes = [vp]
+    L.tl_genetic_algorithm_max_n.restype = u32
+    L.tl_genetic_algorithm.argtypes = [vp, vp, u32, vp, vp, u32, C.c_float, u32, u64, vp, f32p, C.POINTER(TlStats)]
+    L.tl_genetic_algorithm_trace.argtypes = [vp, vp, u32, vp, vp, u32, C.c_float, u32, u64, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32), vp, u32]
+    L.tl_genetic_algorithm_trace_run.argtypes = [vp, vp, u32, vp, vp, u32, C.c_float, u32, u64, u32, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32), vp,
+                                                 u32]
+    L.tl_genetic_algorithm_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, C.c_float, u32, u64, vp, vp, C.POINTER(u32), C.POINTER(TlStats)]
+    L.tl_ga_draw.argtypes = [u64, u32, u64, u32]
+    L.tl_ga_draw.restype = u64
+    L.tl_genetic_algorithm_plan.argtypes = [u32, u32, i32, i32, u64, C.POINTER(u32), C.POINTER(i32), C.POINTER(u64)]
+    L.tl_ga_selftest_crossover.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp]
     _lib = L
     return L

@@ -356,8 +356,42 @@ size_t tabu_search_lds_bytes(uint32_t n);    // LDS of one chain's workgroup (ei
 uint32_t tabu_search_lds_max_n(int lds_budget);
 hipError_t launch_tabu_search(const TabuArgs &A, uint32_t count, int threads, hipStream_t s);
 
+// genetic.hip — the genetic algorithm, the run a grid dimension, two launches per generation
+struct GaArgs {
+    const float2 *xy;       // n cities, city order (coordinate form)
+    const float *dm_full;   // the matrix expanded to row-major n x n, or nullptr
+    const uint32_t *init;   // the initial tour (from_cities_seeded), or nullptr (from_cities)
+    uint16_t *pop[2];       // [runs][pop_stride] the populations, current and next: up to n routes of n cities each
+    float *fit[2];          // [runs][n] their fitness values
+    uint32_t *order;        // [runs][n] the individuals of the current population, sorted (stable, fitness descending)
+    float *prefix;          // [runs][n + 1] the roulette's running sum over the sorted population
+    uint32_t *state;        // [runs][8] best fitness bits, improved generations, mutations, status, best index
+    uint32_t *out_pos;      // [runs][n] the best route of the last population
+    float *out_cost;        // [runs] its tour_length
+    uint32_t *log;          // optional: [log_cap][4] best index, fitness bits, tour_length bits, population length per generation of run 0
+    uint32_t *route_log;    // optional: [route_cap][n] the best route of the first generations of run 0
+    uint64_t seed;
+    uint64_t pop_stride;    // elements between two runs' populations (>= n * n)
+    uint32_t log_cap, route_cap;
+    uint32_t first_run;     // stream id of the launch's run 0
+    uint32_t n, n_elite;
+    float p_mut;
+    uint32_t generation;    // breed: the generation being bred; rank: the generations bred so far
+    uint32_t len;           // the length of the current population
+    uint32_t src;           // which of pop / fit is the current one
+    uint32_t last;          // rank: no generation follows — write the result
+};
+size_t genetic_lds_bytes(uint32_t n);        // LDS of one workgroup (either form)
+uint32_t genetic_max_n(int lds_budget);
+int genetic_threads(uint32_t n);
+hipError_t launch_ga_init(const GaArgs &A, uint32_t runs, hipStream_t s);
+hipError_t launch_ga_rank(const GaArgs &A, uint32_t runs, hipStream_t s);
+hipError_t launch_ga_breed(const GaArgs &A, uint32_t runs, uint32_t next_len, hipStream_t s);
+hipError_t launch_ga_selftest_crossover(const uint16_t *p1, const uint16_t *p2, uint32_t n, uint32_t from, uint32_t to, uint16_t *out1, uint16_t *out2,
+                                        hipStream_t s);
+
 // lk.hip
-struct LkState {             // device-side state machine of the multi-CU LK variant
+struct LkState {           // device-side state machine of the multi-CU LK variant
     uint32_t key;            // min pair index with a valid chain in the current scan (0xFFFFFFFF: none)
     uint32_t finished;
     uint32_t stage;          // 0: initial lk_pass, 1: ILS epochs

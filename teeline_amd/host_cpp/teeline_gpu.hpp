@@ -1020,8 +1020,67 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOp
 }
 }  // namespace tabu_search
 
+namespace genetic_algorithm {  // genetic_algorithm.rs:16-336
+struct GAOptions {  // mod.rs:815-846
+    HeuristicOptions heuristic;
+    float mutation_probability = 0.001f;
+    size_t n_elite = 3;
+    std::string validate() const
+    {
+        if (!std::isfinite(mutation_probability) || mutation_probability < 0.0f || mutation_probability > 1.0f)
+            return "mutation_probability must be in [0, 1] (got " + std::to_string(mutation_probability) + ")";
+        return "";
+    }
+};
+// The algorithm is the reference's; its random draws (a pure function of seed, run, generation, pair or individual, and role) are
+// this project's specification (include/teeline_gpu.h).  runs > 1: runs 0 .. runs-1 of the seed at once, the best one returned
+// (lowest cost, then lowest run).  With a progress callback the reference's messages — one PathUpdate(best route, its tour_length)
+// per generation, one more, then Done (genetic_algorithm.rs:33-40,91-98) — are replayed from that run's trace and route log.
+inline Solution solve(Context &ctx, const TspProblem &problem, const GAOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
+                      uint64_t seed = 1, uint32_t runs = 1)
+{
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size();
+    const uint32_t epochs = (uint32_t)opts.heuristic.epochs, e = (uint32_t)std::min<size_t>(opts.n_elite, 0xFFFFFFFFu);
+    const float p = opts.mutation_probability;
+    std::vector<uint32_t> init, out(n);
+    if (init_tour) init = problem.positions_of(*init_tour);
+    const uint32_t *ip = init_tour ? init.data() : nullptr;
+    float cost = 0.f;
+    tl_stats st{};
+    uint32_t run = 0;
+    if (runs > 1) {
+        std::vector<uint32_t> outs((size_t)runs * n);
+        std::vector<float> costs(runs);
+        ctx.check(tl_genetic_algorithm_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, 0u, runs, epochs, p, e, seed, outs.data(), costs.data(),
+                                                  &run, &st));
+        std::copy(outs.begin() + (size_t)run * n, outs.begin() + (size_t)(run + 1) * n, out.begin());
+        cost = costs[run];
+        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
+    } else if (!(progress_tx && *progress_tx)) {
+        ctx.check(tl_genetic_algorithm(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, epochs, p, e, seed, out.data(), &cost, &st));
+        return detail::finish(problem, out, cost, st, nullptr);
+    }
+    uint32_t len = 0;
+    std::vector<uint32_t> log((size_t)std::max(epochs, 1u) * 4, 0u), routes((size_t)std::max(epochs, 1u) * n, 0u);
+    ctx.check(tl_genetic_algorithm_trace_run(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, epochs, p, e, seed, run, out.data(), &cost, &st, log.data(),
+                                             epochs, &len, routes.data(), epochs));
+    std::vector<size_t> route(n);
+    for (uint32_t g = 0; g < len && g < epochs; ++g) {
+        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[routes[(size_t)g * n + q]].id;
+        float d;
+        std::memcpy(&d, &log[4 * (size_t)g + 2], 4);
+        (*progress_tx)(ProgressKind::PathUpdate, route, d);
+    }
+    Solution s = detail::finish(problem, out, cost, st, nullptr);
+    (*progress_tx)(ProgressKind::PathUpdate, s.route_, cost);
+    (*progress_tx)(ProgressKind::Done, s.route_, cost);
+    return s;
+}
+}  // namespace genetic_algorithm
+
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
-enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch };
+enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm };
 
 inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
 {
@@ -1039,15 +1098,17 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
     else if (s == "simulated_annealing") out = Solvers::SimulatedAnnealing;  // (the alias `sa` stays refused, below: this build's annealing is a
                                                                               // seeded chain of its own specification, asked for by its long name)
     else if (s == "tabu_search") out = Solvers::TabuSearch;  // (the alias `tabu` stays refused, below, as `sa` does)
+    else if (s == "genetic_algorithm") out = Solvers::GeneticAlgorithm;  // (the alias `ga` likewise)
     else {
         static const char *cpu_only[] = {"aco", "ant_colony", "branch_bound",
-                                         "cs", "cuckoo_search", "fpa", "flower_pollination", "fourier", "ga", "genetic_algorithm", "gsa",
+                                         "cs", "cuckoo_search", "fpa", "flower_pollination", "fourier", "ga", "gsa",
                                          "gravitational_search", "pso", "particle_swarm", "sa",
                                          "som", "kohonen", "kohonen_som", "stochastic_hill", "tabu"};
         for (const char *c : cpu_only)
             if (s == c) {
                 why = "solver `" + s + "` is not accelerated by this build (nn, gec, sav, chr, bhk, 2opt, 3opt, or_opt, lk, shuffle are, and simulated_annealing under its long name)";
                 if (s == "tabu") why += "; the seeded tabu search of this build is `tabu_search`";
+                if (s == "ga") why += "; the seeded genetic algorithm of this build is `genetic_algorithm`";
                 return false;
             }
         why = "unknown solver";  // FromStr's Err (mod.rs:588)
@@ -1070,6 +1131,7 @@ inline const char *solver_name(Solvers s)
         case Solvers::BellmanKarp: return "bellman_karp";
         case Solvers::SimulatedAnnealing: return "simulated_annealing";
         case Solvers::TabuSearch: return "tabu_search";
+        case Solvers::GeneticAlgorithm: return "genetic_algorithm";
         default: return "shuffle";
     }
 }
@@ -1082,7 +1144,9 @@ struct StageOptions {
     simulated_annealing::SAOptions sa;
     uint32_t sa_chains = 1;  // an sa stage runs this many chains and keeps the best
     uint32_t tabu_chains = 1;  // a tabu_search stage likewise
-    uint64_t seed = 1;  // LK kicks, shuffle, SA and tabu draws
+    genetic_algorithm::GAOptions ga;
+    uint32_t ga_runs = 1;  // a genetic_algorithm stage breeds this many runs and keeps the best
+    uint64_t seed = 1;  // LK kicks, shuffle, SA, tabu and GA draws
     const ProgressFn *progress = nullptr;  // handed to every stage's solve() (the reference's CLI passes None; teeline-qt a sender)
 };
 struct StageOutcome {  // :11-14
@@ -1145,6 +1209,7 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             case Solvers::BellmanKarp: sol = bellman_karp::solve(ctx, problem, o.heuristic, o.progress, init); break;
             case Solvers::SimulatedAnnealing: sol = simulated_annealing::solve(ctx, problem, o.sa, o.progress, init, o.seed, o.sa_chains); break;
             case Solvers::TabuSearch: sol = tabu_search::solve(ctx, problem, o.heuristic, o.progress, init, o.seed, o.tabu_chains); break;
+            case Solvers::GeneticAlgorithm: sol = genetic_algorithm::solve(ctx, problem, o.ga, o.progress, init, o.seed, o.ga_runs); break;
         }
         const auto t1 = std::chrono::steady_clock::now();
         const uint64_t ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();

@@ -11,6 +11,9 @@
 //               --chains K (own flag: K chains of the seed at once, the best kept); `solve simulated_annealing` alone is pipeline(shuffle, simulated_annealing) (mod.rs:144-157)
 //     tabu     : tabu_search (long name only: `tabu` stays refused) runs --epochs + 1 epochs of seeded draws (--seed); --tabu-chains K (own flag:
 //               K chains of the seed at once, the best kept); `solve tabu_search` alone is pipeline(nn, tabu_search) (mod.rs:129-139)
+//     genetic  : genetic_algorithm (long name only: `ga` stays refused) breeds --epochs generations of seeded draws (--seed) with
+//               --mutation-probability P and --n-elite N (GAOptions, mod.rs:815-846); --ga-runs K (own flag: K runs of the seed at once,
+//               the best kept); `solve genetic_algorithm` alone is pipeline(shuffle, genetic_algorithm) (mod.rs:144-157, 2152)
 //     solve   : 2opt / 3opt / or_opt / lk auto-expand to pipeline(nn, solver) unless --no-seed (main.rs:387-397, mod.rs:129-139);
 //               gec (greedy_edge), sav (savings) and chr (christofides) are constructions and run alone; so does bhk (bellman_karp),
 //               the exact solver (n <= 26, mod.rs:2137) — as a later pipeline stage it ignores its seed
@@ -48,11 +51,12 @@ struct Args {
 {
     if (why) std::fprintf(stderr, "error: %s\n", why);
     std::fprintf(stderr,
-                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
+                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|genetic_algorithm|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
                  "                         [--optimal-tour FILE] [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P]\n"
                  "                         [--n_nearest K] [--max-depth D] [--seed S] [--best-sweep] [--device N] [--stats]\n"
                  "                         [--progress-digest] [--exact-walk]\n"
                  "                         [--cooling-rate C] [--min-temperature LO] [--max-temperature HI] [--chains K] [--tabu-chains K]\n"
+                 "                         [--mutation-probability P] [--n-elite N] [--ga-runs K]\n"
                  "       teeline-gpu pipeline --steps=nn,2opt,... | --steps=greedy_edge,2opt,... | --steps=savings,2opt,... | --steps=christofides,lk,... [-i FILE] [options as above]\n"
                  "       teeline-gpu solvers [--short]\n");
     std::exit(2);  // clap's usage-error exit code
@@ -105,11 +109,14 @@ Args parse(int argc, char **argv)
         else if (s == "--output-format") a.output_format = val();
         else if (s == "--optimal-tour") a.optimal_tour = val();
         else if (s == "--distance-type") a.distance_type = val();
-        else if (s == "--epochs") a.opt.heuristic.epochs = a.opt.lk.heuristic.epochs = a.opt.sa.heuristic.epochs = parse_usize(s, val());
+        else if (s == "--epochs") a.opt.heuristic.epochs = a.opt.lk.heuristic.epochs = a.opt.sa.heuristic.epochs = a.opt.ga.heuristic.epochs = parse_usize(s, val());
         else if (s == "--cooling-rate" || s == "--cooling_rate") a.opt.sa.cooling_rate = std::stof(val());
         else if (s == "--min-temperature" || s == "--min_temperature") a.opt.sa.min_temperature = std::stof(val());
         else if (s == "--max-temperature" || s == "--max_temperature") a.opt.sa.max_temperature = std::stof(val());
         else if (s == "--tabu-chains" || s == "--tabu_chains") a.opt.tabu_chains = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
+        else if (s == "--mutation-probability" || s == "--mutation_probability") a.opt.ga.mutation_probability = std::stof(val());
+        else if (s == "--n-elite" || s == "--n_elite") a.opt.ga.n_elite = parse_usize(s, val());
+        else if (s == "--ga-runs" || s == "--ga_runs") a.opt.ga_runs = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--chains") a.opt.sa_chains = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--platoo_epochs" || s == "--platoo-epochs") a.opt.heuristic.platoo_epochs = a.opt.lk.heuristic.platoo_epochs = parse_usize(s, val());
         else if (s == "--n_nearest" || s == "--n-nearest") a.opt.heuristic.n_nearest = a.opt.lk.heuristic.n_nearest = parse_usize(s, val());
@@ -138,6 +145,13 @@ Args parse(int argc, char **argv)
     }
     {   // SAOptions::from_cli validates (mod.rs:708-742)
         const std::string why = a.opt.sa.validate();
+        if (!why.empty()) {
+            std::fprintf(stderr, "error: %s\n", why.c_str());
+            std::exit(1);
+        }
+    }
+    {   // GAOptions::validate (mod.rs:833-846)
+        const std::string why = a.opt.ga.validate();
         if (!why.empty()) {
             std::fprintf(stderr, "error: %s\n", why.c_str());
             std::exit(1);
@@ -238,7 +252,7 @@ int run(int argc, char **argv)
                 // auto_expand_with_nn (mod.rs:129-139): deterministic local searches are seeded with a nearest-neighbour stage
                 const bool expand = s == Solvers::TwoOpt || s == Solvers::ThreeOpt || s == Solvers::LinKernighan || s == Solvers::OrOpt || s == Solvers::TabuSearch;
                 if (!a.no_seed && expand) stages = {Solvers::NearestNeighbor, s};
-                else if (!a.no_seed && s == Solvers::SimulatedAnnealing) stages = {Solvers::RandomShuffle, s};  // mod.rs:144-157
+                else if (!a.no_seed && (s == Solvers::SimulatedAnnealing || s == Solvers::GeneticAlgorithm)) stages = {Solvers::RandomShuffle, s};  // mod.rs:144-157
                 else stages = {s};
             }
         } else {
