@@ -9,7 +9,20 @@ using namespace tl;
 using namespace tlapi;
 
 static constexpr uint64_t kSaMaxEpochs = 0xFFFFFFFFull;
-static constexpr uint32_t kSaChunk = 1u << 22;  // epochs per launch: the temperature table goes up in pieces of 16 MB
+static constexpr uint32_t kSaChunkDefault = 1u << 22;  // epochs per launch: the temperature table goes up in pieces of 16 MB
+
+// The piece length of a schedule.  Tuning builds only (python -m teeline_amd.build --tune) read TL_SA_CHUNK (1 .. 2^22), so that tests
+// reach the second piece with a short schedule: the product library never reads the environment.
+static inline uint32_t sa_chunk()
+{
+#ifdef TL_TUNE
+    if (const char *e = getenv("TL_SA_CHUNK")) {
+        const long v = atol(e);
+        if (v >= 1 && v <= (long)kSaChunkDefault) return (uint32_t)v;
+    }
+#endif
+    return kSaChunkDefault;
+}
 static const tl_sa_opts kSaDefaults = {10000u, 1e-4f, 1e-3f, 1000.0f};  // mod.rs:598-608, 697-705
 
 // SAOptions::validate (mod.rs:707-741): the first complaint, or nullptr
@@ -119,7 +132,8 @@ static int sa_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, const
     int rc;
     const size_t words = (size_t)count * n, starts = init_count ? init_count : 1u;
     const uint32_t dev_log_cap = move_log ? log_cap : 0u;
-    const size_t table_cap = total < kSaChunk ? (size_t)total : kSaChunk;
+    const uint32_t chunk = sa_chunk();
+    const size_t table_cap = total < chunk ? (size_t)total : chunk;
     if ((rc = ensure(c, c->init, starts * n * 4)) || (rc = ensure(c, c->out_pos, words * 4)) || (rc = ensure(c, c->out_cost, (size_t)count * 4)) ||
         (rc = ensure(c, c->misc, (size_t)count * 16)) || (rc = ensure(c, c->work, up256((table_cap ? table_cap : 1u) * 4) + (size_t)(dev_log_cap ? dev_log_cap : 1u) * 16)))
         return rc;
@@ -158,7 +172,7 @@ static int sa_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, const
     bool first = true;
     float T = o.max_temperature;
     do {  // (an empty schedule is one launch of no epochs: the start tours and their lengths come back)
-        const uint64_t end = total - done < kSaChunk ? total : done + kSaChunk;
+        const uint64_t end = total - done < chunk ? total : done + chunk;
         if (end > done) {  // the temperatures of [done, end), continued from where the last piece ended
             for (uint64_t e = done; e < end; ++e) {
                 table[e - done] = T;

@@ -41,3 +41,32 @@ def check_conditions(name, n, epochs, trace, cnt):
         assert cnt["children"] // 4 < cnt["mutations"] < 3 * cnt["children"] // 4, (name, cnt)
     if name in ("berlin52", "synth65_init"):  # a mutated best: its recomputed length is not 1 / fitness
         assert any(np.float32(1.0) / f != c for _b, f, c, _l in trace), name
+
+
+# ---------------------------------------------------------------- past two compaction rounds, past one thread per individual
+CUS, LDS_BYTES, WORK = K.CUS, K.LDS_BYTES, 8 << 30  # the device the sizes below were chosen for; the GPU tests read theirs from device_info
+CROSS_SIZES = (511, 512, 513, 769, 1025, 4097)      # and tl_genetic_algorithm_max_n
+WIDE = dict(n=520, epochs=2, p=0.5, e=3, seed=520)   # three compaction rounds per child on 256 threads
+RANK = dict(n=1030, epochs=1, p=0.5, e=3, seed=1030)  # more individuals than the 1024 threads that rank them; the next generation has n - 3
+
+
+def instance(n):
+    return K.synth(n, 700 + n)
+
+
+def crossover_segments(n):
+    """(from, to) of the crossover self-test at n > 8: the wave-edge list the small sizes use, segments that start or end on the
+    workgroup's widths and their neighbours, the whole route and single positions at both ends"""
+    pairs = [(0, n - 1), (0, 0), (n - 1, n - 1), (0, 1), (n - 2, n - 1), (0, n - 2), (1, n - 1), (n // 2, n // 2), (1, n - 2), (62, 64), (63, 63), (0, 63)]
+    for v in (255, 256, 257, 511, 512):
+        pairs += [(v, n - 1), (0, v), (v, v), (v, v + 300), (v - 200, v), (1, v), (v, n - 2)]
+    out = []
+    for lo, hi in pairs:
+        if 0 <= lo <= hi < n and (lo, hi) not in out:
+            out.append((lo, hi))
+    return out
+
+
+def rounds(n, threads):
+    """trips of the compaction loop (one per `threads` positions): the two sets of wave counts alternate, set 0 is used again in the third"""
+    return -(-n // threads)

@@ -47,21 +47,30 @@ class TabuList:
     """tabu_search.rs:87-110: capacity routes, newest first; a full list drops its oldest"""
 
     def __init__(self, capacity):
-        self.capacity, self.items = capacity, deque()
+        self.capacity, self.items, self.added = capacity, deque(), 0
 
     def add(self, route):
         if len(self.items) >= self.capacity:
             self.items.pop()
         self.items.appendleft(np.asarray(route, dtype=np.int64).tobytes())
+        self.added += 1
 
     def contains(self, route):
         return np.asarray(route, dtype=np.int64).tobytes() in self.items
 
+    def ring_indices(self, route):
+        """where the listed copies of `route` sit in a ring that writes its k-th route to slot k mod capacity (the device's layout),
+        ascending; empty when the route is not listed"""
+        b = np.asarray(route, dtype=np.int64).tobytes()
+        return sorted((self.added - 1 - i) % self.capacity for i, r in enumerate(self.items) if r == b)
 
-def solve(xy, packed, n, init=None, *, epochs, seed=1, chain=0):
+
+def solve(xy, packed, n, init=None, *, epochs, seed=1, chain=0, record=None):
     """One chain.  Returns (best tour, its cost, log, counters): log = [(taken attempt, from, to, cost)] of every epoch; counters =
     hits (improving candidates the list refused), forced (epochs that took attempt n), bests (new bests), candidates (the sum of
-    taken attempt + 1), reversed (elements moved), deepest (the largest taken attempt)."""
+    taken attempt + 1), reversed (elements moved), deepest (the largest taken attempt).  record: a dict that receives what the
+    list did — "refusals" = [(epoch, attempt, ring indices of the listed copies that matched)], "list_len" = the list's length at
+    every epoch, "checked" = per epoch the improving candidates looked up in the list (refused ones included)."""
     if n < 2:
         raise ValueError("reference panics: n_items must be bigger than 2")
     if epochs == 0:
@@ -74,16 +83,21 @@ def solve(xy, packed, n, init=None, *, epochs, seed=1, chain=0):
     tabu.add(best)
     best_distance = tour_length(d, u)
     log, cnt = [], dict(hits=0, forced=0, bests=0, candidates=0, reversed=0, deepest=0)
+    refusals, list_len, checked = [], [], []
     with np.errstate(all="ignore"):
         for e in range(epochs + 1):
             local = tour_length(d, u)
             taken = None
+            list_len.append(len(tabu.items))
+            checked.append(0)
             for a0 in range(0, n, CHUNK):
                 pairs = [pair_from_key(key, event(e, n, a), n) for a in range(a0, min(n, a0 + CHUNK))]
                 cands, costs = candidate_costs(d, u, pairs)
                 for r in np.flatnonzero(costs < local):
+                    checked[-1] += 1
                     if tabu.contains(cands[r]):
                         cnt["hits"] += 1
+                        refusals.append((e, a0 + int(r), tuple(tabu.ring_indices(cands[r]))))
                         continue
                     taken = (a0 + int(r), pairs[r], cands[r].copy(), costs[r])
                     break
@@ -104,16 +118,26 @@ def solve(xy, packed, n, init=None, *, epochs, seed=1, chain=0):
             cnt["candidates"] += a + 1
             cnt["reversed"] += hi - lo + 1
             cnt["deepest"] = max(cnt["deepest"], a)
+    if record is not None:
+        record.update(refusals=refusals, list_len=list_len, checked=checked)
     return best.astype(np.uint32), np.float32(best_distance), log, cnt
 
 
 _cache = {}
+_records = {}
 
 
 def solve_cached(key, *args, **kw):
     """solve() once per process and key; the results are shared between tests and must not be written to"""
     if key not in _cache:
-        tour, cost, log, cnt = solve(*args, **kw)
+        rec = {}
+        tour, cost, log, cnt = solve(*args, record=rec, **kw)
         tour.setflags(write=False)
         _cache[key] = (tour, cost, tuple(log), dict(cnt))
+        _records[key] = rec
     return _cache[key]
+
+
+def record_of(key):
+    """the list's record (solve's `record`) of a chain that solve_cached has computed under `key`"""
+    return _records[key]

@@ -309,3 +309,26 @@ def test_header_and_bindings_agree_on_the_symbols(lib):
     for sym in ("tl_genetic_algorithm", "tl_genetic_algorithm_trace", "tl_genetic_algorithm_trace_run", "tl_genetic_algorithm_population",
                 "tl_genetic_algorithm_max_n", "tl_genetic_algorithm_plan", "tl_ga_draw", "tl_ga_selftest_crossover"):
         assert sym in _capi.SYMBOLS and re.search(rf"\b{sym}\(", text) and hasattr(lib, sym)
+
+
+# ---------------------------------------------------------------- the conditions of the cases past two rounds / one thread each
+def test_wide_and_rank_cases_are_what_they_claim(lib):
+    per, t, need = C.c_uint32(), C.c_int(), C.c_uint64()
+    w, r = GC.WIDE, GC.RANK
+    assert lib.tl_genetic_algorithm_plan(w["n"], 1, GC.CUS, GC.LDS_BYTES, GC.WORK, C.byref(per), C.byref(t), C.byref(need)) == 0
+    assert GC.rounds(w["n"], t.value) >= 3 and all(GC.rounds(n, t.value) >= 2 for n in GC.CROSS_SIZES) and GC.rounds(GC.CROSS_SIZES[2], t.value) == 3
+    for n in GC.CROSS_SIZES:  # every boundary the segments are meant to sit on is there
+        segs = GC.crossover_segments(n)
+        assert {(0, n - 1), (0, 0), (n - 1, n - 1)} <= set(segs) and all(0 <= lo <= hi < n for lo, hi in segs)
+        for v in (255, 256, 257, 511, 512):
+            if v < n:
+                assert any(lo == v for lo, _hi in segs) and any(hi == v for _lo, hi in segs), (n, v)
+    for init in (None, GC.start_tour(w["n"], w["n"])):
+        _tour, _cost, trace, cnt = GA.solve_cached(("wide", init is not None), GC.instance(w["n"]), None, w["n"], init, epochs=w["epochs"],
+                                                   mutation_probability=w["p"], n_elite=w["e"], seed=w["seed"])
+        assert cnt["children"] == 2 * (w["n"] // 2 - w["e"]) * w["epochs"] and 0 < cnt["mutations"] < cnt["children"]
+        assert [ln for *_x, ln in trace] == [w["e"] + 2 * (w["n"] // 2 - w["e"])] * w["epochs"]
+    # the first rank sees n > 1024 individuals, the second the next generation's n - 3
+    _tour, _cost, trace, cnt = GA.solve_cached("rank", GC.instance(r["n"]), None, r["n"], None, epochs=r["epochs"], mutation_probability=r["p"],
+                                               n_elite=r["e"], seed=r["seed"])
+    assert r["n"] > 1024 and [ln for *_x, ln in trace] == [r["n"] - 3] and r["n"] - 3 > 1024 and cnt["children"] == r["n"] - 6

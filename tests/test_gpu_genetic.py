@@ -99,11 +99,15 @@ def test_selftest_crossover_recorded_examples(ctx):
         assert [v + z for v in g1] == c1 and [v + z for v in g2] == c2
 
 
+def _random_parents(n):
+    rng = np.random.default_rng(n)
+    return [int(v) for v in rng.permutation(n)], [int(v) for v in rng.permutation(n)]
+
+
 @pytest.mark.parametrize("n", [2, 3, 8, 63, 64, 65, 129, 257])
 def test_selftest_crossover_random_parents(ctx, n):
     """n = 63 .. 65, 129, 257: the wave and workgroup edges of the compaction"""
-    rng = np.random.default_rng(n)
-    p1, p2 = [int(v) for v in rng.permutation(n)], [int(v) for v in rng.permutation(n)]
+    p1, p2 = _random_parents(n)
     if n <= 8:
         pairs = [(lo, hi) for lo in range(n) for hi in range(lo, n)]
     else:
@@ -117,6 +121,19 @@ def test_selftest_crossover_random_parents(ctx, n):
     a = np.ascontiguousarray(p1, dtype=np.uint32)
     assert ctx.lib.tl_ga_selftest_crossover(ctx.handle, _vp(a), _vp(a), n, 1, 0, _vp(o), _vp(o)) == _capi.TL_ERR_BADARG
     assert ctx.lib.tl_ga_selftest_crossover(ctx.handle, _vp(a), _vp(a), n, 0, n, _vp(o), _vp(o)) == _capi.TL_ERR_BADARG
+
+
+@pytest.mark.parametrize("n", GC.CROSS_SIZES + ("top",))
+def test_selftest_crossover_past_two_rounds(ctx, n):
+    """n > 512 on 256 threads: the compaction's third and later rounds use the first set of wave counts again; n = 511 .. 513 its edge;
+    the largest n the algorithm takes.  Segments on the workgroup's widths (GC.crossover_segments)."""
+    if n == "top":
+        n = ctx.lib.tl_genetic_algorithm_max_n(ctx.handle)
+        assert 4097 < n <= 65535
+    assert plan(ctx, n)[1] == 256
+    p1, p2 = _random_parents(n)
+    for lo, hi in GC.crossover_segments(n):
+        assert device_crossover(ctx, p1, p2, lo, hi) == GA.crossover(p1, p2, lo, hi), (n, lo, hi)
 
 
 # ---------------------------------------------------------------- whole runs
@@ -148,6 +165,38 @@ def test_beyond_one_workgroup_width(ctx, n, epochs):
     xy = instance(n)
     check_run(ctx, "wide", xy, None, n, None, epochs, 0.5, 3, n)
     check_run(ctx, "wide_init", xy, None, n, GC.start_tour(n, n), epochs, 0.5, 0, n)
+
+
+def test_whole_runs_past_two_compaction_rounds(ctx):
+    """n = 520: three compaction rounds per child; with and without a start tour, and once as a packed matrix"""
+    from teeline_amd import _capi
+    w = GC.WIDE
+    n, xy = w["n"], GC.instance(w["n"])
+    assert GC.rounds(n, plan(ctx, n)[1]) >= 3
+    for init in (None, GC.start_tour(n, n)):
+        want = GA.solve_cached(("wide", init is not None), xy, None, n, init, epochs=w["epochs"], mutation_probability=w["p"], n_elite=w["e"], seed=w["seed"])
+        rc, out, gcost, glog, ln, st, _routes = gpu_trace(ctx, xy, None, n, init, w["epochs"], w["p"], w["e"], w["seed"])
+        assert rc == 0 and ln == w["epochs"] and [tuple(int(v) for v in r) for r in glog] == want_trace(want[2]), init is not None
+        assert out.tolist() == want[0].tolist() and bits(gcost) == bits(want[1])
+        assert (st["candidates"], st["moves"], st["reversed"]) == (want[3]["children"], want[3]["improved"], want[3]["mutations"])
+    check_run(ctx, "wide_routes", xy, None, n, None, w["epochs"], w["p"], w["e"], w["seed"])  # and every logged route
+    pk = np.empty(n * (n - 1) // 2, dtype=np.float32)
+    ctx.check(ctx.lib.tl_dm_build(ctx.handle, _vp(xy), n, _capi.TL_DIST_EUC2D, _capi.TL_DM_PACKED_LOWER, _vp(pk), None))
+    want = GA.solve_cached(("wide", False), xy, None, n, None, epochs=w["epochs"], mutation_probability=w["p"], n_elite=w["e"], seed=w["seed"])
+    rc, out, gcost, glog, ln, _st, _routes = gpu_trace(ctx, None, pk, n, None, w["epochs"], w["p"], w["e"], w["seed"])
+    assert rc == 0 and out.tolist() == want[0].tolist() and bits(gcost) == bits(want[1]) and [tuple(int(v) for v in r) for r in glog] == want_trace(want[2])
+
+
+def test_rank_past_one_thread_per_individual(ctx):
+    """n = 1030, one generation, three elites: 1030 individuals ranked by 1024 threads, then the 1027 of the next generation"""
+    r = GC.RANK
+    n, xy = r["n"], GC.instance(r["n"])
+    want = GA.solve_cached("rank", xy, None, n, None, epochs=r["epochs"], mutation_probability=r["p"], n_elite=r["e"], seed=r["seed"])
+    rc, out, gcost, glog, ln, st, _routes = gpu_trace(ctx, xy, None, n, None, r["epochs"], r["p"], r["e"], r["seed"])
+    assert rc == 0, ctx.lib.tl_last_error(ctx.handle).decode()
+    assert ln == 1 and [tuple(int(v) for v in x) for x in glog] == want_trace(want[2]) and want[2][0][3] == n - 3 > 1024
+    assert out.tolist() == want[0].tolist() and bits(gcost) == bits(want[1])
+    assert (st["sweeps"], st["candidates"], st["moves"], st["reversed"]) == (1, want[3]["children"], want[3]["improved"], want[3]["mutations"])
 
 
 @pytest.mark.parametrize("epochs", [0, 1, 2, 50])
@@ -387,5 +436,7 @@ def test_jitter_build():
         check_run(jctx, "epochs", K.small(8), None, 8, None, 50, 0.5, 3, 5)
         xy, packed, n, init, epochs, p, e, seed, run = GOLDEN["synth65_init"]
         check_run(jctx, "synth65_init", xy, packed, n, init, epochs, p, e, seed, run)
+        w = GC.WIDE  # three compaction rounds per child: the first set of wave counts is used again
+        check_run(jctx, "wide_routes", GC.instance(w["n"]), None, w["n"], None, w["epochs"], w["p"], w["e"], w["seed"])
     finally:
         jctx.close()

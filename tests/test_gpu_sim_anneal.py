@@ -423,9 +423,15 @@ class _RawContext:
         self.lib.tl_last_error.restype = C.c_char_p
         self.lib.tl_sim_anneal_trace_chain.argtypes = [vp, vp, u32, vp, vp, C.POINTER(_capi.TlSaOpts), u64, u32, vp, C.POINTER(C.c_float),
                                                        C.POINTER(_capi.TlStats), vp, u32, C.POINTER(u32)]
+        self.lib.tl_sim_anneal_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, C.POINTER(_capi.TlSaOpts), u64, vp, vp, vp, C.POINTER(u32),
+                                                      C.POINTER(_capi.TlStats)]
         self.handle = vp()
         rc = self.lib.tl_create(0, 0, C.byref(self.handle))
         assert rc == 0, self.lib.tl_last_error(None)
+        self.lib.tl_device_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
+        cus = C.c_int()
+        assert self.lib.tl_device_info(self.handle, C.byref(cus), None, None, 0) == 0
+        self.cus = cus.value
 
     def close(self):
         self.lib.tl_destroy(self.handle)
@@ -440,5 +446,149 @@ def test_jitter_build():
         for name in ("berlin52_hot", "berlin52_cold", "small3_hot"):
             xy, packed, n, init, opts, seed = CASES[name]
             check_chain(jctx, name, xy, packed, n, init, opts, seed)
+        n = 200  # the one-wave population chain with a reversal past one trip
+        seed, mid = K.LONG_POP[n]
+        traces, _st = check_population_chains(jctx, f"long{n}", K.synth(n, n), None, n, None, 0, jctx.cus + 1, K.long_opts(), seed, (0, mid, jctx.cus))
+        K.check_long_reversals(traces[mid], n, 64)
     finally:
         jctx.close()
+
+
+# ---------------------------------------------------------------- past one pass of a workgroup's loops
+def check_population_chains(ctx, key, xy, packed, n, init, init_count, count, opts, seed, sample, oracle_xy=None):
+    """chains `sample` of a population against the oracle: tour, cost, accepted moves.  key: the name the oracle's chains are cached
+    under (check_chain's); oracle_xy: the coordinates behind a matrix"""
+    rc, out, costs, moves, best, st = gpu_population(ctx, xy, packed, n, init, init_count, 0, count, opts, seed)
+    assert rc == 0, ctx.lib.tl_last_error(ctx.handle).decode()
+    assert (np.sort(out, axis=1) == np.arange(n)).all()
+    traces = {}
+    for r in sample:
+        start = None if init_count == 0 else init if init_count == 1 else init[r]
+        tour, cost, trace = SA.solve_cached((key, seed, r), xy if oracle_xy is None else oracle_xy, None, n, start, seed=seed, chain=r, **opts)
+        assert out[r].tolist() == tour.tolist() and bits(costs[r]) == bits(cost) and moves[r] == len(trace), (key, count, r)
+        traces[r] = trace
+    keys = [(bits(c) << 32) | r for r, c in enumerate(costs)]
+    assert best == int(np.argmin(keys)) and st["sweeps"] == len(SA.schedule(**opts)) * count and st["moves"] == int(moves.sum())
+    return traces, st
+
+
+@pytest.mark.parametrize("n", sorted(K.LONG_POP))
+def test_one_wave_chains_reverse_past_one_trip(ctx, nospec, n):
+    """cus + 1 chains of one wave each at n = 130 and 200: loops over the tour take a second and a third trip, and the chain between the
+    first and the last accepts a reversal of more than 128 elements (a second trip of the reversal loops on 64 threads) and a move that
+    rebuilds the closing edge (K.check_long_reversals on the oracle's trace).  The same chain alone without speculation."""
+    seed, mid = K.LONG_POP[n]
+    cus = ctx.device_info()["cus"]
+    _w, nt, _per, _cus = plan(ctx, n, cus + 1)
+    assert nt == 64 and 0 < mid < cus
+    xy, opts = K.synth(n, n), K.long_opts()
+    traces, _st = check_population_chains(ctx, f"long{n}", xy, None, n, None, 0, cus + 1, opts, seed, (0, mid, cus))
+    assert any(t - f + 1 > 128 for _e, f, t, _c in traces[mid])
+    K.check_long_reversals(traces[mid], n, nt)
+    assert plan(nospec, n)[:2] == (1, 64)
+    check_chain(nospec, f"long{n}", xy, None, n, None, opts, seed, mid)
+
+
+def test_four_wave_chain_reverses_past_one_trip(ctx):
+    """n = 1500 on 256 threads: accepted reversals of more than 512 elements, one of them with from = 0 or to = n - 1"""
+    n, seed = K.LONG_SINGLE
+    assert plan(ctx, n)[1] == 256
+    trace = check_chain(ctx, f"long{n}", K.synth(n, n), None, n, None, K.long_opts(), seed)
+    assert any(t - f + 1 > 512 for _e, f, t, _c in trace)
+    K.check_long_reversals(trace, n, 256, same_move=True)
+
+
+TOP_EPOCHS = 40
+
+
+def test_at_the_lds_limit(ctx):
+    """n = tl_sim_anneal_lds_max_n: the verdict slots are the last 32 bytes of the LDS allocation.  One chain with its trace, nothing
+    written behind the n output positions, and a population of two."""
+    from teeline_amd import _capi
+    top = ctx.lib.tl_sim_anneal_lds_max_n(ctx.handle)
+    assert top == (ctx.device_info()["lds_bytes"] - 32) // 12 and plan(ctx, top)[0] > 0 and plan(ctx, top + 1)[0] == 0
+    xy, opts = K.synth(top, 77), K.long_opts(TOP_EPOCHS)
+    tour, cost, trace = SA.solve_cached(("top", 9, 0), xy, None, top, None, seed=9, chain=0, **opts)
+    assert len(trace) > TOP_EPOCHS // 2
+    pad = 4096
+    out = np.full(top + pad, 0xA5A5A5A5, dtype=np.uint32)
+    log = np.zeros((TOP_EPOCHS + 1, 4), dtype=np.uint32)
+    gcost, ln, st, o = C.c_float(-1.0), C.c_uint32(), _capi.TlStats(), c_opts(opts)
+    rc = ctx.lib.tl_sim_anneal_trace_chain(ctx.handle, _vp(xy), top, None, None, C.byref(o), 9, 0, _vp(out), C.byref(gcost), C.byref(st), _vp(log), len(log),
+                                           C.byref(ln))
+    assert rc == 0, ctx.lib.tl_last_error(ctx.handle).decode()
+    assert (out[top:] == 0xA5A5A5A5).all(), "written behind the tour"
+    assert ln.value == len(trace) and [tuple(int(v) for v in r) for r in log[:ln.value]] == [(e, f, t, bits(c)) for e, f, t, c in trace]
+    assert out[:top].tolist() == tour.tolist() and bits(gcost.value) == bits(cost)
+    assert st.sweeps == TOP_EPOCHS and st.moves == len(trace) and st.reversed == sum(t - f + 1 for _e, f, t, _c in trace)
+    check_population_chains(ctx, "top", xy, None, top, None, 0, 2, opts, 9, (0, 1))
+
+
+def test_matrix_form_past_one_trip(ctx):
+    """n = 257 as a packed EUC_2D matrix: the chain of the coordinate form, alone and as chain 0 of cus + 1 one-wave chains"""
+    from teeline_amd import _capi
+    xy, _packed, n, _init, opts, seed = CASES["synth257_short"]
+    pk = np.empty(n * (n - 1) // 2, dtype=np.float32)
+    ctx.check(ctx.lib.tl_dm_build(ctx.handle, _vp(xy), n, _capi.TL_DIST_EUC2D, _capi.TL_DM_PACKED_LOWER, _vp(pk), None))
+    tour, cost, trace = SA.solve_cached(("synth257_short", seed, 0), xy, None, n, None, seed=seed, chain=0, **opts)
+    rc, out, gcost, log, ln, st = gpu_trace(ctx, None, pk, n, None, opts, seed)
+    assert rc == 0 and out.tolist() == tour.tolist() and bits(gcost) == bits(cost) and ln == len(trace) == st["moves"]
+    assert [tuple(int(v) for v in r) for r in log] == [(e, f, t, bits(c)) for e, f, t, c in trace]
+    cus = ctx.device_info()["cus"]
+    assert plan(ctx, n, cus + 1)[1] == 64
+    check_population_chains(ctx, "synth257_short", None, pk, n, None, 0, cus + 1, opts, seed, (0, cus), oracle_xy=xy)
+
+
+# ---------------------------------------------------------------- schedules longer than one piece (the tuning build's TL_SA_CHUNK)
+def _on_tune_build():
+    import teeline_amd as TA
+    return TA._capi.load().tl_version().decode().endswith("+tune")
+
+
+TUNE_ONLY = pytest.mark.skipif("not _on_tune_build()", reason="TL_SA_CHUNK is read by libteeline_gpu_tune.so only "
+                                                              "(test_schedules_in_pieces_on_the_tune_build runs these in a child process)")
+
+
+@TUNE_ONLY
+@pytest.mark.parametrize("piece", K.PIECES)
+def test_schedule_in_pieces(ctx, monkeypatch, piece):
+    """From the second piece on the chains restart from out_pos with a stride of n, the temperature table is re-based, the trace index
+    and the counters continue: the whole trace, the tour, the cost and the stats of chains whose schedule takes several launches."""
+    monkeypatch.setenv("TL_SA_CHUNK", str(piece))
+    for name, (xy, n, init, opts, seed) in K.piece_cases(piece).items():
+        trace = check_chain(ctx, name, xy, None, n, init, opts, seed)
+        assert len(SA.schedule(**opts)) > piece and sum(piece <= e < 2 * piece for e, *_x in trace) >= 2
+    # a trace that ends inside the second piece
+    xy, n, init, opts, seed = K.piece_cases(piece)["berlin52_hot"]
+    tour, cost, trace = SA.solve_cached(("berlin52_hot", seed, 0), xy, None, n, init, seed=seed, **opts)
+    cap = sum(e < piece for e, *_x in trace) + 1
+    assert cap < len(trace) and piece <= trace[cap - 1][0] < 2 * piece
+    rc, out, gcost, log, ln, _st = gpu_trace(ctx, xy, None, n, init, opts, seed, cap=cap)
+    assert rc == 0 and ln == len(trace) and len(log) == cap and out.tolist() == tour.tolist() and bits(gcost) == bits(cost)
+    assert [tuple(int(v) for v in r) for r in log] == [(e, f, t, bits(c)) for e, f, t, c in trace[:cap]]
+    # three chains, from a start tour each (stride n from the first piece on) and from city order (stride 0, then n)
+    own = K.piece_start_tours()
+    for key, init, init_count in (("piece_own", own, 3), ("piece_city", None, 0)):
+        traces, st = check_population_chains(ctx, key, xy, None, n, init, init_count, 3, K.SHORT, K.PIECE_POP_SEED, (0, 1, 2))
+        assert st["reversed"] == sum(t - f + 1 for tr in traces.values() for _e, f, t, _c in tr)
+        assert len({len(tr) for tr in traces.values()}) > 1  # per-chain counts that differ
+
+
+def test_schedules_in_pieces_on_the_tune_build(ctx, monkeypatch):
+    """test_schedule_in_pieces in ONE child process bound to libteeline_gpu_tune.so (a process binds one library).  With TL_SA_CHUNK set the
+    product library's chain on a short schedule is the oracle's as before.  (That cannot show whether the variable was read, a schedule
+    in pieces being the same chain; that the product library does not read it is the `#ifdef TL_TUNE` around the getenv in tl_api_sa.hip.)"""
+    import sys
+    if _on_tune_build():
+        pytest.skip("already the child")
+    tune = os.path.join(ROOT, "teeline_amd", "libteeline_gpu_tune.so")
+    assert os.path.exists(tune), "built by __graft_entry__.build() / python -m teeline_amd.build"
+    monkeypatch.setenv("TL_SA_CHUNK", "100")
+    xy, packed, n, init, opts, seed = CASES["berlin52_short"]
+    check_chain(ctx, "berlin52_short", xy, packed, n, init, opts, seed)
+    env = dict(os.environ, TEELINE_GPU_LIB=tune)
+    env.pop("TL_SA_CHUNK")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q", "-k", "test_schedule_in_pieces"], env=env,
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert r.stdout.splitlines()[-1].startswith(f"{len(K.PIECES)} passed") and "skipped" not in r.stdout.splitlines()[-1], r.stdout[-500:]

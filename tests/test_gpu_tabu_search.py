@@ -86,13 +86,7 @@ def full():
     c.close()
 
 
-def opt_start(xy):
-    """a 2-opt local optimum (the plain-C oracle's descent from city order): no reversal shortens it, so early epochs reach deep attempts"""
-    import _oracle as O
-    n = len(xy)
-    rc, route, _cost, _st = O.two_opt(xy, None, n, init=np.arange(n, dtype=np.uint32))
-    assert rc == 0
-    return np.asarray(route, dtype=np.uint32)
+opt_start = TC.opt_start
 
 
 GOLDEN = TC.golden_cases()
@@ -269,6 +263,85 @@ def test_best_index_and_its_tie_rule(ctx):
         assert out[r].tolist() == tour.tolist() and bits(costs[r]) == bits(cost) and moves[r] == cnt["bests"]
 
 
+# ---------------------------------------------------------------- lists longer than one look-up round
+def check_population_chains(ctx, key, xy, packed, n, init, init_count, count, epochs, seed, sample, oracle_xy=None):
+    """chains `sample` of a population against the oracle: best tour, cost, new bests.  key: the name the oracle's chains are cached under
+    (check_chain's); oracle_xy: the coordinates behind a matrix"""
+    rc, out, costs, moves, best, st = gpu_population(ctx, xy, packed, n, init, init_count, 0, count, epochs, seed)
+    assert rc == 0, ctx.lib.tl_last_error(ctx.handle).decode()
+    assert (np.sort(out, axis=1) == np.arange(n)).all()
+    for r in sample:
+        tour, cost, _log, cnt = TO.solve_cached((key, seed, r), xy if oracle_xy is None else oracle_xy, None, n, init, epochs=epochs, seed=seed, chain=r)
+        assert out[r].tolist() == tour.tolist() and bits(costs[r]) == bits(cost) and moves[r] == cnt["bests"], (key, count, r)
+    keys = [(bits(c) << 32) | r for r, c in enumerate(costs)]
+    assert best == int(np.argmin(keys)) and st["sweeps"] == (epochs + 1) * count and st["moves"] == int(moves.sum())
+    return st
+
+
+@pytest.mark.parametrize("n", sorted(TC.WRAP_SEEDS))
+def test_wrapped_ring_beyond_one_round_population_width(ctx, full, n):
+    """One wave per chain looks 64 listed routes up per round.  n = 66 .. 70 from a 2-opt local optimum for 161 epochs: the list grows past
+    64 routes and wraps, and (TC.check_wrapped_ring on the oracle's record) refuses a candidate because of a route at a ring index >= 64,
+    refuses one after the wrap and lets improving candidates through after it.  Chain 0 of cus + 1 chains, the last chain, and chain 0
+    again where every listed route is compared."""
+    key, xy, packed, _n, start, epochs, seed = TC.wrap_chain(n)
+    cus = ctx.device_info()["cus"]
+    W = plan(ctx, n, cus + 1)[0]
+    assert W == plan(ctx, n, cus + 1)[1] == 64
+    _tour, _cost, log, _cnt = TO.solve_cached((key, seed, 0), xy, None, n, start, epochs=epochs, seed=seed, chain=0)
+    TC.check_wrapped_ring(n, W, log, TO.record_of((key, seed, 0)))
+    for c in (ctx, full):
+        check_population_chains(c, key, xy, None, n, start, 1, cus + 1, epochs, seed, (0, cus))
+    for c in (ctx, full):  # the same chain alone (four waves: one round), with its log
+        check_chain(c, key, xy, None, n, start, epochs, seed)
+
+
+def test_long_list_beyond_one_round_single_chain(ctx, full):
+    """A chain alone looks 256 listed routes up per round.  n = 300 from city order for 331 epochs: improving candidates are looked up in
+    a list of more than 256 routes, before and after the ring wraps at epoch 300 (TC.check_long_list).  No seed of 1 .. 13 000 gives this
+    chain a true refusal, at any index (scanned with the oracle), so none at an index >= 256 is asserted.  What this case can show is a
+    false hit in rows >= 256, with the hashes or with every listed route compared: that changes the chain.  Rows >= 256 that are never
+    looked at change nothing here, the list refusing nothing; the one-wave case above is the one that sees a look-up cut short."""
+    key, xy, packed, n, init, epochs, seed = TC.long_chain()
+    W = plan(ctx, n)[0]
+    assert W == 256
+    for c in (ctx, full):
+        log, _cnt = check_chain(c, key, xy, packed, n, init, epochs, seed)
+        TC.check_long_list(n, W, log, TO.record_of((key, seed, 0)))
+
+
+TOP_EPOCHS = 12
+
+
+def test_at_the_lds_limit(ctx):
+    """n = tl_tabu_search_lds_max_n from a seeded permutation: the ring is n x n 16-bit entries.  One chain with its log, and two chains."""
+    top = ctx.lib.tl_tabu_search_lds_max_n(ctx.handle)
+    assert 0 < top <= 65535 and plan(ctx, top)[0] > 0 and plan(ctx, top + 1)[:3] == (0, 0, 0)
+    xy = K.synth(top, 78)
+    start = np.random.default_rng(top).permutation(top).astype(np.uint32)
+    _log, cnt = check_chain(ctx, "top", xy, None, top, start, TOP_EPOCHS, 9)
+    assert cnt["bests"] >= 1
+    assert plan(ctx, top, 2)[2] >= 2
+    check_population_chains(ctx, "top", xy, None, top, start, 1, 2, TOP_EPOCHS, 9, (0, 1))
+
+
+def test_matrix_form_past_one_trip(ctx):
+    """n = 257 as a packed EUC_2D matrix: the chain of the coordinate form, alone and as chain 0 of cus + 1 one-wave chains"""
+    from teeline_amd import _capi
+    n, epochs, seed = 257, 150, 257
+    xy = K.synth(n, n)
+    pk = np.empty(n * (n - 1) // 2, dtype=np.float32)
+    ctx.check(ctx.lib.tl_dm_build(ctx.handle, _vp(xy), n, _capi.TL_DIST_EUC2D, _capi.TL_DM_PACKED_LOWER, _vp(pk), None))
+    tour, cost, log, cnt = TO.solve_cached(("synth257", seed, 0), xy, None, n, None, epochs=epochs, seed=seed, chain=0)
+    rc, out, gcost, glog, ln, st = gpu_trace(ctx, None, pk, n, None, epochs, seed)
+    assert rc == 0 and out.tolist() == tour.tolist() and bits(gcost) == bits(cost) and ln == epochs + 1
+    assert [tuple(int(v) for v in r) for r in glog] == want_log(log)
+    assert (st["candidates"], st["moves"], st["reversed"]) == (cnt["candidates"], cnt["bests"], cnt["reversed"])
+    cus = ctx.device_info()["cus"]
+    assert plan(ctx, n, cus + 1)[1] == 64
+    check_population_chains(ctx, "synth257", None, pk, n, None, 0, cus + 1, epochs, seed, (0, cus), oracle_xy=xy)
+
+
 # ---------------------------------------------------------------- context reuse, errors
 def test_context_reuse_larger_then_smaller(ctx):
     """a stale ring must not leak: the larger instance leaves its routes and hashes where the smaller ones' lists begin"""
@@ -412,9 +485,14 @@ class _RawContext:
         self.lib.tl_last_error.restype = C.c_char_p
         self.lib.tl_tabu_search_trace_chain.argtypes = [vp, vp, u32, vp, vp, u32, u64, u32, vp, C.POINTER(C.c_float), C.POINTER(_capi.TlStats), vp, u32,
                                                         C.POINTER(u32)]
+        self.lib.tl_tabu_search_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, u32, u64, vp, vp, vp, C.POINTER(u32), C.POINTER(_capi.TlStats)]
+        self.lib.tl_device_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
         self.handle = vp()
         rc = self.lib.tl_create(0, 0, C.byref(self.handle))
         assert rc == 0, self.lib.tl_last_error(None)
+        cus = C.c_int()
+        assert self.lib.tl_device_info(self.handle, C.byref(cus), None, None, 0) == 0
+        self.cus = cus.value
 
     def close(self):
         self.lib.tl_destroy(self.handle)
@@ -429,5 +507,9 @@ def test_jitter_build():
         for name in TC.HIT_CASES:
             xy, packed, n, init, epochs, seed, chain = GOLDEN[name]
             check_chain(jctx, name, xy, packed, n, init, epochs, seed, chain)
+        key, xy, packed, n, start, epochs, seed = TC.wrap_chain(66)  # the wrapped ring with a refusal in the look-up's second round
+        check_population_chains(jctx, key, xy, None, n, start, 1, jctx.cus + 1, epochs, seed, (0, jctx.cus))
+        log = TO.solve_cached((key, seed, 0), xy, None, n, start, epochs=epochs, seed=seed, chain=0)[2]
+        TC.check_wrapped_ring(n, 64, log, TO.record_of((key, seed, 0)))
     finally:
         jctx.close()

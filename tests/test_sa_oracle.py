@@ -231,3 +231,50 @@ def test_plan_is_host_only(lib):
     assert lib.tl_sim_anneal_plan(20000, 1, 256, 163840, 0, C.byref(w), C.byref(t), C.byref(per)) == 0
     assert (w.value, t.value, per.value) == (0, 0, 0)
     assert lib.tl_sim_anneal_plan(52, 1, 0, 163840, 0, None, None, None) == _capi.TL_ERR_BADARG
+
+
+# ---------------------------------------------------------------- the conditions of the cases past one workgroup pass
+def threads(lib, n, count, flags=0):
+    w, t, per = C.c_uint32(), C.c_int(), C.c_uint32()
+    assert lib.tl_sim_anneal_plan(n, count, K.CUS, K.LDS_BYTES, flags, C.byref(w), C.byref(t), C.byref(per)) == 0
+    return t.value
+
+
+@pytest.mark.parametrize("n", sorted(K.LONG_POP))
+def test_long_population_chains_reverse_past_one_trip(lib, n):
+    """the chain between the first and the last of cus + 1 one-wave chains: a reversal of more than 128 elements and a closing-edge
+    move, accepted; the same chain alone without speculation runs on 64 threads too"""
+    from teeline_amd import _capi
+    seed, mid = K.LONG_POP[n]
+    nt = threads(lib, n, K.CUS + 1)
+    assert nt == threads(lib, n, 1, _capi.TL_FLAG_SA_NO_SPECULATION) == 64 and 0 < mid < K.CUS and n > 2 * nt
+    key, *args, opts, seed, chain = K.long_chain(n, seed, mid)
+    trace = SA.solve_cached(key, *args, seed=seed, chain=chain, **opts)[2]
+    assert len(SA.schedule(**opts)) == K.LONG_EPOCHS and len(trace) > K.LONG_EPOCHS // 2
+    assert any(t - f + 1 > 128 for _e, f, t, _c in trace)
+    K.check_long_reversals(trace, n, nt)
+
+
+def test_long_single_chain_reverses_past_one_trip(lib):
+    n, seed = K.LONG_SINGLE
+    nt = threads(lib, n, 1)
+    assert nt == 256
+    key, *args, opts, seed, chain = K.long_chain(n, seed, 0)
+    trace = SA.solve_cached(key, *args, seed=seed, chain=chain, **opts)[2]
+    assert any(t - f + 1 > 512 for _e, f, t, _c in trace)
+    K.check_long_reversals(trace, n, nt, same_move=True)
+
+
+@pytest.mark.parametrize("piece", K.PIECES)
+def test_piece_cases_reach_a_second_piece(piece):
+    """every schedule run in pieces has more than one; the last piece of one epoch is one; accepted epochs fall into the second piece
+    (the trace index continues there) and a trace can be cut inside it"""
+    for name, (xy, n, init, opts, seed) in K.piece_cases(piece).items():
+        epochs = len(SA.schedule(**opts))
+        trace = SA.solve_cached((name, seed, 0), xy, None, n, init, seed=seed, **opts)[2]
+        assert epochs > piece, name
+        if name.startswith("last_piece_of_one"):
+            assert epochs % piece == 1 and epochs // piece == 2 and trace[-1][0] == epochs - 1
+        first = sum(e < piece for e, *_x in trace)
+        second = sum(piece <= e < 2 * piece for e, *_x in trace)
+        assert first >= 1 and second >= 2, (name, first, second)  # a cap of first + 1 ends the trace inside the second piece

@@ -269,3 +269,57 @@ def test_header_and_bindings_agree_on_the_new_flag_and_symbols(lib):
     for sym in ("tl_tabu_search", "tl_tabu_search_trace", "tl_tabu_search_trace_chain", "tl_tabu_search_population", "tl_tabu_search_lds_max_n",
                 "tl_tabu_search_plan", "tl_tabu_draw"):
         assert sym in _capi.SYMBOLS and re.search(rf"\b{sym}\(", text) and hasattr(lib, sym)
+
+
+# ---------------------------------------------------------------- the list's record, and the cases chosen with it
+def test_the_record_agrees_with_the_counters_and_the_replayed_list():
+    """solve's record: one list length and one look-up count per epoch, one entry per refusal, and the ring indices are where a ring
+    that writes its k-th route to slot k mod n holds the refused candidate"""
+    for name in TC.HIT_CASES:
+        xy, packed, n, _init, epochs, seed, chain = CASES[name]
+        _tour, _cost, log, cnt = oracle(name)
+        rec = TO.record_of((name, seed, chain))
+        assert len(rec["list_len"]) == len(rec["checked"]) == epochs + 1 and len(rec["refusals"]) == cnt["hits"] >= 1
+        assert rec["list_len"] == [min(e + 1, n) for e in range(epochs + 1)]
+        ring, u, k = [None] * n, list(range(n)), 1
+        ring[0] = tuple(u)
+        by_epoch = {}
+        for e, a, idx in rec["refusals"]:
+            by_epoch.setdefault(e, []).append((a, idx))
+        for e, (a, lo, hi, _c) in enumerate(log):
+            for ra, idx in by_epoch.get(e, []):
+                plo, phi = TO.pair(seed, chain, n, e, ra)
+                cand = tuple(u[:plo] + u[plo:phi + 1][::-1] + u[phi + 1:])
+                assert ra < a and idx and list(idx) == [j for j in range(n) if ring[j] == cand], (name, e)
+            assert rec["checked"][e] == len(by_epoch.get(e, [])) + (a < n)
+            ring[k % n] = tuple(u)
+            k += 1
+            u = u[:lo] + u[lo:hi + 1][::-1] + u[hi + 1:]
+
+
+def widths(lib, n):
+    """(threads of a chain alone, threads of a chain among more chains than CUs): the look-up takes that many listed routes per round"""
+    w, t, per = C.c_uint32(), C.c_int(), C.c_uint32()
+    out = []
+    for count in (1, TC.CUS + 1):
+        assert lib.tl_tabu_search_plan(n, count, TC.CUS, TC.LDS_BYTES, TC.WORK, 0, C.byref(w), C.byref(t), C.byref(per)) == 0
+        out.append(t.value)
+    return tuple(out)
+
+
+@pytest.mark.parametrize("n", sorted(TC.WRAP_SEEDS))
+def test_wrapped_ring_cases_refuse_beyond_one_round(lib, n):
+    key, xy, packed, _n, init, epochs, seed = TC.wrap_chain(n)
+    _tour, _cost, log, _cnt = TO.solve_cached((key, seed, 0), xy, packed, n, init, epochs=epochs, seed=seed, chain=0)
+    assert widths(lib, n)[1] == 64
+    TC.check_wrapped_ring(n, widths(lib, n)[1], log, TO.record_of((key, seed, 0)))
+
+
+def test_long_list_case_looks_up_beyond_one_round(lib):
+    """(No seed of 1 .. 13 000 gives this chain a single refusal, at any ring index: from city order improving candidates that the list
+    does not hold are plentiful for all 331 epochs.  So the case covers look-ups in a list of more than 256 routes against false hits
+    only; a look-up that stops after 256 rows gives the same chain.)"""
+    key, xy, packed, n, init, epochs, seed = TC.long_chain()
+    _tour, _cost, log, _cnt = TO.solve_cached((key, seed, 0), xy, packed, n, init, epochs=epochs, seed=seed, chain=0)
+    assert widths(lib, n)[0] == 256
+    TC.check_long_list(n, widths(lib, n)[0], log, TO.record_of((key, seed, 0)))
