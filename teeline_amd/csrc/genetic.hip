@@ -17,6 +17,7 @@
 //               two waves, at once), fitness by IEEE division, and the mutation applied to the stored genotype only.
 //
 //   LDS of a workgroup: 384 bytes of header and wave counts | E1[n], E2[n] f32 | c1[n], c2[n] u16 | fa[n], fb[n] u8 (14 n bytes).
+#include "chain_tour.h"
 #include "ga_spec.h"
 #include "tl_kernels.h"
 
@@ -27,18 +28,6 @@ namespace tl {
 namespace {
 
 constexpr size_t kGaFixedBytes = 384;  // header (16 words), then the wave counts (2 parities x 2 children x 16 waves)
-
-template <bool DM>
-struct GaDist {
-    const float2 *xy;
-    const float *full;
-    uint32_t n;
-    __device__ __forceinline__ float operator()(uint32_t a, uint32_t b) const
-    {
-        if (DM) return full[(size_t)a * n + b];
-        return dist(xy[a], xy[b]);
-    }
-};
 
 __device__ __forceinline__ size_t ga_up16(size_t v) { return (v + 15u) & ~(size_t)15u; }
 
@@ -152,7 +141,7 @@ __global__ __launch_bounds__(256) void k_ga_init(GaArgs A)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t n = A.n, tid = threadIdx.x, nt = blockDim.x, ind = blockIdx.x, run = blockIdx.y;
     const GaLds L(smem, n);
-    const GaDist<DM> D{A.xy, A.dm_full, n};
+    const CityDist<DM> D{A.xy, A.dm_full, n};
     const uint64_t key = sa_chain_key(A.seed, (uint64_t)A.first_run + run);
     const uint32_t n_seeded = A.init ? (n / 5u > 1u ? n / 5u : 1u) : 0u;
     uint16_t *r = L.c1;
@@ -206,7 +195,7 @@ __global__ __launch_bounds__(1024) void k_ga_rank(GaArgs A)
     float *f = reinterpret_cast<float *>(smem + 256);
     float *sf = f + ((len + 3u) & ~3u);
     float *E = sf + ((len + 3u) & ~3u);
-    const GaDist<DM> D{A.xy, A.dm_full, n};
+    const CityDist<DM> D{A.xy, A.dm_full, n};
     const float *fit = A.fit[A.src] + (size_t)run * n;
     const uint16_t *pop = A.pop[A.src] + (size_t)run * A.pop_stride;
     uint32_t *order = A.order + (size_t)run * n;
@@ -294,7 +283,7 @@ __global__ __launch_bounds__(256) void k_ga_breed(GaArgs A)
         return;
     }
     const GaLds L(smem, n);
-    const GaDist<DM> D{A.xy, A.dm_full, n};
+    const CityDist<DM> D{A.xy, A.dm_full, n};
     const uint32_t p = slot - ne;
     if (tid == 0) {
         const uint64_t key = sa_chain_key(A.seed, (uint64_t)A.first_run + run);

@@ -13,8 +13,8 @@
 //   sequential f32).  Positions before from - 1 are untouched, so the lane starts from S[from-1]: the new edge, E[to-1] ... E[from]
 //   backwards, the second new edge, E[to+1 ... n-2].  With from = 0 or to = n - 1 the closing edge changes and the sum starts
 //   from scratch.  The lanes of a wave walk k together, so most of them read the same E[k] (an LDS broadcast).
+#include "chain_tour.h"
 #include "sa_spec.h"
-#include "tl_kernels.h"
 
 #pragma clang fp contract(off)
 
@@ -23,28 +23,6 @@ namespace tl {
 namespace {
 
 constexpr size_t kSaSlotBytes = 32;  // three winner slots (rotating), from, to
-
-template <bool DM>
-struct SaDist {
-    const float2 *xy;
-    const float *full;
-    uint32_t n;
-    __device__ __forceinline__ float operator()(uint32_t a, uint32_t b) const
-    {
-        if (DM) return full[(size_t)a * n + b];
-        return dist(xy[a], xy[b]);
-    }
-};
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
 
 }  // namespace
 
@@ -60,7 +38,7 @@ __global__ __launch_bounds__(1024) void k_sim_anneal(SaArgs A)
     // barrier, so a fast wave posts its next verdict while a slow one still reads this one; the slot of window w + 2 is cleared
     // behind window w's barrier, when every wave has read it (as window w - 1's) and none can post to it yet.  [3] from, [4] to
     uint32_t *slot = reinterpret_cast<uint32_t *>(S + n);
-    const SaDist<DM> D{A.xy, A.dm_full, n};
+    const CityDist<DM> D{A.xy, A.dm_full, n};
     const uint64_t key = sa_chain_key(A.seed, (uint64_t)A.first_chain + blk);
 
     const uint32_t *init = A.init + (size_t)blk * A.init_stride;
@@ -100,6 +78,7 @@ __global__ __launch_bounds__(1024) void k_sim_anneal(SaArgs A)
                 tot = S[start];
             }
         }
+        // (this costing and the commit below stand in tabu_search.hip too, character for character: change both — chain_tour.h says why)
         // the wave's lanes walk k together from the lowest start among them
         const uint32_t k0 = wave_min_u32(start);
         const uint32_t rsum = from + to - 1u;

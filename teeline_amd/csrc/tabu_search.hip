@@ -14,8 +14,8 @@
 //   hash costs its lane four edge hashes — combined with the bits of the route's cost.  A lane-parallel look-up over the hashes
 //   names the listed routes that may equal the candidate; a wave then compares each of them with the candidate element for
 //   element.  The hash never decides alone: with full_compare every listed route is compared.
+#include "chain_tour.h"
 #include "tabu_spec.h"
-#include "tl_kernels.h"
 
 #pragma clang fp contract(off)
 
@@ -24,28 +24,6 @@ namespace tl {
 namespace {
 
 constexpr size_t kTabuFixedBytes = 2 * 16 * 8 + 32;  // two sets of 16 wave ballots; listed[2], from, to, hash, the start tour's edge hash
-
-template <bool DM>
-struct TabuDist {
-    const float2 *xy;
-    const float *full;
-    uint32_t n;
-    __device__ __forceinline__ float operator()(uint32_t a, uint32_t b) const
-    {
-        if (DM) return full[(size_t)a * n + b];
-        return dist(xy[a], xy[b]);
-    }
-};
-
-__device__ __forceinline__ uint32_t tabu_wave_min_u32(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
 
 // the hash of the undirected edge {a, b}
 __device__ __forceinline__ uint32_t tabu_edge_hash(uint32_t a, uint32_t b)
@@ -79,7 +57,7 @@ __global__ __launch_bounds__(1024) void k_tabu_search(TabuArgs A)
     uint32_t *perm = slot + 8;
     float *E = reinterpret_cast<float *>(perm + n);
     float *S = E + n;
-    const TabuDist<DM> D{A.xy, A.dm_full, n};
+    const CityDist<DM> D{A.xy, A.dm_full, n};
     const uint64_t key = sa_chain_key(A.seed, (uint64_t)A.first_chain + blk);
     uint16_t *ring = A.ring + (size_t)blk * A.ring_stride;
     uint32_t *rhash = A.hashes + (size_t)blk * n;
@@ -137,8 +115,9 @@ __global__ __launch_bounds__(1024) void k_tabu_search(TabuArgs A)
                     tot = S[start];
                 }
             }
+            // (this costing and the commit below stand in sim_anneal.hip too, character for character: change both — chain_tour.h says why)
             // the wave's lanes walk k together from the lowest start among them
-            const uint32_t k0 = tabu_wave_min_u32(start);
+            const uint32_t k0 = wave_min_u32(start);
             const uint32_t rsum = from + to - 1u;
 #pragma unroll 4
             for (uint32_t k = k0; k + 1u < n; ++k) {

@@ -1,7 +1,8 @@
 // tl_api_common.h — what the host-side translation units of the C ABI share (internal to libteeline_gpu): the context, its
 // single-thread guard, error reporting and the grow-only device buffers.  tl_api.hip (context, matrix, tour length),
 // tl_api_two_opt.hip, tl_api_scans.hip (3-opt, Or-opt), tl_api_lk.hip (candidate lists, NN seed, Lin-Kernighan), tl_api_greedy.hip
-// (greedy-edge, savings, Christofides) and tl_api_bhk.hip (Bellman-Held-Karp) include it.
+// (greedy-edge, savings, Christofides) and tl_api_bhk.hip (Bellman-Held-Karp) include it; tl_api_sa.hip, tl_api_tabu.hip and
+// tl_api_ga.hip (the seeded chains) through tl_api_chains.h, which adds what those three share.
 #pragma once
 #include "../../include/teeline_gpu.h"
 #include "tl_kernels.h"
@@ -159,17 +160,18 @@ inline int upload_input(tl_ctx *c, const float *xy, const float *dm_packed, uint
     return dm_packed ? upload_dm(c, dm_packed, n, ddm) : upload_xy(c, xy, n, dxy);
 }
 
-// The start permutation (init == NULL: the identity) to d_perm, and a synchronise: the identity lives in here, and every host
-// vector whose copy the caller enqueued before this call may go out of scope behind it.  The last upload of a setup.
-inline int upload_start_sync(tl_ctx *c, const uint32_t *init, uint32_t n, void *d_perm)
+// The start permutation (init == NULL: the identity), or `tours` of them one after the other, to d_perm, and a synchronise: the
+// identity lives in here, and every host vector whose copy the caller enqueued before this call may go out of scope behind it.
+// The last upload of a setup.
+inline int upload_start_sync(tl_ctx *c, const uint32_t *init, uint32_t n, void *d_perm, size_t tours = 1)
 {
     std::vector<uint32_t> ident;
     if (!init) {
-        ident.resize(n);
-        for (uint32_t i = 0; i < n; ++i) ident[i] = i;
+        ident.resize(tours * n);
+        for (size_t i = 0; i < ident.size(); ++i) ident[i] = (uint32_t)(i % n);
         init = ident.data();
     }
-    HIPCHK(c, hipMemcpyAsync(d_perm, init, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_perm, init, tours * n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return TL_OK;
 }

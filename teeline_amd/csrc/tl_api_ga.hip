@@ -1,7 +1,7 @@
 // tl_api_ga.hip — C ABI, the genetic algorithm: tl_genetic_algorithm* (src/tsp/genetic_algorithm.rs:16-336) over genetic.hip, the
 // host-only queries of its specification (tl_ga_draw, tl_genetic_algorithm_plan) and the device self-test of the crossover.
 #include "ga_spec.h"
-#include "tl_api_common.h"
+#include "tl_api_chains.h"
 
 using namespace tl;
 using namespace tlapi;
@@ -38,10 +38,8 @@ static int ga_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, const
                   uint32_t *log, uint32_t log_cap, uint32_t *log_len, uint32_t *route_log, uint32_t route_cap)
 {
     if (log_len) *log_len = 0;
-    if (!c || (!xy && !dm_packed)) return fail(c, TL_ERR_BADARG, "%s: NULL argument", who);
+    if (int rc = check_chain_call(c, who, xy, dm_packed, count, out_pos, init_pos, init_pos ? 1u : 0u, first_run, "run")) return rc;
     if (count == 0) return TL_OK;
-    if (!out_pos) return fail(c, TL_ERR_BADARG, "%s: NULL argument", who);
-    if ((uint64_t)first_run + count > 0x100000000ull) return fail(c, TL_ERR_BADARG, "%s: run ids beyond 2^32 - 1", who);
     if (c->flags & kGaUnassignedFlags) return fail(c, TL_ERR_UNSUPPORTED, "%s: the context's flags 0x%x hold a bit no flag has", who, c->flags);
     if (!(p_mut >= 0.0f && p_mut <= 1.0f)) return fail(c, TL_ERR_BADARG, "%s: mutation_probability must be in [0, 1] (got %g)", who, (double)p_mut);
     if (n == 0u) return fail(c, TL_ERR_REF_PANICS, "%s: n=0: the reference panics (genetic_algorithm.rs:257-262 best() of an empty population)", who);
@@ -88,16 +86,7 @@ static int ga_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, const
         (rc = ensure(c, c->misc, (size_t)count * 32)) || (rc = ensure(c, c->work, log_bytes + route_bytes + (size_t)held * ga_run_bytes(n))))
         return rc;
     GaArgs A{};
-    const float *d_dm = nullptr;
-    if ((rc = upload_input(c, xy, dm_packed, n, &A.xy, &d_dm))) return rc;
-    c->ev_valid = false;
-    if (d_dm) {
-        if ((rc = ws_order(c, c->stream))) return rc;  // dmfull may still be read by a batch this context enqueued on another stream
-        if ((rc = ensure(c, c->dmfull, up256((size_t)n * n * 4)))) return rc;
-        HIPCHK(c, launch_dm_expand_full(d_dm, n, (float *)c->dmfull.p, c->stream));
-        A.dm_full = (const float *)c->dmfull.p;
-        A.xy = nullptr;
-    }
+    if ((rc = upload_instance_full(c, xy, dm_packed, n, &A.xy, &A.dm_full))) return rc;
     HIPCHK(c, hipMemsetAsync(c->misc.p, 0, (size_t)count * 32, c->stream));
     if (init_pos) {
         HIPCHK(c, hipMemcpyAsync(c->init.p, init_pos, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
@@ -149,28 +138,24 @@ static int ga_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, const
     }
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     c->ev_valid = true;
-    std::vector<uint32_t> state((size_t)count * 8);
-    std::vector<float> costs(count);
-    HIPCHK(c, hipMemcpyAsync(state.data(), c->misc.p, (size_t)count * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(costs.data(), c->out_cost.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out_pos, c->out_pos.p, words * 4, hipMemcpyDeviceToHost, c->stream));
+    std::vector<uint32_t> state;
+    std::vector<float> costs;
+    if ((rc = download_chains(c, count, n, 8u, out_pos, state, costs))) return rc;
     if (dev_log_cap) HIPCHK(c, hipMemcpyAsync(log, A.log, (size_t)dev_log_cap * 16, hipMemcpyDeviceToHost, c->stream));
     if (dev_route_cap) HIPCHK(c, hipMemcpyAsync(route_log, A.route_log, (size_t)dev_route_cap * n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    uint64_t improved = 0, mutations = 0, best_key = ~0ull;
+    uint64_t improved = 0, mutations = 0;
     for (uint32_t r = 0; r < count; ++r) {
-        if (state[8u * r + 3u])
+        if (state[8u * r + 3u]) {
+            if (best_index) *best_index = best_chain(costs, r);  // of the runs before it, like the out_costs written so far
             return fail(c, TL_ERR_REF_PANICS, "%s: run %u: the reference panics (genetic_algorithm.rs:277 random_range on an empty range: total fitness not > 0 or not finite)",
                         who, first_run + r);
+        }
         if (out_costs) out_costs[r] = costs[r];
         improved += state[8u * r + 1u];
         mutations += state[8u * r + 2u];
-        const uint64_t k = tl_pack_cost_key(costs[r], r);
-        if (k < best_key) {
-            best_key = k;
-            if (best_index) *best_index = r;
-        }
     }
+    if (best_index) *best_index = best_chain(costs, count);
     if (log_len) *log_len = epochs;
     if (stats) {
         stats->sweeps = (uint64_t)epochs * count;

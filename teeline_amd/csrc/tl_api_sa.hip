@@ -1,7 +1,7 @@
 // tl_api_sa.hip — C ABI, simulated annealing: tl_sim_anneal* (src/tsp/simulated_annealing.rs:10-83) over sim_anneal.hip, the host-only
 // queries of its specification (tl_sa_draw, tl_sa_schedule_epochs, tl_sim_anneal_plan) and tl_sa_selftest_accept.
 #include "sa_spec.h"
-#include "tl_api_common.h"
+#include "tl_api_chains.h"
 
 #pragma clang fp contract(off)
 
@@ -80,8 +80,7 @@ extern "C" int tl_sim_anneal_plan(uint32_t n, uint32_t count, int cus, int lds_b
     if (window) *window = !fits ? 0u : (flags & TL_FLAG_SA_NO_SPECULATION) ? 1u : (uint32_t)nt;
     if (threads) *threads = nt;
     if (per_launch) {
-        uint64_t per_cu = fits ? (uint64_t)lds_bytes / sim_anneal_lds_bytes(n) : 0u;
-        if (fits && per_cu > 2048u / (uint32_t)nt) per_cu = 2048u / (uint32_t)nt;
+        const uint64_t per_cu = fits ? chains_per_cu(lds_bytes, sim_anneal_lds_bytes(n), nt) : 0u;
         *per_launch = (uint32_t)(per_cu * (uint32_t)cus);
     }
     return TL_OK;
@@ -93,12 +92,8 @@ static int sa_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, const
                   uint32_t *best_index, tl_stats *stats, uint32_t *move_log, uint32_t log_cap, uint32_t *log_len)
 {
     if (log_len) *log_len = 0;
-    if (!c || (!xy && !dm_packed)) return fail(c, TL_ERR_BADARG, "%s: NULL argument", who);
+    if (int rc = check_chain_call(c, who, xy, dm_packed, count, out_pos, init_pos, init_count, first_chain, "chain")) return rc;
     if (count == 0) return TL_OK;
-    if (!out_pos || (init_count && !init_pos)) return fail(c, TL_ERR_BADARG, "%s: NULL argument", who);
-    if (init_count != 0u && init_count != 1u && init_count != count)
-        return fail(c, TL_ERR_BADARG, "%s: init_count is %u: 0 (city order), 1 (one start tour) or count (%u)", who, init_count, count);
-    if ((uint64_t)first_chain + count > 0x100000000ull) return fail(c, TL_ERR_BADARG, "%s: chain ids beyond 2^32 - 1", who);
     const tl_sa_opts o = opts ? *opts : kSaDefaults;
     const bool empty = o.epochs == 0u && !(o.max_temperature > o.min_temperature);
     if (!empty)
@@ -138,16 +133,7 @@ static int sa_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, const
         (rc = ensure(c, c->misc, (size_t)count * 16)) || (rc = ensure(c, c->work, up256((table_cap ? table_cap : 1u) * 4) + (size_t)(dev_log_cap ? dev_log_cap : 1u) * 16)))
         return rc;
     SaArgs A{};
-    const float *d_dm = nullptr;
-    if ((rc = upload_input(c, xy, dm_packed, n, &A.xy, &d_dm))) return rc;
-    c->ev_valid = false;
-    if (d_dm) {
-        if ((rc = ws_order(c, c->stream))) return rc;  // dmfull may still be read by a batch this context enqueued on another stream
-        if ((rc = ensure(c, c->dmfull, up256((size_t)n * n * 4)))) return rc;
-        HIPCHK(c, launch_dm_expand_full(d_dm, n, (float *)c->dmfull.p, c->stream));
-        A.dm_full = (const float *)c->dmfull.p;
-        A.xy = nullptr;
-    }
+    if ((rc = upload_instance_full(c, xy, dm_packed, n, &A.xy, &A.dm_full))) return rc;
     HIPCHK(c, hipMemsetAsync(c->misc.p, 0, (size_t)count * 16, c->stream));
     A.temps = (const float *)c->work.p;
     A.log = move_log ? (uint32_t *)((unsigned char *)c->work.p + up256((table_cap ? table_cap : 1u) * 4)) : nullptr;
@@ -155,17 +141,7 @@ static int sa_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, const
     A.seed = seed;
     A.n = n;
     A.window = window;
-    {   // the start tours: city order, one tour, or one per chain
-        std::vector<uint32_t> ident;
-        const uint32_t *src = init_pos;
-        if (!init_count) {
-            ident.resize(n);
-            for (uint32_t i = 0; i < n; ++i) ident[i] = i;
-            src = ident.data();
-        }
-        HIPCHK(c, hipMemcpyAsync(c->init.p, src, starts * n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    if ((rc = upload_start_sync(c, init_count ? init_pos : nullptr, n, c->init.p, starts))) return rc;  // city order, one tour, or one per chain
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     std::vector<float> table(table_cap);
     uint64_t done = 0;
@@ -205,27 +181,21 @@ static int sa_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, const
     } while (done < total);
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     c->ev_valid = true;
-    std::vector<uint32_t> run((size_t)count * 4);
-    std::vector<float> costs(count);
-    HIPCHK(c, hipMemcpyAsync(run.data(), c->misc.p, (size_t)count * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(costs.data(), c->out_cost.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out_pos, c->out_pos.p, words * 4, hipMemcpyDeviceToHost, c->stream));
+    std::vector<uint32_t> run;
+    std::vector<float> costs;
+    if ((rc = download_chains(c, count, n, 4u, out_pos, run, costs))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (move_log && dev_log_cap && run[0])
         HIPCHK(c, hipMemcpy(move_log, A.log, (size_t)(run[0] < dev_log_cap ? run[0] : dev_log_cap) * 16, hipMemcpyDeviceToHost));
     if (log_len) *log_len = run[0];
-    uint64_t moves = 0, reversed = 0, best_key = ~0ull;
+    uint64_t moves = 0, reversed = 0;
     for (uint32_t r = 0; r < count; ++r) {
         if (out_costs) out_costs[r] = costs[r];
         if (out_moves) out_moves[r] = run[4u * r];
         moves += run[4u * r];
         reversed += (uint64_t)run[4u * r + 2u] << 32 | run[4u * r + 1u];
-        const uint64_t k = tl_pack_cost_key(costs[r], r);
-        if (k < best_key) {
-            best_key = k;
-            if (best_index) *best_index = r;
-        }
     }
+    if (best_index) *best_index = best_chain(costs, count);
     if (stats) {
         stats->sweeps = stats->candidates = total * count;
         stats->moves = moves;

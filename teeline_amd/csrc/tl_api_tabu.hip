@@ -1,7 +1,7 @@
 // tl_api_tabu.hip — C ABI, tabu search: tl_tabu_search* (src/tsp/tabu_search.rs:9-110) over tabu_search.hip and the host-only queries
 // of its specification (tl_tabu_draw, tl_tabu_search_plan).
 #include "tabu_spec.h"
-#include "tl_api_common.h"
+#include "tl_api_chains.h"
 
 using namespace tl;
 using namespace tlapi;
@@ -33,9 +33,7 @@ extern "C" int tl_tabu_search_plan(uint32_t n, uint32_t count, int cus, int lds_
     if (window) *window = (uint32_t)nt;
     if (threads) *threads = nt;
     if (per_launch) {
-        uint64_t per_cu = fits ? (uint64_t)lds_bytes / tabu_search_lds_bytes(n) : 0u;
-        if (fits && per_cu > 2048u / (uint32_t)nt) per_cu = 2048u / (uint32_t)nt;
-        uint64_t per = per_cu * (uint32_t)cus;
+        uint64_t per = fits ? chains_per_cu(lds_bytes, tabu_search_lds_bytes(n), nt) * (uint32_t)cus : 0u;
         const uint64_t held = fits ? workspace_bytes / (tabu_ring_bytes(n) + tabu_hash_bytes(n)) : 0u;
         if (per > held) per = held;
         *per_launch = per > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)per;
@@ -49,12 +47,8 @@ static int tabu_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, con
                     uint32_t *best_index, tl_stats *stats, uint32_t *move_log, uint32_t log_cap, uint32_t *log_len)
 {
     if (log_len) *log_len = 0;
-    if (!c || (!xy && !dm_packed)) return fail(c, TL_ERR_BADARG, "%s: NULL argument", who);
+    if (int rc = check_chain_call(c, who, xy, dm_packed, count, out_pos, init_pos, init_count, first_chain, "chain")) return rc;
     if (count == 0) return TL_OK;
-    if (!out_pos || (init_count && !init_pos)) return fail(c, TL_ERR_BADARG, "%s: NULL argument", who);
-    if (init_count != 0u && init_count != 1u && init_count != count)
-        return fail(c, TL_ERR_BADARG, "%s: init_count is %u: 0 (city order), 1 (one start tour) or count (%u)", who, init_count, count);
-    if ((uint64_t)first_chain + count > 0x100000000ull) return fail(c, TL_ERR_BADARG, "%s: chain ids beyond 2^32 - 1", who);
     if (c->flags & kTabuUnassignedFlags) return fail(c, TL_ERR_UNSUPPORTED, "%s: the context's flags 0x%x hold a bit no flag has", who, c->flags);
     if (epochs == 0u) return fail(c, TL_ERR_UNSUPPORTED, "%s: epochs = 0 never ends in the reference (tabu_search.rs:83-85)", who);
     if (epochs == 0xFFFFFFFFu) return fail(c, TL_ERR_UNSUPPORTED, "%s: epochs + 1 epochs run, and 2^32 do not fit", who);
@@ -83,16 +77,7 @@ static int tabu_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, con
         (rc = ensure(c, c->misc, (size_t)count * 32)) || (rc = ensure(c, c->work, log_bytes + (size_t)held * (tabu_ring_bytes(n) + tabu_hash_bytes(n)))))
         return rc;
     TabuArgs A{};
-    const float *d_dm = nullptr;
-    if ((rc = upload_input(c, xy, dm_packed, n, &A.xy, &d_dm))) return rc;
-    c->ev_valid = false;
-    if (d_dm) {
-        if ((rc = ws_order(c, c->stream))) return rc;  // dmfull may still be read by a batch this context enqueued on another stream
-        if ((rc = ensure(c, c->dmfull, up256((size_t)n * n * 4)))) return rc;
-        HIPCHK(c, launch_dm_expand_full(d_dm, n, (float *)c->dmfull.p, c->stream));
-        A.dm_full = (const float *)c->dmfull.p;
-        A.xy = nullptr;
-    }
+    if ((rc = upload_instance_full(c, xy, dm_packed, n, &A.xy, &A.dm_full))) return rc;
     HIPCHK(c, hipMemsetAsync(c->misc.p, 0, (size_t)count * 32, c->stream));
     unsigned char *w = (unsigned char *)c->work.p;
     A.log = move_log ? (uint32_t *)w : nullptr;
@@ -104,17 +89,7 @@ static int tabu_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, con
     A.n = n;
     A.epochs = total;
     A.full_compare = (c->flags & TL_FLAG_TABU_FULL_COMPARE) ? 1u : 0u;
-    {   // the start tours: city order, one tour, or one per chain
-        std::vector<uint32_t> ident;
-        const uint32_t *src = init_pos;
-        if (!init_count) {
-            ident.resize(n);
-            for (uint32_t i = 0; i < n; ++i) ident[i] = i;
-            src = ident.data();
-        }
-        HIPCHK(c, hipMemcpyAsync(c->init.p, src, starts * n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    if ((rc = upload_start_sync(c, init_count ? init_pos : nullptr, n, c->init.p, starts))) return rc;  // city order, one tour, or one per chain
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     A.init_stride = init_count == count ? n : 0u;  // (0: every chain from the one tour uploaded)
     for (uint32_t b0 = 0; b0 < count; b0 += per_launch) {  // launches on one stream follow each other: the next takes over the rings
@@ -130,27 +105,21 @@ static int tabu_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, con
     }
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     c->ev_valid = true;
-    std::vector<uint32_t> run((size_t)count * 8);
-    std::vector<float> costs(count);
-    HIPCHK(c, hipMemcpyAsync(run.data(), c->misc.p, (size_t)count * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(costs.data(), c->out_cost.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out_pos, c->out_pos.p, words * 4, hipMemcpyDeviceToHost, c->stream));
+    std::vector<uint32_t> run;
+    std::vector<float> costs;
+    if ((rc = download_chains(c, count, n, 8u, out_pos, run, costs))) return rc;
     if (move_log && dev_log_cap) HIPCHK(c, hipMemcpyAsync(move_log, A.log, (size_t)dev_log_cap * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (log_len) *log_len = total;
-    uint64_t moves = 0, candidates = 0, reversed = 0, best_key = ~0ull;
+    uint64_t moves = 0, candidates = 0, reversed = 0;
     for (uint32_t r = 0; r < count; ++r) {
         if (out_costs) out_costs[r] = costs[r];
         if (out_moves) out_moves[r] = run[8u * r];
         moves += run[8u * r];
         candidates += (uint64_t)run[8u * r + 2u] << 32 | run[8u * r + 1u];
         reversed += (uint64_t)run[8u * r + 4u] << 32 | run[8u * r + 3u];
-        const uint64_t k = tl_pack_cost_key(costs[r], r);
-        if (k < best_key) {
-            best_key = k;
-            if (best_index) *best_index = r;
-        }
     }
+    if (best_index) *best_index = best_chain(costs, count);
     if (stats) {
         stats->sweeps = (uint64_t)total * count;
         stats->candidates = candidates;

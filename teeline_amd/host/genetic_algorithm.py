@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import HeuristicOptions
+from ._chains import bits_to_f32, vp
 
 
 class GAOptions:
@@ -54,7 +55,6 @@ def solve(problem, opts=None, progress_tx=None, init_tour=None, *, seed=1, runs=
     epochs, p, e = int(opts.epochs), float(opts.mutation_probability), int(opts.n_elite)
     init_pos = problem.positions_of(init_tour) if init_tour is not None else None
     packed = problem.explicit_packed()
-    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
     st = _capi.TlStats()
     run, extra = 0, {}
     if runs > 1:
@@ -83,7 +83,7 @@ def solve(problem, opts=None, progress_tx=None, init_tour=None, *, seed=1, runs=
                                                      C.byref(st1), vp(log), epochs, C.byref(ln), vp(routes), epochs))
     ids = problem.ids
     for g in range(epochs):
-        progress_tx("PathUpdate", ([int(v) for v in ids[routes[g]]], float(log[g, 2:3].view(np.float32)[0])))
+        progress_tx("PathUpdate", ([int(v) for v in ids[routes[g]]], float(bits_to_f32(log[g, 2]))))
     progress_tx("PathUpdate", ([int(v) for v in ids[out]], float(cost.value)))
     progress_tx("Done", None)
     return Solution(cost.value, ids[out], problem, dict((st if runs > 1 else st1).as_dict(), **extra))

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import HeuristicOptions
+from ._chains import bits_to_f32, solve_chains, start_tour, swap_cities, vp
 
 
 class SAOptions:
@@ -67,79 +68,48 @@ def solve(problem, opts=None, progress_tx=None, init_tour=None, *, ctx=None, see
     accepted epoch and Done (simulated_annealing.rs:33-38,49-54,63-65); with a channel the solve goes through tl_sim_anneal_trace and
     the sequence is replayed from the accepted (epoch, from, to, cost) list.  chains > 1: chains 0 .. chains-1 of `seed` run at once
     (tl_sim_anneal_population) and the best one (lowest cost, then lowest chain) is returned; the replay is of that chain."""
-    from . import Solution, default_context
-    from .. import _capi
+    from . import default_context
     ctx = ctx or default_context()
     opts = opts or SAOptions()
     n = len(problem)
     init_pos = problem.positions_of(init_tour) if init_tour is not None else None
     packed = problem.explicit_packed()
     o = opts.as_c()
-    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    st = _capi.TlStats()
-    chain = 0
-    if chains > 1:
-        outs = np.empty((chains, n), dtype=np.uint32)
-        costs = np.empty(chains, dtype=np.float32)
-        moves = np.zeros(chains, dtype=np.uint32)
-        best = C.c_uint32()
-        ctx.check(ctx.lib.tl_sim_anneal_population(ctx.handle, vp(problem.xy), n, vp(packed), vp(init_pos), 0 if init_pos is None else 1, 0, chains,
-                                                   C.byref(o), seed, vp(outs), vp(costs), vp(moves), C.byref(best), C.byref(st)))
-        chain = int(best.value)
-        out, cost = outs[chain], float(costs[chain])
-        stats = dict(st.as_dict(), moves=int(moves[chain]), chain=chain)
-        if progress_tx is not None:  # the best chain once more, alone, for its accepted epochs
-            _, _, log = _trace(ctx, problem, packed, init_pos, o, seed, chain, n)
-            replay_progress(problem, init_pos, log, progress_tx)
-        return Solution(cost, problem.ids[out], problem, stats)
-    out = np.empty(n, dtype=np.uint32)
-    cost = C.c_float()
-    if progress_tx is None:
-        ctx.check(ctx.lib.tl_sim_anneal(ctx.handle, vp(problem.xy), n, vp(packed), vp(init_pos), C.byref(o), seed, vp(out), C.byref(cost), C.byref(st)))
-        return Solution(cost.value, problem.ids[out], problem, st.as_dict())
-    out, costv, log, st = _trace(ctx, problem, packed, init_pos, o, seed, 0, n, want_stats=True)
-    replay_progress(problem, init_pos, log, progress_tx)
-    return Solution(costv, problem.ids[out], problem, st)
+    lib, inst = ctx.lib, (ctx.handle, vp(problem.xy), n, vp(packed), vp(init_pos))
 
+    def population(chains, outs, costs, moves, best, st):
+        ctx.check(lib.tl_sim_anneal_population(*inst, 0 if init_pos is None else 1, 0, chains, C.byref(o), seed, vp(outs), vp(costs), vp(moves),
+                                               C.byref(best), C.byref(st)))
 
-def _trace(ctx, problem, packed, init_pos, o, seed, chain, n, want_stats=False):
-    """Chain `chain` of `seed` alone, with its accepted epochs (tl_sim_anneal_trace_chain; chain 0 is tl_sim_anneal_trace)."""
-    from .. import _capi
-    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    out = np.empty(n, dtype=np.uint32)
-    cost = C.c_float()
-    st = _capi.TlStats()
-    cap = 1 << 14
-    while True:
-        log = np.empty((cap, 4), dtype=np.uint32)
-        ln = C.c_uint32()
-        ctx.check(ctx.lib.tl_sim_anneal_trace_chain(ctx.handle, vp(problem.xy), n, vp(packed), vp(init_pos), C.byref(o), seed, chain, vp(out),
-                                                    C.byref(cost), C.byref(st), vp(log), cap, C.byref(ln)))
-        if ln.value <= cap:
-            break
-        cap = int(ln.value)  # deterministic: once more with room for every accepted epoch
-    log = log[:ln.value]
-    if want_stats:
-        return out, cost.value, log, st.as_dict()
-    return out, cost.value, log
+    def single(out, cost, st):
+        ctx.check(lib.tl_sim_anneal(*inst, C.byref(o), seed, vp(out), C.byref(cost), C.byref(st)))
 
+    def trace(chain):
+        """Chain `chain` of `seed` alone, with its accepted epochs (tl_sim_anneal_trace_chain; chain 0 is tl_sim_anneal_trace)."""
+        from .. import _capi
+        out = np.empty(n, dtype=np.uint32)
+        cost = C.c_float()
+        st = _capi.TlStats()
+        cap = 1 << 14
+        while True:
+            log = np.empty((cap, 4), dtype=np.uint32)
+            ln = C.c_uint32()
+            ctx.check(lib.tl_sim_anneal_trace_chain(*inst, C.byref(o), seed, chain, vp(out), C.byref(cost), C.byref(st), vp(log), cap, C.byref(ln)))
+            if ln.value <= cap:
+                return out, cost.value, log[:ln.value], st.as_dict()
+            cap = int(ln.value)  # deterministic: once more with room for every accepted epoch
 
-def swap_cities(tour, frm, to):
-    """route.rs:102-113: positions from..=to of the open path reversed; returns the new tour"""
-    t = np.array(tour, copy=True)
-    t[frm:to + 1] = t[frm:to + 1][::-1]
-    return t
+    return solve_chains(problem, progress_tx, chains, population, single, trace, lambda log: replay_progress(problem, init_pos, log, progress_tx))
 
 
 def replay_progress(problem, init_pos, log, progress_tx):
     """The reference's message stream (simulated_annealing.rs:33-65) from the accepted epochs of tl_sim_anneal_trace."""
     from .or_opt import tour_length_f32
-    n = len(problem)
-    tour = np.arange(n, dtype=np.uint32) if init_pos is None else np.array(init_pos, dtype=np.uint32)
+    tour = start_tour(problem, init_pos)
     ids = problem.ids
     progress_tx("PathUpdate", ([int(v) for v in ids[tour]], float(tour_length_f32(problem, tour))))
     for _epoch, frm, to, bits in np.asarray(log, dtype=np.uint32).reshape(-1, 4):
         tour = swap_cities(tour, int(frm), int(to))
-        progress_tx("PathUpdate", ([int(v) for v in ids[tour]], float(np.array([bits], dtype=np.uint32).view(np.float32)[0])))
+        progress_tx("PathUpdate", ([int(v) for v in ids[tour]], float(bits_to_f32(bits))))
     progress_tx("Done", None)
     return tour

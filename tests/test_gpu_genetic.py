@@ -335,6 +335,9 @@ def test_errors(ctx):
     rc = ctx.lib.tl_genetic_algorithm(ctx.handle, _vp(b["xy"]), top + 1, None, None, 5, 0.5, 3, 1, _vp(out), C.byref(cost), None)
     assert rc == _capi.TL_ERR_UNSUPPORTED and "exceeds the limit" in err()
     assert ctx.lib.tl_genetic_algorithm(ctx.handle, None, 52, None, None, 5, 0.5, 3, 1, _vp(out), C.byref(cost), None) == _capi.TL_ERR_BADARG
+    assert err() == "tl_genetic_algorithm: NULL argument"
+    assert gpu_population(ctx, b["xy"], None, 52, None, 2 ** 32 - 3, 6, 3, 0.5, 3, 1)[0] == _capi.TL_ERR_BADARG
+    assert err() == "tl_genetic_algorithm_population: run ids beyond 2^32 - 1"
     log, ln = np.zeros((4, 4), dtype=np.uint32), C.c_uint32()
     assert ctx.lib.tl_genetic_algorithm_trace(ctx.handle, _vp(b["xy"]), 52, None, None, 5, 0.5, 3, 1, _vp(out), C.byref(cost), None, None, 4, C.byref(ln), None,
                                               0) == _capi.TL_ERR_BADARG

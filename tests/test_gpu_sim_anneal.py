@@ -225,8 +225,11 @@ def test_population_start_tours_and_chain_ids(ctx):
     check_population(ctx, b["xy"], 52, one, 1, 0, count, range(count))
     check_population(ctx, b["xy"], 52, own, count, 100, count, range(count))
     rc, *_ = gpu_population(ctx, b["xy"], None, 52, own, 2, 0, count, POP, 31)
-    assert rc == -1 and "init_count" in ctx.lib.tl_last_error(ctx.handle).decode()
+    assert rc == -1 and ctx.lib.tl_last_error(ctx.handle).decode() == "tl_sim_anneal_population: init_count is 2: 0 (city order), 1 (one start tour) or count (6)"
     assert gpu_population(ctx, b["xy"], None, 52, None, 1, 0, count, POP, 31)[0] == -1  # init_count 1 without a tour
+    assert ctx.lib.tl_last_error(ctx.handle).decode() == "tl_sim_anneal_population: NULL argument"
+    assert gpu_population(ctx, b["xy"], None, 52, None, 0, 2 ** 32 - 3, count, POP, 31)[0] == -1
+    assert ctx.lib.tl_last_error(ctx.handle).decode() == "tl_sim_anneal_population: chain ids beyond 2^32 - 1"
     bad = own.copy()
     bad[4, 0] = bad[4, 1]
     rc, *_ = gpu_population(ctx, b["xy"], None, 52, bad, count, 0, count, POP, 31)
@@ -289,6 +292,7 @@ def test_errors(ctx):
     rc = ctx.lib.tl_sim_anneal(ctx.handle, _vp(b["xy"]), top + 1, None, None, C.byref(o), 1, _vp(out), C.byref(cost), None)
     assert rc == _capi.TL_ERR_UNSUPPORTED and "LDS-resident limit" in err()
     assert ctx.lib.tl_sim_anneal(ctx.handle, None, 52, None, None, C.byref(o), 1, _vp(out), C.byref(cost), None) == _capi.TL_ERR_BADARG
+    assert err() == "tl_sim_anneal: NULL argument"
     assert TA.TL_FLAG_SA_NO_SPECULATION == 1 << 29
 
 
