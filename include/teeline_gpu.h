@@ -671,6 +671,61 @@ int tl_genetic_algorithm_plan(uint32_t n, uint32_t count, int cus, int lds_bytes
 int tl_ga_selftest_crossover(tl_ctx *ctx, const uint32_t *p1, const uint32_t *p2, uint32_t n, uint32_t from, uint32_t to, uint32_t *out1,
                              uint32_t *out2);
 
+/* ---- the ant colony solver (src/tsp/ant_colony.rs:97-252) ------------------------------------- */
+/* The reference's Ant System with its quirks kept, all arithmetic f32.  n <= 2: city order, no device.  With init_pos: best = that
+ * tour, tau0 = (float)num_ants / best_cost where best_cost > 0 (else 1) and one deposit of the tour before epoch 0; without: best =
+ * a shuffle of city order, tau0 = 1.  tau_min = tau0 1e-4f; eta_beta[u][v] = pow(1.0f / max(d(u, v), 1e-6f), beta), the diagonal 0;
+ * per epoch tau_alpha = pow(tau, alpha); every ant, in ant order, draws a start city and makes n - 1 selections (select_next: the
+ * weights tau_alpha eta over the unvisited cities in city order, their SEQUENTIAL f32 sum > 0 and finite, else eta only with r2, else
+ * the first candidate; roulette_select's strict acc > r sum, the last candidate when the walk is exhausted); its cost is
+ * tour_length_by_pos (closing edge first); cost < best_cost is strict and in ant order; then tau *= (1.0f - rate), floored at
+ * tau_min, and every ant deposits 1.0f / cost on both cells of each of its edges, in ant order (nothing where cost <= 0).  The
+ * result is the best tour and its cost.  epochs = 0 returns the start tour.
+ * TWO THINGS ARE THIS PROJECT'S SPECIFICATION, NOT THE REFERENCE'S (tests/_aco_oracle.py is the statement;
+ * csrc/aco_spec.h the text).  The draws: tl_genetic_algorithm's stream, u(seed, run, event, slot) (tl_aco_draw = tl_ga_draw); ant a
+ * of epoch g at step s owns the event (g num_ants + a) n + s: slot 0 of step 0 is the start city, ((u >> 32) n) >> 32; slots 1 and
+ * 2 of steps 1 .. n - 1 are r1 and r2, float(u >> 40) 2^-24; the shuffle is the Fisher-Yates pass of the events 2^58 + j, slot 26.
+ * The power: tl_aco_pow(x, a), a fixed f64 operation sequence without FMA or library calls, exact at a = 0, 1 and 2.
+ * Errors (AcoOptions::validate, mod.rs:1115-1153): alpha not finite or < 0, beta outside [0, 6], evaporation_rate outside (0, 1),
+ * num_ants = 0, init_pos not a permutation: TL_ERR_BADARG.  num_ants > 4096, n > tl_ant_colony_max_n, epochs x num_ants x n > 2^58,
+ * a context whose flags hold a bit no flag has: TL_ERR_UNSUPPORTED, before anything of size n is read.  dm_packed as in tl_sim_anneal.
+ * tl_ant_colony runs run 0.  stats (optional): sweeps = epochs, candidates = tours constructed, moves = improving ants, reversed =
+ * selections that left the primary weights; tl_ant_colony_population's stats are these summed over its runs (sweeps = epochs x count).
+ * tl_ant_colony_trace: the same plus 3 num_ants words per epoch: every ant's cost bits, then every ant's start city, then every
+ * ant's count of fallback selections.  *log_len counts the epochs; the log holds the first log_cap.  route_log (optional, route_cap
+ * rows of n + 3 words: epoch, ant, cost bits, the tour; row 0 is the start tour with epoch = ant = 0xFFFFFFFF): the improving ants
+ * in the order they improved; *route_len (optional) counts the rows there are.  A caller replays the reference's messages from it:
+ * PathUpdate(row 0), per epoch a PathUpdate per row of that epoch and EpochUpdate(epoch), then Done.  tl_ant_colony_trace_run: the
+ * same for run `run` of the seed.
+ * tl_ant_colony_population: runs first_run .. first_run + count - 1, each its own stream of draws, at once (more runs than the
+ * workspace limit holds — tl_ant_colony_plan's per_launch — go in further sequences).  init_count: 0, 1 (one tour for every run) or
+ * count.  out_pos, out_costs, *best_index, count == 0: as tl_tabu_search_population.  Run c of any batch equals first_run = c, count = 1.
+ * Host-only queries: tl_aco_draw; tl_aco_pow; tl_ant_colony_plan — the runs one launch sequence holds, the threads of a construct
+ * workgroup and the workspace bytes of min(count, per_launch) runs (outputs optional; all 0 where n is outside 3 .. the limit or
+ * num_ants outside 1 .. 4096; the entries plan with 8 GiB); tl_ant_colony_max_n: the largest n (a construct workgroup keeps 12 bytes
+ * per city in LDS beside its tiles; a run keeps 12 n^2 bytes of workspace).
+ * tl_aco_selftest_select: the DEVICE's selection for one ant on a given row: weights and eta hold n f32 each, visited n words (non-zero:
+ * not a candidate; at least one candidate, 1 <= n <= the limit, else TL_ERR_BADARG).  out[0] the chosen city, out[1] the path that
+ * chose it (0 primary, 1 eta only, 2 first candidate), out[2] the primary total's bits, out[3] the eta total's bits (0 on path 0). */
+uint32_t tl_ant_colony_max_n(const tl_ctx *ctx);
+int tl_ant_colony(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t epochs, float alpha, float beta,
+                  float evaporation_rate, uint32_t num_ants, uint64_t seed, uint32_t *out_pos, float *out_cost, tl_stats *stats);
+int tl_ant_colony_trace(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t epochs, float alpha, float beta,
+                        float evaporation_rate, uint32_t num_ants, uint64_t seed, uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *log,
+                        uint32_t log_cap, uint32_t *log_len, uint32_t *route_log, uint32_t route_cap, uint32_t *route_len);
+int tl_ant_colony_trace_run(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t epochs, float alpha,
+                            float beta, float evaporation_rate, uint32_t num_ants, uint64_t seed, uint32_t run, uint32_t *out_pos, float *out_cost,
+                            tl_stats *stats, uint32_t *log, uint32_t log_cap, uint32_t *log_len, uint32_t *route_log, uint32_t route_cap,
+                            uint32_t *route_len);
+int tl_ant_colony_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
+                             uint32_t first_run, uint32_t count, uint32_t epochs, float alpha, float beta, float evaporation_rate, uint32_t num_ants,
+                             uint64_t seed, uint32_t *out_pos, float *out_costs, uint32_t *best_index, tl_stats *stats);
+uint64_t tl_aco_draw(uint64_t seed, uint32_t run, uint64_t event, uint32_t slot);
+float tl_aco_pow(float x, float a);
+int tl_ant_colony_plan(uint32_t n, uint32_t num_ants, uint32_t count, int cus, int lds_bytes, uint64_t workspace_bytes, uint32_t *per_launch, int *threads,
+                       uint64_t *workspace_needed);
+int tl_aco_selftest_select(tl_ctx *ctx, const float *weights, const float *eta, const uint32_t *visited, uint32_t n, float r1, float r2, uint32_t *out);
+
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts
  * first..first+count as above; seed ignored otherwise).  d_out_pos: count x n u32, d_out_cost: count f32,

@@ -125,6 +125,17 @@ unsafe extern "C" {
                                        epochs: u32, mutation_probability: f32, n_elite: u32, seed: u64, out_pos: *mut u32, out_costs: *mut f32,
                                        best_index: *mut u32, stats: *mut Stats) -> i32;
     fn tl_ga_draw(seed: u64, run: u32, event: u64, slot: u32) -> u64;
+    fn tl_ant_colony_max_n(ctx: *const TlCtx) -> u32;
+    fn tl_ant_colony(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, epochs: u32, alpha: f32, beta: f32,
+                     evaporation_rate: f32, num_ants: u32, seed: u64, out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats) -> i32;
+    fn tl_ant_colony_trace_run(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, epochs: u32, alpha: f32, beta: f32,
+                               evaporation_rate: f32, num_ants: u32, seed: u64, run: u32, out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats,
+                               log: *mut u32, log_cap: u32, log_len: *mut u32, route_log: *mut u32, route_cap: u32, route_len: *mut u32) -> i32;
+    fn tl_ant_colony_population(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, init_count: u32, first_run: u32,
+                                count: u32, epochs: u32, alpha: f32, beta: f32, evaporation_rate: f32, num_ants: u32, seed: u64, out_pos: *mut u32,
+                                out_costs: *mut f32, best_index: *mut u32, stats: *mut Stats) -> i32;
+    fn tl_aco_draw(seed: u64, run: u32, event: u64, slot: u32) -> u64;
+    fn tl_aco_pow(x: f32, a: f32) -> f32;
     fn tl_nearest_neighbor(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, n_nearest: u32,
                            out_pos: *mut u32, out_cost: *mut f32) -> c_int;
     fn tl_greedy_edge(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
@@ -603,6 +614,29 @@ impl Context {
                                  &mut t.cost, &mut t.stats)
         };
         self.check(rc).map(|_| t)
+    }
+
+    /// `ant_colony::solve` (ant_colony.rs:97-252), run 0 of `seed`.  The algorithm is the reference's; its random draws and its power
+    /// function are the library's own specification (include/teeline_gpu.h).  (Written against the header; not compiled here: no Rust
+    /// toolchain on the build machine, see scripts/check_rust.sh.)
+    #[allow(clippy::too_many_arguments)]
+    pub fn ant_colony(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, epochs: u32, alpha: f32, beta: f32, evaporation_rate: f32,
+                      num_ants: u32, seed: u64) -> Result<Tour, Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        // SAFETY: as in two_opt.
+        let rc = unsafe {
+            tl_ant_colony(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), epochs, alpha, beta, evaporation_rate, num_ants, seed,
+                          t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats)
+        };
+        self.check(rc).map(|_| t)
+    }
+
+    /// Largest n of `ant_colony` (a construct workgroup keeps 12 bytes per city in LDS beside its tiles).
+    pub fn ant_colony_max_n(&self) -> u32 {
+        // SAFETY: a live context.
+        unsafe { tl_ant_colony_max_n(self.raw) }
     }
 
     /// Run `run` of `seed` with every generation `[best index, fitness bits, cost bits, population length]` and its best route, from which

@@ -63,6 +63,8 @@ SYMBOLS = [
     "tl_tabu_draw",
     "tl_genetic_algorithm", "tl_genetic_algorithm_trace", "tl_genetic_algorithm_trace_run", "tl_genetic_algorithm_population", "tl_genetic_algorithm_max_n",
     "tl_genetic_algorithm_plan", "tl_ga_draw", "tl_ga_selftest_crossover",
+    "tl_ant_colony", "tl_ant_colony_trace", "tl_ant_colony_trace_run", "tl_ant_colony_population", "tl_ant_colony_max_n", "tl_ant_colony_plan",
+    "tl_aco_draw", "tl_aco_pow", "tl_aco_selftest_select",
 ]
 
 
@@ -199,5 +201,20 @@ def load():
     L.tl_ga_draw.restype = u64
     L.tl_genetic_algorithm_plan.argtypes = [u32, u32, i32, i32, u64, C.POINTER(u32), C.POINTER(i32), C.POINTER(u64)]
     L.tl_ga_selftest_crossover.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp]
+    f32 = C.c_float
+    L.tl_ant_colony_max_n.argtypes = [vp]
+    L.tl_ant_colony_max_n.restype = u32
+    L.tl_ant_colony.argtypes = [vp, vp, u32, vp, vp, u32, f32, f32, f32, u32, u64, vp, f32p, C.POINTER(TlStats)]
+    L.tl_ant_colony_trace.argtypes = [vp, vp, u32, vp, vp, u32, f32, f32, f32, u32, u64, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32), vp, u32,
+                                      C.POINTER(u32)]
+    L.tl_ant_colony_trace_run.argtypes = [vp, vp, u32, vp, vp, u32, f32, f32, f32, u32, u64, u32, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32), vp, u32,
+                                          C.POINTER(u32)]
+    L.tl_ant_colony_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, u32, f32, f32, f32, u32, u64, vp, vp, C.POINTER(u32), C.POINTER(TlStats)]
+    L.tl_aco_draw.argtypes = [u64, u32, u64, u32]
+    L.tl_aco_draw.restype = u64
+    L.tl_aco_pow.argtypes = [f32, f32]
+    L.tl_aco_pow.restype = f32
+    L.tl_ant_colony_plan.argtypes = [u32, u32, u32, i32, i32, u64, C.POINTER(u32), C.POINTER(i32), C.POINTER(u64)]
+    L.tl_aco_selftest_select.argtypes = [vp, vp, vp, vp, u32, f32, f32, vp]
     _lib = L
     return L

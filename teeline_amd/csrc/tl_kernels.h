@@ -390,6 +390,40 @@ hipError_t launch_ga_breed(const GaArgs &A, uint32_t runs, uint32_t next_len, hi
 hipError_t launch_ga_selftest_crossover(const uint16_t *p1, const uint16_t *p2, uint32_t n, uint32_t from, uint32_t to, uint16_t *out1, uint16_t *out2,
                                         hipStream_t s);
 
+// ant_colony.hip — the ant colony solver, the run (colony) a grid dimension, three launches per epoch
+struct AcoArgs {
+    const float2 *xy;       // n cities, city order (coordinate form)
+    const float *dm_full;   // the matrix expanded to row-major n x n, or nullptr
+    const uint32_t *init;   // the initial tour(s), or nullptr (a shuffle)
+    uint32_t init_stride;   // 0: one tour for every run, n: one per run
+    float *tau, *eta, *w;   // [runs][mat_stride] pheromone, eta^beta, tau^alpha eta^beta
+    uint16_t *tour, *succ, *pred;  // [runs][num_ants][n] every ant's tour by position, and its successor / predecessor by city
+    float *cost;            // [runs][num_ants] the ants' tour lengths
+    uint32_t *start, *fb;   // [runs][num_ants] their start cities and their counts of fallback selections
+    uint32_t *state;        // [runs][8] best cost bits, improvements, fallback selections (lo), tau0 bits, tau_min bits, fallbacks (hi)
+    uint32_t *out_pos;      // [runs][n] the best tour so far
+    float *out_cost;        // [runs] its cost
+    uint32_t *log;          // optional: [log_cap][3 num_ants] cost bits, start cities, fallback counts per epoch of run 0
+    uint32_t *route_log;    // optional: [route_cap][n + 3] epoch, ant, cost bits, tour: the start tour, then every improving ant of run 0
+    uint64_t seed;
+    uint64_t mat_stride;    // elements between two runs' matrices (>= n * n)
+    uint32_t log_cap, route_cap;
+    uint32_t first_run;     // stream id of the launch's run 0
+    uint32_t n, num_ants;
+    uint32_t epoch;
+    uint32_t pre;           // update: the deposit of the initial tour before epoch 0 (no evaporation; one "ant", or none)
+    float alpha, beta, rate;
+};
+size_t ant_colony_lds_bytes(uint32_t n);     // LDS of a construct workgroup
+uint32_t ant_colony_max_n(int lds_budget);
+int ant_colony_threads();
+hipError_t launch_aco_init(const AcoArgs &A, uint32_t runs, hipStream_t s);    // start tour, its cost, tau0; then tau and eta
+hipError_t launch_aco_construct(const AcoArgs &A, uint32_t runs, hipStream_t s);
+hipError_t launch_aco_best(const AcoArgs &A, uint32_t runs, hipStream_t s);
+hipError_t launch_aco_update(const AcoArgs &A, uint32_t runs, int lds_budget, hipStream_t s);
+hipError_t launch_aco_selftest_select(const float *weights, const float *eta, const uint32_t *visited, uint32_t n, float r1, float r2, uint32_t *out,
+                                      hipStream_t s);
+
 // lk.hip
 struct LkState {           // device-side state machine of the multi-CU LK variant
     uint32_t key;            // min pair index with a valid chain in the current scan (0xFFFFFFFF: none)

@@ -169,7 +169,7 @@ struct Solution {  // mod.rs:1753-1814
     const std::vector<size_t> &route() const { return route_; }
 };
 
-enum class ProgressKind { PathUpdate, CityChange, Done };
+enum class ProgressKind { PathUpdate, CityChange, Done, EpochUpdate };  // EpochUpdate(epoch): the epoch is the one entry of the id list
 using ProgressFn = std::function<void(ProgressKind, const std::vector<size_t> &, float)>;  // progress.rs ProgressMessage
 
 inline bool validate_tour(const std::vector<size_t> &tour, const std::vector<KDPoint> &cities)  // mod.rs:1620-1634
@@ -1079,8 +1079,84 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const GAOptions &
 }
 }  // namespace genetic_algorithm
 
+namespace ant_colony {  // ant_colony.rs:97-252
+struct AcoOptions {  // mod.rs:1082-1153
+    HeuristicOptions heuristic;
+    float alpha = 1.0f, beta = 2.0f, evaporation_rate = 0.5f;
+    size_t num_ants = 25;
+    AcoOptions() { heuristic.epochs = 150; }
+    std::string validate() const
+    {
+        if (!std::isfinite(alpha) || alpha < 0.0f) return "alpha must be >= 0 (got " + std::to_string(alpha) + ")";
+        if (!(beta >= 0.0f && beta <= 6.0f)) return "beta must be in [0, 6] (got " + std::to_string(beta) + ")";
+        if (!std::isfinite(evaporation_rate) || evaporation_rate <= 0.0f || evaporation_rate >= 1.0f)
+            return "evaporation_rate must be in (0, 1) (got " + std::to_string(evaporation_rate) + ")";
+        if (num_ants == 0) return "num_ants must be >= 1";
+        return "";
+    }
+};
+// The algorithm is the reference's; its random draws and its power function are this project's specification
+// (include/teeline_gpu.h).  runs > 1: runs 0 .. runs-1 of the seed at once, the best one returned (lowest cost, then lowest run).
+// With a progress callback the reference's messages — PathUpdate(start tour), per epoch a PathUpdate per improving ant in ant order
+// and EpochUpdate(epoch), then Done (ant_colony.rs:141-147,225-231,241-248) — are replayed from that run's route log.
+inline Solution solve(Context &ctx, const TspProblem &problem, const AcoOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
+                      uint64_t seed = 1, uint32_t runs = 1)
+{
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size();
+    const uint32_t epochs = (uint32_t)opts.heuristic.epochs, ants = (uint32_t)std::min<size_t>(opts.num_ants, 0xFFFFFFFFu);
+    const float a = opts.alpha, b = opts.beta, r = opts.evaporation_rate;
+    std::vector<uint32_t> init, out(n);
+    if (init_tour) init = problem.positions_of(*init_tour);
+    const uint32_t *ip = init_tour ? init.data() : nullptr;
+    float cost = 0.f;
+    tl_stats st{};
+    uint32_t run = 0;
+    if (runs > 1) {
+        std::vector<uint32_t> outs((size_t)runs * n);
+        std::vector<float> costs(runs);
+        ctx.check(tl_ant_colony_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, runs, epochs, a, b, r, ants, seed, outs.data(),
+                                           costs.data(), &run, &st));
+        std::copy(outs.begin() + (size_t)run * n, outs.begin() + (size_t)(run + 1) * n, out.begin());
+        cost = costs[run];
+        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
+    } else if (!(progress_tx && *progress_tx)) {
+        ctx.check(tl_ant_colony(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, epochs, a, b, r, ants, seed, out.data(), &cost, &st));
+        return detail::finish(problem, out, cost, st, nullptr);
+    }
+    uint32_t len = 0, rows = 0, cap = 64;
+    std::vector<uint32_t> log((size_t)3 * std::max(ants, 1u), 0u), routes;
+    for (;;) {  // the route log holds every improving ant: ask again with the count where 64 rows were too few
+        routes.assign((size_t)cap * (n + 3), 0u);
+        ctx.check(tl_ant_colony_trace_run(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, epochs, a, b, r, ants, seed, run, out.data(), &cost, &st,
+                                          log.data(), 1u, &len, routes.data(), cap, &rows));
+        if (rows <= cap) break;
+        cap = rows;
+    }
+    std::vector<size_t> route(n);
+    const auto path_update = [&](uint32_t k) {
+        const uint32_t *rec = routes.data() + (size_t)k * (n + 3);
+        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[rec[3 + q]].id;
+        float d;
+        std::memcpy(&d, &rec[2], 4);
+        (*progress_tx)(ProgressKind::PathUpdate, route, d);
+    };
+    if (rows > 0) {  // (n <= 2: no row, the reference sends Done alone)
+        path_update(0);
+        uint32_t k = 1;
+        for (uint32_t g = 0; g < epochs; ++g) {
+            for (; k < rows && routes[(size_t)k * (n + 3)] == g; ++k) path_update(k);
+            (*progress_tx)(ProgressKind::EpochUpdate, std::vector<size_t>{g}, 0.0f);
+        }
+    }
+    Solution s = detail::finish(problem, out, cost, st, nullptr);
+    (*progress_tx)(ProgressKind::Done, s.route_, cost);
+    return s;
+}
+}  // namespace ant_colony
+
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
-enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm };
+enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony };
 
 inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
 {
@@ -1099,8 +1175,9 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
                                                                               // seeded chain of its own specification, asked for by its long name)
     else if (s == "tabu_search") out = Solvers::TabuSearch;  // (the alias `tabu` stays refused, below, as `sa` does)
     else if (s == "genetic_algorithm") out = Solvers::GeneticAlgorithm;  // (the alias `ga` likewise)
+    else if (s == "ant_colony") out = Solvers::AntColony;  // (the alias `aco` likewise)
     else {
-        static const char *cpu_only[] = {"aco", "ant_colony", "branch_bound",
+        static const char *cpu_only[] = {"aco", "branch_bound",
                                          "cs", "cuckoo_search", "fpa", "flower_pollination", "fourier", "ga", "gsa",
                                          "gravitational_search", "pso", "particle_swarm", "sa",
                                          "som", "kohonen", "kohonen_som", "stochastic_hill", "tabu"};
@@ -1109,6 +1186,7 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
                 why = "solver `" + s + "` is not accelerated by this build (nn, gec, sav, chr, bhk, 2opt, 3opt, or_opt, lk, shuffle are, and simulated_annealing under its long name)";
                 if (s == "tabu") why += "; the seeded tabu search of this build is `tabu_search`";
                 if (s == "ga") why += "; the seeded genetic algorithm of this build is `genetic_algorithm`";
+                if (s == "aco") why += "; the seeded ant colony of this build is `ant_colony`";
                 return false;
             }
         why = "unknown solver";  // FromStr's Err (mod.rs:588)
@@ -1132,6 +1210,7 @@ inline const char *solver_name(Solvers s)
         case Solvers::SimulatedAnnealing: return "simulated_annealing";
         case Solvers::TabuSearch: return "tabu_search";
         case Solvers::GeneticAlgorithm: return "genetic_algorithm";
+        case Solvers::AntColony: return "ant_colony";
         default: return "shuffle";
     }
 }
@@ -1146,6 +1225,8 @@ struct StageOptions {
     uint32_t tabu_chains = 1;  // a tabu_search stage likewise
     genetic_algorithm::GAOptions ga;
     uint32_t ga_runs = 1;  // a genetic_algorithm stage breeds this many runs and keeps the best
+    ant_colony::AcoOptions aco;
+    uint32_t aco_runs = 1;  // an ant_colony stage runs this many colonies and keeps the best
     uint64_t seed = 1;  // LK kicks, shuffle, SA, tabu and GA draws
     const ProgressFn *progress = nullptr;  // handed to every stage's solve() (the reference's CLI passes None; teeline-qt a sender)
 };
@@ -1210,6 +1291,7 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             case Solvers::SimulatedAnnealing: sol = simulated_annealing::solve(ctx, problem, o.sa, o.progress, init, o.seed, o.sa_chains); break;
             case Solvers::TabuSearch: sol = tabu_search::solve(ctx, problem, o.heuristic, o.progress, init, o.seed, o.tabu_chains); break;
             case Solvers::GeneticAlgorithm: sol = genetic_algorithm::solve(ctx, problem, o.ga, o.progress, init, o.seed, o.ga_runs); break;
+            case Solvers::AntColony: sol = ant_colony::solve(ctx, problem, o.aco, o.progress, init, o.seed, o.aco_runs); break;
         }
         const auto t1 = std::chrono::steady_clock::now();
         const uint64_t ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();

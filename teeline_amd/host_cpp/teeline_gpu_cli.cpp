@@ -14,6 +14,9 @@
 //     genetic  : genetic_algorithm (long name only: `ga` stays refused) breeds --epochs generations of seeded draws (--seed) with
 //               --mutation-probability P and --n-elite N (GAOptions, mod.rs:815-846); --ga-runs K (own flag: K runs of the seed at once,
 //               the best kept); `solve genetic_algorithm` alone is pipeline(shuffle, genetic_algorithm) (mod.rs:144-157, 2152)
+//     colony   : ant_colony (long name only: `aco` stays refused) runs --epochs epochs (default 150) of seeded draws (--seed) with --alpha A
+//               --beta B --evaporation-rate R --num-ants N (AcoOptions, mod.rs:1082-1153); --runs K (K colonies of the seed at once, the
+//               best kept); `solve ant_colony` alone is pipeline(shuffle, ant_colony) (mod.rs:2158)
 //     solve   : 2opt / 3opt / or_opt / lk auto-expand to pipeline(nn, solver) unless --no-seed (main.rs:387-397, mod.rs:129-139);
 //               gec (greedy_edge), sav (savings) and chr (christofides) are constructions and run alone; so does bhk (bellman_karp),
 //               the exact solver (n <= 26, mod.rs:2137) — as a later pipeline stage it ignores its seed
@@ -51,12 +54,13 @@ struct Args {
 {
     if (why) std::fprintf(stderr, "error: %s\n", why);
     std::fprintf(stderr,
-                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|genetic_algorithm|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
+                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|genetic_algorithm|ant_colony|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
                  "                         [--optimal-tour FILE] [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P]\n"
                  "                         [--n_nearest K] [--max-depth D] [--seed S] [--best-sweep] [--device N] [--stats]\n"
                  "                         [--progress-digest] [--exact-walk]\n"
                  "                         [--cooling-rate C] [--min-temperature LO] [--max-temperature HI] [--chains K] [--tabu-chains K]\n"
                  "                         [--mutation-probability P] [--n-elite N] [--ga-runs K]\n"
+                 "                         [--alpha A] [--beta B] [--evaporation-rate R] [--num-ants N] [--runs K]\n"
                  "       teeline-gpu pipeline --steps=nn,2opt,... | --steps=greedy_edge,2opt,... | --steps=savings,2opt,... | --steps=christofides,lk,... [-i FILE] [options as above]\n"
                  "       teeline-gpu solvers [--short]\n");
     std::exit(2);  // clap's usage-error exit code
@@ -109,7 +113,7 @@ Args parse(int argc, char **argv)
         else if (s == "--output-format") a.output_format = val();
         else if (s == "--optimal-tour") a.optimal_tour = val();
         else if (s == "--distance-type") a.distance_type = val();
-        else if (s == "--epochs") a.opt.heuristic.epochs = a.opt.lk.heuristic.epochs = a.opt.sa.heuristic.epochs = a.opt.ga.heuristic.epochs = parse_usize(s, val());
+        else if (s == "--epochs") a.opt.heuristic.epochs = a.opt.lk.heuristic.epochs = a.opt.sa.heuristic.epochs = a.opt.ga.heuristic.epochs = a.opt.aco.heuristic.epochs = parse_usize(s, val());
         else if (s == "--cooling-rate" || s == "--cooling_rate") a.opt.sa.cooling_rate = std::stof(val());
         else if (s == "--min-temperature" || s == "--min_temperature") a.opt.sa.min_temperature = std::stof(val());
         else if (s == "--max-temperature" || s == "--max_temperature") a.opt.sa.max_temperature = std::stof(val());
@@ -117,6 +121,11 @@ Args parse(int argc, char **argv)
         else if (s == "--mutation-probability" || s == "--mutation_probability") a.opt.ga.mutation_probability = std::stof(val());
         else if (s == "--n-elite" || s == "--n_elite") a.opt.ga.n_elite = parse_usize(s, val());
         else if (s == "--ga-runs" || s == "--ga_runs") a.opt.ga_runs = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
+        else if (s == "--alpha") a.opt.aco.alpha = std::stof(val());
+        else if (s == "--beta") a.opt.aco.beta = std::stof(val());
+        else if (s == "--evaporation-rate" || s == "--evaporation_rate") a.opt.aco.evaporation_rate = std::stof(val());
+        else if (s == "--num-ants" || s == "--num_ants") a.opt.aco.num_ants = parse_usize(s, val());
+        else if (s == "--runs") a.opt.aco_runs = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--chains") a.opt.sa_chains = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--platoo_epochs" || s == "--platoo-epochs") a.opt.heuristic.platoo_epochs = a.opt.lk.heuristic.platoo_epochs = parse_usize(s, val());
         else if (s == "--n_nearest" || s == "--n-nearest") a.opt.heuristic.n_nearest = a.opt.lk.heuristic.n_nearest = parse_usize(s, val());
@@ -152,6 +161,13 @@ Args parse(int argc, char **argv)
     }
     {   // GAOptions::validate (mod.rs:833-846)
         const std::string why = a.opt.ga.validate();
+        if (!why.empty()) {
+            std::fprintf(stderr, "error: %s\n", why.c_str());
+            std::exit(1);
+        }
+    }
+    {   // AcoOptions::validate (mod.rs:1115-1153)
+        const std::string why = a.opt.aco.validate();
         if (!why.empty()) {
             std::fprintf(stderr, "error: %s\n", why.c_str());
             std::exit(1);
@@ -252,7 +268,7 @@ int run(int argc, char **argv)
                 // auto_expand_with_nn (mod.rs:129-139): deterministic local searches are seeded with a nearest-neighbour stage
                 const bool expand = s == Solvers::TwoOpt || s == Solvers::ThreeOpt || s == Solvers::LinKernighan || s == Solvers::OrOpt || s == Solvers::TabuSearch;
                 if (!a.no_seed && expand) stages = {Solvers::NearestNeighbor, s};
-                else if (!a.no_seed && (s == Solvers::SimulatedAnnealing || s == Solvers::GeneticAlgorithm)) stages = {Solvers::RandomShuffle, s};  // mod.rs:144-157
+                else if (!a.no_seed && (s == Solvers::SimulatedAnnealing || s == Solvers::GeneticAlgorithm || s == Solvers::AntColony)) stages = {Solvers::RandomShuffle, s};  // mod.rs:144-157
                 else stages = {s};
             }
         } else {
@@ -315,12 +331,12 @@ int run(int argc, char **argv)
         // and the message stream — which this mirror replays from the *_trace entries — is summarised on stderr: counts per kind and
         // an FNV-1a digest over (kind, ids as u64, f32 bits) per message (Done: the kind only), comparable across the mirrors
         struct Digest {
-            uint64_t h = 1469598103934665603ull, n[3] = {0, 0, 0};
+            uint64_t h = 1469598103934665603ull, n[4] = {0, 0, 0, 0};
             void byte(uint8_t b) { h = (h ^ b) * 1099511628211ull; }
             void word(uint64_t v, int bytes) { for (int k = 0; k < bytes; ++k) byte((uint8_t)(v >> (8 * k))); }
         } dg;
         ProgressFn on_progress = [&dg](ProgressKind kind, const std::vector<size_t> &ids, float v) {
-            const int k = kind == ProgressKind::PathUpdate ? 0 : kind == ProgressKind::CityChange ? 1 : 2;
+            const int k = kind == ProgressKind::PathUpdate ? 0 : kind == ProgressKind::CityChange ? 1 : kind == ProgressKind::EpochUpdate ? 3 : 2;
             dg.n[k] += 1;
             dg.byte((uint8_t)k);
             if (k == 2) return;
@@ -347,9 +363,12 @@ int run(int argc, char **argv)
             runs_json += "]}";
         }
         const auto t_out = clk::now();
-        if (a.progress_digest)
-            std::fprintf(stderr, "progress: path_updates=%llu city_changes=%llu done=%llu digest=%016llx\n", (unsigned long long)dg.n[0],
+        if (a.progress_digest) {
+            std::fprintf(stderr, "progress: path_updates=%llu city_changes=%llu done=%llu digest=%016llx", (unsigned long long)dg.n[0],
                          (unsigned long long)dg.n[1], (unsigned long long)dg.n[2], (unsigned long long)dg.h);
+            if (dg.n[3]) std::fprintf(stderr, " epoch_updates=%llu", (unsigned long long)dg.n[3]);  // (ant_colony stages only)
+            std::fprintf(stderr, "\n");
+        }
         const Solution &tour = outcomes.back().solution;
         if (!json_mode) std::fputs(cli::format_solution(tour, false).c_str(), stdout);
         cli::OptimalComparison cmp;
