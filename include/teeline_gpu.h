@@ -726,6 +726,73 @@ int tl_ant_colony_plan(uint32_t n, uint32_t num_ants, uint32_t count, int cus, i
                        uint64_t *workspace_needed);
 int tl_aco_selftest_select(tl_ctx *ctx, const float *weights, const float *eta, const uint32_t *visited, uint32_t n, float r1, float r2, uint32_t *out);
 
+/* ---- the particle swarm solver (src/tsp/particle_swarm.rs:22-129) ---------------------------- */
+/* The reference's discrete particle swarm with its quirks kept.  P = max(n_nearest, 30) particles (the count rides on
+ * HeuristicOptions::n_nearest), v_max = max(ceil(0.35 n), 1) in f64.  Particle 0 starts on init_pos if given, every other particle
+ * (and particle 0 without init_pos) on a Fisher-Yates shuffle of city order; velocities start empty; pbest = the start positions,
+ * their costs tour_length as everywhere here (closing edge first, sequential f32); gbest = the FIRST minimum.  Epoch e:
+ * w = 0.9 - (0.9 - 0.4) (e / max(epochs, 1)) in f64; the particles IN INDEX ORDER: r1, r2 in [0, 1);
+ * inertia_keep = round(w len(v)), cog_keep = round((1.5 r1) len(cog)), soc_keep = round((1.5 r2) len(soc)), round half away from
+ * zero, a keep above its length clamped by `take`; cog = swap_sequence(pos, pbest) and soc = swap_sequence(pos, gbest), both from
+ * the SAME pos, lists of position pairs (route.rs:118-134: for i = 0 .. n - 2, where pos[i] differs from the target, the pair (i, j)
+ * with j > i the place of target[i], applied before i + 1 is looked at); new_vel = v[:inertia_keep] ++ cog[:cog_keep] ++
+ * soc[:soc_keep] truncated to v_max; pos = the swaps applied in order; cost < pbest_cost updates pbest, cost < gbest_cost updates
+ * gbest AT ONCE — the next particle of the same epoch sees it.  The result is gbest and its cost; epochs = 0 returns the start gbest.
+ * TWO THINGS ARE THIS PROJECT'S SPECIFICATION, NOT THE REFERENCE'S (tests/_pso_oracle.py is the statement;
+ * csrc/pso_spec.h the text).  The draws: tl_genetic_algorithm's stream, u(seed, run, event, slot) (tl_pso_draw = tl_ga_draw);
+ * particle i of epoch e owns the event e P + i, r1 on slot 0 and r2 on slot 1, each (u >> 11) 2^-53; start particle i owns the events
+ * 2^58 + i n + j, slot 26: step j = n - 1 .. 1 of its pass, swap(a[j], a[position(u, j + 1)]).  The rounding: tl_pso_keep(x) =
+ * t + (x - t >= 0.5) with t = trunc(x) for x >= 0 (0 for x < 0 or NaN), every f64 product left to right without FMA; tl_pso_weight
+ * is w above.
+ * On the device (csrc/particle_swarm.hip) every particle of an epoch is moved at once against the epoch-start gbest; a commit
+ * launch then walks the particles in index order and, from the first one that improves gbest, moves the later ones again against
+ * the new gbest, one after the other — the reference's order in two launches per epoch.  The swap sequences come from their orbit
+ * form, one lane per position.
+ * opts NULL: the defaults (10 000 epochs, n_nearest 3).  n = 0: TL_OK, nothing written, cost 0 (the reference returns the empty
+ * route, as tl_ant_colony).  n = 1: the one city at cost 0, no device work.  init_pos not a permutation: TL_ERR_BADARG.
+ * epochs = 2^32 - 1, more than 4096 particles, n > tl_particle_swarm_max_n, a context whose flags hold a bit no flag has:
+ * TL_ERR_UNSUPPORTED, before anything of size n is read or allocated.  dm_packed as in tl_sim_anneal.
+ * tl_particle_swarm runs run 0.  stats (optional): sweeps = epochs, candidates = particle steps (epochs x P), moves = gbest
+ * improvements; tl_particle_swarm_population's stats are these summed over its runs.
+ * tl_particle_swarm_trace: run `run` of the seed, the same result plus a log of 4 words per record: epoch, particle, cost bits,
+ * the index of the record's route in route_log (0xFFFFFFFF beyond route_cap).  Record 0 is the start gbest (epoch 0xFFFFFFFF, the
+ * particle it came from); every gbest improvement follows in the order it happened.  *log_len counts the records there are; the log
+ * holds the first log_cap, route_log (optional, route_cap x n) the routes of the first route_cap.  epoch_log (optional, epoch_cap
+ * rows of 2 P words): for the first epoch_cap epochs every particle's cost bits, then every particle's velocity length, as the
+ * epoch leaves them.  A caller replays the reference's messages from the log: PathUpdate(record 0), per epoch a PathUpdate per record
+ * of that epoch and EpochUpdate(epoch), then Done.  n <= 1: record 0 alone, every epoch row zero.
+ * tl_particle_swarm_population: runs first_run .. first_run + count - 1, each its own stream of draws, at once (more runs than the
+ * workspace limit holds — tl_particle_swarm_plan's per_launch — go in further launch sequences).  init_count: 0, 1 (one tour for
+ * every run) or count.  out_pos, out_costs, out_moves (improvements per run), *best_index, count == 0: as tl_sim_anneal_population.
+ * Run c of any batch equals first_run = c, count = 1.
+ * Host-only queries: tl_pso_draw; tl_pso_weight; tl_pso_keep; tl_particle_swarm_plan — the particles, the threads of a particle's
+ * workgroup and the runs one launch sequence holds (outputs optional; all 0 where n is outside 2 .. the limit or P > 4096; a flag bit
+ * no flag has: TL_ERR_UNSUPPORTED; the entries plan with 8 GiB).  tl_particle_swarm_max_n: the largest n (a workgroup keeps
+ * 14 n + 4 v_max bytes in LDS).
+ * tl_pso_selftest_swap_sequence: the DEVICE's swap sequence on `count` given pairs of permutations of 0..n-1 (from, to: count x n;
+ * 1 <= n <= the limit, 1 <= count <= 65535, else TL_ERR_BADARG): out_len[c] is the length of pair c's sequence, out_pairs
+ * (count x n x 2) its pairs (i, j), 0xFFFFFFFF beyond the length. */
+typedef struct tl_pso_opts { /* HeuristicOptions, src/tsp/mod.rs:596-611: what particle_swarm reads of it */
+    uint32_t epochs;
+    uint32_t n_nearest; /* P = max(n_nearest, 30) */
+} tl_pso_opts;
+uint32_t tl_particle_swarm_max_n(const tl_ctx *ctx);
+int tl_particle_swarm(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_pso_opts *opts, uint64_t seed,
+                      uint32_t *out_pos, float *out_cost, tl_stats *stats);
+int tl_particle_swarm_trace(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_pso_opts *opts,
+                            uint64_t seed, uint32_t run, uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *log, uint32_t log_cap,
+                            uint32_t *log_len, uint32_t *route_log, uint32_t route_cap, uint32_t *epoch_log, uint32_t epoch_cap);
+int tl_particle_swarm_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
+                                 uint32_t first_run, uint32_t count, const tl_pso_opts *opts, uint64_t seed, uint32_t *out_pos, float *out_costs,
+                                 uint32_t *out_moves, uint32_t *best_index, tl_stats *stats);
+uint64_t tl_pso_draw(uint64_t seed, uint32_t run, uint64_t event, uint32_t slot);
+double tl_pso_weight(uint32_t epoch, uint32_t epochs);
+uint32_t tl_pso_keep(double x);
+int tl_particle_swarm_plan(uint32_t n, uint32_t n_nearest, uint32_t count, int cus, int lds_bytes, uint64_t workspace_bytes, uint32_t flags,
+                           uint32_t *particles, int *threads, uint32_t *per_launch);
+int tl_pso_selftest_swap_sequence(tl_ctx *ctx, const uint32_t *from, const uint32_t *to, uint32_t n, uint32_t count, uint32_t *out_pairs,
+                                  uint32_t *out_len);
+
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts
  * first..first+count as above; seed ignored otherwise).  d_out_pos: count x n u32, d_out_cost: count f32,

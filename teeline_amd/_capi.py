@@ -65,6 +65,8 @@ SYMBOLS = [
     "tl_genetic_algorithm_plan", "tl_ga_draw", "tl_ga_selftest_crossover",
     "tl_ant_colony", "tl_ant_colony_trace", "tl_ant_colony_trace_run", "tl_ant_colony_population", "tl_ant_colony_max_n", "tl_ant_colony_plan",
     "tl_aco_draw", "tl_aco_pow", "tl_aco_selftest_select",
+    "tl_particle_swarm", "tl_particle_swarm_trace", "tl_particle_swarm_population", "tl_particle_swarm_max_n", "tl_particle_swarm_plan",
+    "tl_pso_draw", "tl_pso_weight", "tl_pso_keep", "tl_pso_selftest_swap_sequence",
 ]
 
 
@@ -84,6 +86,11 @@ class TlLkOpts(C.Structure):
 class TlSaOpts(C.Structure):
     """tl_sa_opts: SAOptions (src/tsp/mod.rs:689-706)"""
     _fields_ = [("epochs", C.c_uint32), ("cooling_rate", C.c_float), ("min_temperature", C.c_float), ("max_temperature", C.c_float)]
+
+
+class TlPsoOpts(C.Structure):
+    """tl_pso_opts: what particle_swarm reads of HeuristicOptions (src/tsp/mod.rs:596-611)"""
+    _fields_ = [("epochs", C.c_uint32), ("n_nearest", C.c_uint32)]
 
 
 # tl_lk_progress_fn: void (*)(void *user, const uint32_t *best_pos, uint32_t n, float best_dist)
@@ -216,5 +223,19 @@ def load():
     L.tl_aco_pow.restype = f32
     L.tl_ant_colony_plan.argtypes = [u32, u32, u32, i32, i32, u64, C.POINTER(u32), C.POINTER(i32), C.POINTER(u64)]
     L.tl_aco_selftest_select.argtypes = [vp, vp, vp, vp, u32, f32, f32, vp]
+    L.tl_particle_swarm_max_n.argtypes = [vp]
+    L.tl_particle_swarm_max_n.restype = u32
+    L.tl_particle_swarm.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlPsoOpts), u64, vp, f32p, C.POINTER(TlStats)]
+    L.tl_particle_swarm_trace.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlPsoOpts), u64, u32, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32), vp, u32, vp,
+                                          u32]
+    L.tl_particle_swarm_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, C.POINTER(TlPsoOpts), u64, vp, vp, vp, C.POINTER(u32), C.POINTER(TlStats)]
+    L.tl_pso_draw.argtypes = [u64, u32, u64, u32]
+    L.tl_pso_draw.restype = u64
+    L.tl_pso_weight.argtypes = [u32, u32]
+    L.tl_pso_weight.restype = C.c_double
+    L.tl_pso_keep.argtypes = [C.c_double]
+    L.tl_pso_keep.restype = u32
+    L.tl_particle_swarm_plan.argtypes = [u32, u32, u32, i32, i32, u64, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
+    L.tl_pso_selftest_swap_sequence.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     _lib = L
     return L

@@ -424,6 +424,42 @@ hipError_t launch_aco_update(const AcoArgs &A, uint32_t runs, int lds_budget, hi
 hipError_t launch_aco_selftest_select(const float *weights, const float *eta, const uint32_t *visited, uint32_t n, float r1, float r2, uint32_t *out,
                                       hipStream_t s);
 
+// particle_swarm.hip — the particle swarm solver, the run (swarm) a grid dimension, two launches per epoch
+struct PsoArgs {
+    const float2 *xy;       // n cities, city order (coordinate form)
+    const float *dm_full;   // the matrix expanded to row-major n x n, or nullptr
+    const uint32_t *init;   // the initial tour(s) of particle 0, or nullptr (a shuffle)
+    uint32_t init_stride;   // 0: one tour for every run, n: one per run
+    uint16_t *pos[2];       // [runs][particles][n] the positions before and after the epoch's moves (pos[src], pos[src ^ 1])
+    uint16_t *pbest;        // [runs][particles][n]
+    uint16_t *gbest;        // [runs][n]
+    uint32_t *vel[2];       // [runs][particles][vmax] the velocities, a swap (i, j) as i | j << 16
+    uint32_t *vlen[2];      // [runs][particles] their lengths
+    float *cost;            // [runs][particles] tour_length of the moved positions
+    float *pcost;           // [runs][particles] pbest_cost
+    uint32_t *state;        // [runs][8] gbest cost bits, gbest improvements
+    uint32_t *out_pos;      // [runs][n] gbest after the last epoch
+    float *out_cost;        // [runs] its cost
+    uint32_t *log;          // optional: [log_cap][4] epoch, particle, cost bits, route index: the start gbest, then every improvement of run 0
+    uint32_t *route_log;    // optional: [route_cap][n] their routes
+    uint32_t *epoch_log;    // optional: [epoch_cap][2 particles] every particle's cost bits, then every particle's velocity length, of run 0
+    uint64_t seed;
+    uint32_t log_cap, route_cap, epoch_cap;
+    uint32_t first_run;     // stream id of the launch's run 0
+    uint32_t n, particles, vmax;
+    uint32_t epoch, epochs;
+    uint32_t src;           // which of pos / vel / vlen holds the state before the epoch
+    uint32_t last;          // commit: no epoch follows — write the result
+};
+size_t particle_swarm_lds_bytes(uint32_t n);  // LDS of one workgroup (every kernel)
+uint32_t particle_swarm_max_n(int lds_budget);
+int particle_swarm_threads(uint32_t n);
+hipError_t launch_pso_init(const PsoArgs &A, uint32_t runs, hipStream_t s);    // start positions and costs, then the first minimum
+hipError_t launch_pso_move(const PsoArgs &A, uint32_t runs, hipStream_t s);    // every particle against the epoch-start gbest
+hipError_t launch_pso_commit(const PsoArgs &A, uint32_t runs, hipStream_t s);  // the particles in index order; after an improvement the later ones again
+hipError_t launch_pso_selftest_swap_sequence(const uint16_t *from, const uint16_t *to, uint32_t n, uint32_t count, uint32_t *out_pairs, uint32_t *out_len,
+                                             hipStream_t s);
+
 // lk.hip
 struct LkState {           // device-side state machine of the multi-CU LK variant
     uint32_t key;            // min pair index with a valid chain in the current scan (0xFFFFFFFF: none)

@@ -1155,8 +1155,69 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const AcoOptions 
 }
 }  // namespace ant_colony
 
+namespace particle_swarm {  // particle_swarm.rs:22-129
+// The algorithm is the reference's; its random draws and its rounding are this project's specification (include/teeline_gpu.h).
+// The particle count is max(opts.n_nearest, 30).  runs > 1: runs 0 .. runs-1 of the seed at once, the best one returned (lowest
+// cost, then lowest run).  With a progress callback the reference's messages — PathUpdate(start gbest), per epoch a PathUpdate per
+// gbest improvement in particle order and EpochUpdate(epoch), then Done (particle_swarm.rs:72-74,114-127) — are replayed from that
+// run's improvement log.
+inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
+                      uint64_t seed = 1, uint32_t runs = 1)
+{
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size();
+    const tl_pso_opts o{(uint32_t)opts.epochs, (uint32_t)std::min<size_t>(opts.n_nearest, 0xFFFFFFFFu)};
+    std::vector<uint32_t> init, out(n);
+    if (init_tour) init = problem.positions_of(*init_tour);
+    const uint32_t *ip = init_tour ? init.data() : nullptr;
+    float cost = 0.f;
+    tl_stats st{};
+    uint32_t run = 0;
+    if (runs > 1) {
+        std::vector<uint32_t> outs((size_t)runs * n);
+        std::vector<float> costs(runs);
+        ctx.check(tl_particle_swarm_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, runs, &o, seed, outs.data(), costs.data(),
+                                               nullptr, &run, &st));
+        std::copy(outs.begin() + (size_t)run * n, outs.begin() + (size_t)(run + 1) * n, out.begin());
+        cost = costs[run];
+        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
+    } else if (!(progress_tx && *progress_tx)) {
+        ctx.check(tl_particle_swarm(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, out.data(), &cost, &st));
+        return detail::finish(problem, out, cost, st, nullptr);
+    }
+    uint32_t rows = 0, cap = 64;
+    std::vector<uint32_t> log, routes;
+    for (;;) {  // the log holds every improvement: ask again with the count where 64 records were too few
+        log.assign((size_t)cap * 4, 0u);
+        routes.assign((size_t)cap * std::max(n, 1u), 0u);
+        ctx.check(tl_particle_swarm_trace(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, run, out.data(), &cost, &st, log.data(), cap, &rows,
+                                          routes.data(), cap, nullptr, 0u));
+        if (rows <= cap) break;
+        cap = rows;
+    }
+    std::vector<size_t> route(n);
+    const auto path_update = [&](uint32_t k) {
+        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[routes[(size_t)k * n + q]].id;
+        float d;
+        std::memcpy(&d, &log[(size_t)k * 4 + 2], 4);
+        (*progress_tx)(ProgressKind::PathUpdate, route, d);
+    };
+    if (rows > 0) {
+        path_update(0);
+        uint32_t k = 1;
+        for (uint32_t e = 0; e < o.epochs; ++e) {
+            for (; k < rows && log[(size_t)k * 4] == e; ++k) path_update(k);
+            (*progress_tx)(ProgressKind::EpochUpdate, std::vector<size_t>{e}, 0.0f);
+        }
+    }
+    Solution s = detail::finish(problem, out, cost, st, nullptr);
+    (*progress_tx)(ProgressKind::Done, s.route_, cost);
+    return s;
+}
+}  // namespace particle_swarm
+
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
-enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony };
+enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm };
 
 inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
 {
@@ -1176,10 +1237,11 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
     else if (s == "tabu_search") out = Solvers::TabuSearch;  // (the alias `tabu` stays refused, below, as `sa` does)
     else if (s == "genetic_algorithm") out = Solvers::GeneticAlgorithm;  // (the alias `ga` likewise)
     else if (s == "ant_colony") out = Solvers::AntColony;  // (the alias `aco` likewise)
+    else if (s == "particle_swarm") out = Solvers::ParticleSwarm;  // (the alias `pso` likewise)
     else {
         static const char *cpu_only[] = {"aco", "branch_bound",
                                          "cs", "cuckoo_search", "fpa", "flower_pollination", "fourier", "ga", "gsa",
-                                         "gravitational_search", "pso", "particle_swarm", "sa",
+                                         "gravitational_search", "pso", "sa",
                                          "som", "kohonen", "kohonen_som", "stochastic_hill", "tabu"};
         for (const char *c : cpu_only)
             if (s == c) {
@@ -1187,6 +1249,7 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
                 if (s == "tabu") why += "; the seeded tabu search of this build is `tabu_search`";
                 if (s == "ga") why += "; the seeded genetic algorithm of this build is `genetic_algorithm`";
                 if (s == "aco") why += "; the seeded ant colony of this build is `ant_colony`";
+                if (s == "pso") why += "; the seeded particle swarm of this build is `particle_swarm`";
                 return false;
             }
         why = "unknown solver";  // FromStr's Err (mod.rs:588)
@@ -1211,6 +1274,7 @@ inline const char *solver_name(Solvers s)
         case Solvers::TabuSearch: return "tabu_search";
         case Solvers::GeneticAlgorithm: return "genetic_algorithm";
         case Solvers::AntColony: return "ant_colony";
+        case Solvers::ParticleSwarm: return "particle_swarm";
         default: return "shuffle";
     }
 }
@@ -1227,6 +1291,7 @@ struct StageOptions {
     uint32_t ga_runs = 1;  // a genetic_algorithm stage breeds this many runs and keeps the best
     ant_colony::AcoOptions aco;
     uint32_t aco_runs = 1;  // an ant_colony stage runs this many colonies and keeps the best
+    uint32_t pso_runs = 1;  // a particle_swarm stage runs this many swarms and keeps the best
     uint64_t seed = 1;  // LK kicks, shuffle, SA, tabu and GA draws
     const ProgressFn *progress = nullptr;  // handed to every stage's solve() (the reference's CLI passes None; teeline-qt a sender)
 };
@@ -1292,6 +1357,7 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             case Solvers::TabuSearch: sol = tabu_search::solve(ctx, problem, o.heuristic, o.progress, init, o.seed, o.tabu_chains); break;
             case Solvers::GeneticAlgorithm: sol = genetic_algorithm::solve(ctx, problem, o.ga, o.progress, init, o.seed, o.ga_runs); break;
             case Solvers::AntColony: sol = ant_colony::solve(ctx, problem, o.aco, o.progress, init, o.seed, o.aco_runs); break;
+            case Solvers::ParticleSwarm: sol = particle_swarm::solve(ctx, problem, o.heuristic, o.progress, init, o.seed, o.pso_runs); break;
         }
         const auto t1 = std::chrono::steady_clock::now();
         const uint64_t ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();
