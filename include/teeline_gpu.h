@@ -793,6 +793,77 @@ int tl_particle_swarm_plan(uint32_t n, uint32_t n_nearest, uint32_t count, int c
 int tl_pso_selftest_swap_sequence(tl_ctx *ctx, const uint32_t *from, const uint32_t *to, uint32_t n, uint32_t count, uint32_t *out_pairs,
                                   uint32_t *out_len);
 
+/* ---- the cuckoo search solver (src/tsp/cuckoo_search.rs:26-136) ------------------------------- */
+/* The reference's cuckoo search with its quirks kept.  N = max(n_nearest, 25) nests, pa = clamp((f64) mutation_probability, 0.01,
+ * 0.99) (tl_cs_pa; the default 0.001 gives 0.01).  Nest 0 starts on init_pos if given, every other nest (and nest 0 without
+ * init_pos) on a Fisher-Yates shuffle of city order; costs are tour_length as everywhere here (closing edge first, sequential f32).
+ * best is a COPY of the FIRST minimum nest and from then on no nest's property.  Epoch e, the cuckoos IN INDEX ORDER c = 0 .. N - 1:
+ * k = clamp(ceil(|levy| (n 0.1)) as usize, 1, n / 2) (tl_cs_flight_length: NaN gives 1, +inf n / 2); k times i = range(0 .. n - 1),
+ * j = range(i + 1 .. n), reverse [i ..= j] — from nest c AS IT STANDS, so a cuckoo whose nest an earlier flight of the epoch has
+ * overwritten flies from the new tour; the target t = range(0 .. N) AFTER the flight (c = t is allowed); new_cost < costs[t]
+ * (strict) replaces nest t, and if also < best_cost, best.  Then the nests in index order: r < pa replaces the nest UNCONDITIONALLY
+ * by a fresh shuffle, with the same best rule.  The result is best and its cost; epochs = 0 returns the start best.
+ * THE DRAWS AND THE LEVY STEP ARE THIS PROJECT'S SPECIFICATION, NOT THE REFERENCE'S (tests/_cs_oracle.py
+ * is the statement; csrc/cs_spec.h and csrc/levy_spec.h the text).  The draws: tl_genetic_algorithm's stream, u(seed, run, event,
+ * slot) (tl_cs_draw = tl_ga_draw); cuckoo c and nest c of epoch e own the events B .. B + n, B = (e N + c)(n + 1): event B holds
+ * the Levy words on slots 0-3, v's four resample pairs on slots 4-11, the target on slot 12 (position(u, N)) and the abandonment
+ * trial on slot 13 ((u >> 11) 2^-53 < pa); event B + 1 + r, slots 0 / 1, reversal r: i = position(u, n - 1),
+ * j = i + 1 + position(u', n - 1 - i); event B + 1 + j, slot 2, step j = n - 1 .. 1 of the replacement's shuffle; start nest i owns
+ * the events 2^58 + i n + j, slot 26.  epochs N (n + 1) > 2^58: TL_ERR_UNSUPPORTED.  The Levy step (tl_levy_from_words: the 12
+ * words in, the signed step out, *resamples (optional) the further pairs v took) is Mantegna's (probability.rs:8-22) in f64 with a
+ * fixed sequence for log, cos(2 pi u) — an exact quadrant reduction — and the power, IEEE sqrt and /; v = 0 (u2 = 1/4 or 3/4) takes
+ * the next pair, at most four times, and is 1.0 after the last.
+ * On the device (csrc/cuckoo_search.hip) every flight of an epoch is built at once from the epoch-start nests — the k reversals as
+ * a gather, each output position followed back through them — and every replacement whose trial succeeds; a commit launch walks
+ * the cuckoos in order, flies a cuckoo again where its nest has been overwritten earlier in the epoch, and applies the abandonments.
+ * opts NULL: the defaults (10 000 epochs, n_nearest 3, mutation_probability 0.001).  n <= 1 with epochs >= 1: TL_ERR_REF_PANICS
+ * (clamp(1, n / 2) with min > max panics); with epochs = 0, n = 0: TL_OK, nothing written, cost 0; n = 1: the one city at cost 0.
+ * init_pos not a permutation, mutation_probability not finite or outside [0, 1] (CSOptions::validate): TL_ERR_BADARG.
+ * epochs = 2^32 - 1, more than 4096 nests, n > tl_cuckoo_search_max_n, a context whose flags hold a bit no flag has:
+ * TL_ERR_UNSUPPORTED, before anything of size n is read or allocated.  dm_packed as in tl_sim_anneal.
+ * tl_cuckoo_search runs run 0.  stats (optional): sweeps = epochs, candidates = flights (epochs x N), moves = best improvements;
+ * tl_cuckoo_search_population's stats are these summed over its runs.
+ * tl_cuckoo_search_trace: run `run` of the seed, the same result plus a log of 4 words per record: epoch, source, cost bits, the
+ * index of the record's route in route_log (0xFFFFFFFF beyond route_cap).  source is the cuckoo for a flight, N + the nest for an
+ * abandonment.  Record 0 is the start best (epoch 0xFFFFFFFF, the nest it was copied from); every best improvement follows in the
+ * order it happened.  *log_len counts the records there are; the log holds the first log_cap, route_log (optional, route_cap x n)
+ * the routes of the first route_cap.  epoch_log (optional, epoch_cap rows of 4 N words): for the first epoch_cap epochs every
+ * nest's cost bits as the epoch leaves them; every cuckoo's k; every cuckoo's target, bit 31 set when accepted, bit 30 when its
+ * source nest had been overwritten earlier in the epoch; every nest's abandoned flag.  A caller replays the reference's messages
+ * from the log: PathUpdate(record 0), per epoch a PathUpdate per record of that epoch and EpochUpdate(epoch), then Done.
+ * tl_cuckoo_search_population: as tl_particle_swarm_population.  Run c of any batch equals first_run = c, count = 1.
+ * Host-only queries: tl_cs_draw; tl_levy_from_words; tl_cs_flight_length (0 for n < 2); tl_cs_pa; tl_cuckoo_search_plan — the
+ * nests, the threads of a workgroup and the runs one launch sequence holds (outputs optional; all 0 where n is outside 2 .. the
+ * limit or N > 4096; a flag bit no flag has: TL_ERR_UNSUPPORTED; the entries plan with 8 GiB).  tl_cuckoo_search_max_n: the
+ * largest n (a workgroup keeps 10 n bytes in LDS).
+ * tl_cs_selftest_levy: the DEVICE's Levy step on `count` given tuples of 12 words: its bits, tl_cs_flight_length(|step|, n) and
+ * the resamples (n >= 2, 1 <= count <= 2^24, else TL_ERR_BADARG).  tl_cs_selftest_reversals: the DEVICE's gather on `count` given
+ * rows of n elements (each <= 65535) and lists of lens[c] <= kcap <= n / 2 pairs (i, j), 0 <= i < j < n (pairs: count x kcap x 2):
+ * out (count x n) is each row after its reversals in order. */
+typedef struct tl_cs_opts { /* CSOptions, src/tsp/mod.rs:913-925: what cuckoo_search reads of it */
+    uint32_t epochs;
+    uint32_t n_nearest; /* N = max(n_nearest, 25) */
+    float mutation_probability;
+} tl_cs_opts;
+uint32_t tl_cuckoo_search_max_n(const tl_ctx *ctx);
+int tl_cuckoo_search(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_cs_opts *opts, uint64_t seed,
+                     uint32_t *out_pos, float *out_cost, tl_stats *stats);
+int tl_cuckoo_search_trace(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_cs_opts *opts,
+                           uint64_t seed, uint32_t run, uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *log, uint32_t log_cap,
+                           uint32_t *log_len, uint32_t *route_log, uint32_t route_cap, uint32_t *epoch_log, uint32_t epoch_cap);
+int tl_cuckoo_search_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
+                                uint32_t first_run, uint32_t count, const tl_cs_opts *opts, uint64_t seed, uint32_t *out_pos, float *out_costs,
+                                uint32_t *out_moves, uint32_t *best_index, tl_stats *stats);
+uint64_t tl_cs_draw(uint64_t seed, uint32_t run, uint64_t event, uint32_t slot);
+double tl_levy_from_words(const uint64_t *words, uint32_t *resamples);
+uint32_t tl_cs_flight_length(double levy, uint32_t n);
+double tl_cs_pa(float mutation_probability);
+int tl_cuckoo_search_plan(uint32_t n, uint32_t n_nearest, uint32_t count, int cus, int lds_bytes, uint64_t workspace_bytes, uint32_t flags,
+                          uint32_t *nests, int *threads, uint32_t *per_launch);
+int tl_cs_selftest_levy(tl_ctx *ctx, const uint64_t *words, uint32_t count, uint32_t n, uint64_t *out_bits, uint32_t *out_k, uint32_t *out_resamples);
+int tl_cs_selftest_reversals(tl_ctx *ctx, const uint32_t *tours, const uint32_t *pairs, const uint32_t *lens, uint32_t n, uint32_t kcap, uint32_t count,
+                             uint32_t *out);
+
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts
  * first..first+count as above; seed ignored otherwise).  d_out_pos: count x n u32, d_out_cost: count f32,

@@ -67,6 +67,8 @@ SYMBOLS = [
     "tl_aco_draw", "tl_aco_pow", "tl_aco_selftest_select",
     "tl_particle_swarm", "tl_particle_swarm_trace", "tl_particle_swarm_population", "tl_particle_swarm_max_n", "tl_particle_swarm_plan",
     "tl_pso_draw", "tl_pso_weight", "tl_pso_keep", "tl_pso_selftest_swap_sequence",
+    "tl_cuckoo_search", "tl_cuckoo_search_trace", "tl_cuckoo_search_population", "tl_cuckoo_search_max_n", "tl_cuckoo_search_plan",
+    "tl_cs_draw", "tl_levy_from_words", "tl_cs_flight_length", "tl_cs_pa", "tl_cs_selftest_levy", "tl_cs_selftest_reversals",
 ]
 
 
@@ -91,6 +93,11 @@ class TlSaOpts(C.Structure):
 class TlPsoOpts(C.Structure):
     """tl_pso_opts: what particle_swarm reads of HeuristicOptions (src/tsp/mod.rs:596-611)"""
     _fields_ = [("epochs", C.c_uint32), ("n_nearest", C.c_uint32)]
+
+
+class TlCsOpts(C.Structure):
+    """tl_cs_opts: what cuckoo_search reads of CSOptions (src/tsp/mod.rs:913-925)"""
+    _fields_ = [("epochs", C.c_uint32), ("n_nearest", C.c_uint32), ("mutation_probability", C.c_float)]
 
 
 # tl_lk_progress_fn: void (*)(void *user, const uint32_t *best_pos, uint32_t n, float best_dist)
@@ -237,5 +244,22 @@ def load():
     L.tl_pso_keep.restype = u32
     L.tl_particle_swarm_plan.argtypes = [u32, u32, u32, i32, i32, u64, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
     L.tl_pso_selftest_swap_sequence.argtypes = [vp, vp, vp, u32, u32, vp, vp]
+    L.tl_cuckoo_search_max_n.argtypes = [vp]
+    L.tl_cuckoo_search_max_n.restype = u32
+    L.tl_cuckoo_search.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlCsOpts), u64, vp, f32p, C.POINTER(TlStats)]
+    L.tl_cuckoo_search_trace.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlCsOpts), u64, u32, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32), vp, u32, vp,
+                                         u32]
+    L.tl_cuckoo_search_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, C.POINTER(TlCsOpts), u64, vp, vp, vp, C.POINTER(u32), C.POINTER(TlStats)]
+    L.tl_cs_draw.argtypes = [u64, u32, u64, u32]
+    L.tl_cs_draw.restype = u64
+    L.tl_levy_from_words.argtypes = [vp, C.POINTER(u32)]
+    L.tl_levy_from_words.restype = C.c_double
+    L.tl_cs_flight_length.argtypes = [C.c_double, u32]
+    L.tl_cs_flight_length.restype = u32
+    L.tl_cs_pa.argtypes = [f32]
+    L.tl_cs_pa.restype = C.c_double
+    L.tl_cuckoo_search_plan.argtypes = [u32, u32, u32, i32, i32, u64, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
+    L.tl_cs_selftest_levy.argtypes = [vp, vp, u32, u32, vp, vp, vp]
+    L.tl_cs_selftest_reversals.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp]
     _lib = L
     return L

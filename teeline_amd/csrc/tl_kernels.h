@@ -460,6 +460,44 @@ hipError_t launch_pso_commit(const PsoArgs &A, uint32_t runs, hipStream_t s);  /
 hipError_t launch_pso_selftest_swap_sequence(const uint16_t *from, const uint16_t *to, uint32_t n, uint32_t count, uint32_t *out_pairs, uint32_t *out_len,
                                              hipStream_t s);
 
+// cuckoo_search.hip — the cuckoo search solver, the run a grid dimension, two launches per epoch
+struct CsArgs {
+    const float2 *xy;       // n cities, city order (coordinate form)
+    const float *dm_full;   // the matrix expanded to row-major n x n, or nullptr
+    const uint32_t *init;   // the initial tour(s) of nest 0, or nullptr (a shuffle)
+    uint32_t init_stride;   // 0: one tour for every run, n: one per run
+    uint16_t *nest;         // [runs][nests][n]
+    uint16_t *fly;          // [runs][nests][n] cuckoo c's flight, staged
+    uint16_t *repl;         // [runs][nests][n] nest c's replacement, staged where its abandonment trial succeeds
+    uint16_t *best;         // [runs][n]
+    float *cost;            // [runs][nests] the nests' costs
+    float *fcost;           // [runs][nests] the staged flights' costs
+    float *rcost;           // [runs][nests] the staged replacements' costs
+    uint32_t *fk;           // [runs][nests] the flights' lengths k
+    uint32_t *state;        // [runs][8] best cost bits, best improvements
+    uint32_t *out_pos;      // [runs][n] best after the last epoch
+    float *out_cost;        // [runs] its cost
+    uint32_t *log;          // optional: [log_cap][4] epoch, source, cost bits, route index: the start best, then every improvement of run 0
+    uint32_t *route_log;    // optional: [route_cap][n] their routes
+    uint32_t *epoch_log;    // optional: [epoch_cap][4 nests] of run 0: nest cost bits | k | target (bit 31 accepted, bit 30 flown again) | abandoned
+    uint64_t seed;
+    double pa;
+    uint32_t log_cap, route_cap, epoch_cap;
+    uint32_t first_run;     // stream id of the launch's run 0
+    uint32_t n, nests;
+    uint32_t epoch;
+    uint32_t last;          // commit: no epoch follows — write the result
+};
+size_t cuckoo_search_lds_bytes(uint32_t n);  // LDS of one workgroup (every kernel)
+uint32_t cuckoo_search_max_n(int lds_budget);
+int cuckoo_search_threads(uint32_t n);
+hipError_t launch_cs_init(const CsArgs &A, uint32_t runs, hipStream_t s);    // start nests and costs, then the first minimum
+hipError_t launch_cs_fly(const CsArgs &A, uint32_t runs, hipStream_t s);     // every flight from the epoch-start nests, every replacement
+hipError_t launch_cs_commit(const CsArgs &A, uint32_t runs, hipStream_t s);  // the cuckoos in order (a flight from an overwritten nest again), then the abandonments
+hipError_t launch_cs_selftest_levy(const uint64_t *words, uint32_t count, uint32_t n, uint64_t *out_bits, uint32_t *out_k, uint32_t *out_resamples, hipStream_t s);
+hipError_t launch_cs_selftest_reversals(const uint16_t *tours, const uint32_t *pairs, const uint32_t *lens, uint32_t n, uint32_t kcap, uint32_t count,
+                                        uint16_t *out, hipStream_t s);
+
 // lk.hip
 struct LkState {           // device-side state machine of the multi-CU LK variant
     uint32_t key;            // min pair index with a valid chain in the current scan (0xFFFFFFFF: none)
