@@ -864,6 +864,78 @@ int tl_cs_selftest_levy(tl_ctx *ctx, const uint64_t *words, uint32_t count, uint
 int tl_cs_selftest_reversals(tl_ctx *ctx, const uint32_t *tours, const uint32_t *pairs, const uint32_t *lens, uint32_t n, uint32_t kcap, uint32_t count,
                              uint32_t *out);
 
+/* ---- the flower pollination solver (src/tsp/flower_pollination.rs:53-151) --------------------- */
+/* The reference's flower pollination with its quirks kept.  N = max(n_nearest, 25) flowers; switch_prob = 0.8 if
+ * mutation_probability < 0.01 (compared in f32: the default 0.001 gives 0.8), else (f64) mutation_probability (tl_fpa_switch_prob).
+ * Flower 0 starts on init_pos if given, every other flower (and flower 0 without init_pos) on a Fisher-Yates shuffle of city order;
+ * costs are tour_length as everywhere here (closing edge first, sequential f32).  gbest is a COPY of the FIRST minimum flower.
+ * Epoch e, the flowers IN INDEX ORDER i = 0 .. N - 1: u < switch_prob is a GLOBAL pollination — seq = swap_sequence(flower i, gbest);
+ * empty: the flower comes back unchanged and nothing further is drawn; else the first clamp(ceil(|levy| len 0.5) as usize, 1, len)
+ * swaps of it (tl_fpa_global_swaps: the product left to right, NaN gives 1, +inf len) are applied to flower i.  Otherwise a LOCAL
+ * one: j among the flowers other than i, k among those other than i and j, seq = swap_sequence(flower j, flower k) from the
+ * flowers AS THEY STAND; empty: unchanged; else its first clamp(ceil(epsilon len) as usize, 1, len) swaps (tl_fpa_local_swaps) are
+ * applied to FLOWER i.  new_cost < costs[i] (strict: an unchanged flower is never accepted) replaces flower i, and if also
+ * < gbest_cost, gbest AT ONCE — the next flower of the same epoch sees it.  The result is gbest and its cost; epochs = 0 returns
+ * the start gbest.
+ * THE DRAWS ARE THIS PROJECT'S SPECIFICATION, NOT THE REFERENCE'S (tests/_fpa_oracle.py is the statement;
+ * csrc/fpa_spec.h the text; the Levy step is tl_levy_from_words, unchanged).  tl_genetic_algorithm's stream, u(seed, run, event,
+ * slot) (tl_fpa_draw = tl_ga_draw); flower i of epoch e owns the event e N + i: slot 0 the switch trial ((u >> 11) 2^-53 <
+ * switch_prob), slots 1-12 the Levy words, slot 13 j = position(u, N - 1) stepped over i, slot 14 k = position(u, N - 2) stepped
+ * over i and j in ascending order (tl_fpa_partners: the reference's rejection loop has the same distribution), slot 15 epsilon;
+ * start flower i owns the events 2^58 + i n + j, slot 26, as the swarm's and the nests' do.  A draw the reference would not have
+ * made is not read.
+ * On the device (csrc/flower_pollination.hip) every move of an epoch is built at once against the epoch-start state; a commit
+ * launch walks the flowers in order and builds a flower again where its staged move read something that has since changed (a
+ * global move after gbest changed; a local move whose j or k was accepted earlier in the epoch).
+ * opts NULL: the defaults (10 000 epochs, n_nearest 3, mutation_probability 0.001: FPAOptions::default).  n = 0 and n = 1: the
+ * reference does not panic (every sequence is empty, nothing is accepted) — TL_OK, the empty route or the one city at cost 0.
+ * init_pos not a permutation, mutation_probability not finite or outside [0, 1] (FPAOptions::validate): TL_ERR_BADARG.
+ * What validate lets through and the port cannot run — epochs = 2^32 - 1, more than 4096 flowers, n > tl_flower_pollination_max_n —
+ * and a context whose flags hold a bit no flag has: TL_ERR_UNSUPPORTED, before anything of size n is read or allocated.
+ * dm_packed as in tl_sim_anneal.
+ * tl_flower_pollination runs run 0.  stats (optional): sweeps = epochs, candidates = moves built (epochs x N), moves = gbest
+ * improvements; tl_flower_pollination_population's stats are these summed over its runs.
+ * tl_flower_pollination_trace: run `run` of the seed, the same result plus a log of 4 words per record: epoch, flower, cost bits,
+ * the index of the record's route in route_log (0xFFFFFFFF beyond route_cap).  Record 0 is the start gbest (epoch 0xFFFFFFFF, the
+ * flower it was copied from); every gbest improvement follows in the order it happened.  *log_len counts the records there are;
+ * the log holds the first log_cap, route_log (optional, route_cap x n) the routes of the first route_cap.  epoch_log (optional,
+ * epoch_cap rows of 4 N words): for the first epoch_cap epochs every flower's cost bits as the epoch leaves them; every flower's
+ * move — bit 31 set: global, else j | k << 12; every move's sequence length | prefix length << 16 (0 for an empty sequence); bit 0
+ * accepted, bit 1 built again by the commit.  A caller replays the reference's messages from the log: PathUpdate(record 0), per
+ * epoch a PathUpdate per record of that epoch and EpochUpdate(epoch), then Done.
+ * tl_flower_pollination_population: as tl_particle_swarm_population.  Run c of any batch equals first_run = c, count = 1.
+ * Host-only queries: tl_fpa_draw; tl_fpa_switch_prob; tl_fpa_global_swaps and tl_fpa_local_swaps (0 for len = 0); tl_fpa_partners
+ * (3 <= flowers <= 4096, i < flowers, else TL_ERR_BADARG); tl_flower_pollination_plan — the flowers, the threads of a workgroup
+ * and the runs one launch sequence holds (outputs optional; all 0 where n is outside 2 .. the limit or N > 4096; a flag bit no
+ * flag has: TL_ERR_UNSUPPORTED; the entries plan with 8 GiB, at most 65 535 runs a sequence).  tl_flower_pollination_max_n: the
+ * largest n (a workgroup keeps 10 n bytes in LDS).
+ * tl_fpa_selftest_pollinate: the DEVICE's move on `count` given tuples of three permutations of 0 .. n - 1 (count x n each) and a
+ * prefix length: out_len[c] is the length of swap_sequence(source, target), out (count x n) flower c after the first
+ * min(prefix[c], out_len[c]) swaps of it (1 <= n <= the limit, 1 <= count <= 65535, else TL_ERR_BADARG). */
+typedef struct tl_fpa_opts { /* FPAOptions, src/tsp/mod.rs:998-1010: what flower_pollination reads of it */
+    uint32_t epochs;
+    uint32_t n_nearest; /* N = max(n_nearest, 25) */
+    float mutation_probability;
+} tl_fpa_opts;
+uint32_t tl_flower_pollination_max_n(const tl_ctx *ctx);
+int tl_flower_pollination(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_fpa_opts *opts, uint64_t seed,
+                          uint32_t *out_pos, float *out_cost, tl_stats *stats);
+int tl_flower_pollination_trace(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_fpa_opts *opts,
+                                uint64_t seed, uint32_t run, uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *log, uint32_t log_cap,
+                                uint32_t *log_len, uint32_t *route_log, uint32_t route_cap, uint32_t *epoch_log, uint32_t epoch_cap);
+int tl_flower_pollination_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
+                                     uint32_t first_run, uint32_t count, const tl_fpa_opts *opts, uint64_t seed, uint32_t *out_pos, float *out_costs,
+                                     uint32_t *out_moves, uint32_t *best_index, tl_stats *stats);
+uint64_t tl_fpa_draw(uint64_t seed, uint32_t run, uint64_t event, uint32_t slot);
+double tl_fpa_switch_prob(float mutation_probability);
+uint32_t tl_fpa_global_swaps(double levy, uint32_t len);
+uint32_t tl_fpa_local_swaps(double epsilon, uint32_t len);
+int tl_fpa_partners(uint64_t seed, uint32_t run, uint32_t epoch, uint32_t i, uint32_t flowers, uint32_t *j, uint32_t *k);
+int tl_flower_pollination_plan(uint32_t n, uint32_t n_nearest, uint32_t count, int cus, int lds_bytes, uint64_t workspace_bytes, uint32_t flags,
+                               uint32_t *flowers, int *threads, uint32_t *per_launch);
+int tl_fpa_selftest_pollinate(tl_ctx *ctx, const uint32_t *flower, const uint32_t *source, const uint32_t *target, const uint32_t *prefix, uint32_t n,
+                              uint32_t count, uint32_t *out, uint32_t *out_len);
+
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts
  * first..first+count as above; seed ignored otherwise).  d_out_pos: count x n u32, d_out_cost: count f32,

@@ -69,6 +69,8 @@ SYMBOLS = [
     "tl_pso_draw", "tl_pso_weight", "tl_pso_keep", "tl_pso_selftest_swap_sequence",
     "tl_cuckoo_search", "tl_cuckoo_search_trace", "tl_cuckoo_search_population", "tl_cuckoo_search_max_n", "tl_cuckoo_search_plan",
     "tl_cs_draw", "tl_levy_from_words", "tl_cs_flight_length", "tl_cs_pa", "tl_cs_selftest_levy", "tl_cs_selftest_reversals",
+    "tl_flower_pollination", "tl_flower_pollination_trace", "tl_flower_pollination_population", "tl_flower_pollination_max_n", "tl_flower_pollination_plan",
+    "tl_fpa_draw", "tl_fpa_switch_prob", "tl_fpa_global_swaps", "tl_fpa_local_swaps", "tl_fpa_partners", "tl_fpa_selftest_pollinate",
 ]
 
 
@@ -97,6 +99,11 @@ class TlPsoOpts(C.Structure):
 
 class TlCsOpts(C.Structure):
     """tl_cs_opts: what cuckoo_search reads of CSOptions (src/tsp/mod.rs:913-925)"""
+    _fields_ = [("epochs", C.c_uint32), ("n_nearest", C.c_uint32), ("mutation_probability", C.c_float)]
+
+
+class TlFpaOpts(C.Structure):
+    """tl_fpa_opts: what flower_pollination reads of FPAOptions (src/tsp/mod.rs:998-1010)"""
     _fields_ = [("epochs", C.c_uint32), ("n_nearest", C.c_uint32), ("mutation_probability", C.c_float)]
 
 
@@ -261,5 +268,22 @@ def load():
     L.tl_cuckoo_search_plan.argtypes = [u32, u32, u32, i32, i32, u64, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
     L.tl_cs_selftest_levy.argtypes = [vp, vp, u32, u32, vp, vp, vp]
     L.tl_cs_selftest_reversals.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp]
+    L.tl_flower_pollination_max_n.argtypes = [vp]
+    L.tl_flower_pollination_max_n.restype = u32
+    L.tl_flower_pollination.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlFpaOpts), u64, vp, f32p, C.POINTER(TlStats)]
+    L.tl_flower_pollination_trace.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlFpaOpts), u64, u32, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32), vp, u32,
+                                              vp, u32]
+    L.tl_flower_pollination_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, C.POINTER(TlFpaOpts), u64, vp, vp, vp, C.POINTER(u32), C.POINTER(TlStats)]
+    L.tl_fpa_draw.argtypes = [u64, u32, u64, u32]
+    L.tl_fpa_draw.restype = u64
+    L.tl_fpa_switch_prob.argtypes = [f32]
+    L.tl_fpa_switch_prob.restype = C.c_double
+    L.tl_fpa_global_swaps.argtypes = [C.c_double, u32]
+    L.tl_fpa_global_swaps.restype = u32
+    L.tl_fpa_local_swaps.argtypes = [C.c_double, u32]
+    L.tl_fpa_local_swaps.restype = u32
+    L.tl_fpa_partners.argtypes = [u64, u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
+    L.tl_flower_pollination_plan.argtypes = [u32, u32, u32, i32, i32, u64, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
+    L.tl_fpa_selftest_pollinate.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, vp]
     _lib = L
     return L

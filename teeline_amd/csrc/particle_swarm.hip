@@ -24,6 +24,7 @@
 //   lengths afterwards) | nv[vmax] u32 | pos[n], inv[n], pi[n] u16  (14 n + 4 vmax bytes).
 #include "chain_tour.h"
 #include "pso_spec.h"
+#include "swap_seq.h"
 #include "tl_kernels.h"
 
 #pragma clang fp contract(off)
@@ -75,42 +76,6 @@ __device__ __forceinline__ float pso_sum_edges(const float *E, uint32_t n)
     return tot;
 }
 
-// swap_sequence(pos, target) (route.rs:118-134) by the whole workgroup, L.inv being the inverse of the position: the pairs go to
-// out[0 .. len) in ascending i, len (= n - cycles of pi) is returned to every lane.  Begins and ends behind a barrier.
-__device__ uint32_t pso_swap_sequence(const uint16_t *target, uint32_t n, const PsoLds &L, uint32_t *out)
-{
-    const uint32_t tid = threadIdx.x, nt = blockDim.x, lane = tid & 63u, wave = tid >> 6, nw = nt >> 6;
-    for (uint32_t k = tid; k < n; k += nt) L.pi[k] = L.inv[target[k]];
-    TL_SYNC();
-    uint32_t base = 0, par = 0;
-    for (uint32_t t0 = 0; t0 < n; t0 += nt) {
-        const uint32_t i = t0 + tid;
-        bool has = false;
-        uint32_t q = 0;
-        if (i < n) {
-            uint32_t p = L.pi[i];
-            for (uint32_t steps = 0; p < i && steps < n; ++steps) p = L.pi[p];  // (a permutation comes back to i within its cycle: the bound is never met)
-            has = p > i;
-            q = p;
-        }
-        const uint64_t b = __ballot(has), below = (1ull << lane) - 1ull;
-        uint32_t *ws = L.wsum + par * 16u;
-        if (lane == 0u) ws[wave] = (uint32_t)__popcll(b);
-        TL_SYNC();
-        uint32_t off = base, tot = 0;
-        for (uint32_t w = 0; w < nw; ++w) {
-            const uint32_t a = ws[w];
-            if (w < wave) off += a;
-            tot += a;
-        }
-        if (has) out[off + (uint32_t)__popcll(b & below)] = pso_swap(i, q);
-        base += tot;
-        par ^= 1u;
-    }
-    TL_SYNC();
-    return base;
-}
-
 // One particle step (particle_swarm.rs:82-105) by the whole workgroup: from pos / vel / vlen[src] of particle i, its pbest and the
 // run's gbest as they stand, to pos / vel / vlen[src ^ 1] and cost.  Ends behind a barrier.
 template <bool DM>
@@ -127,8 +92,8 @@ __device__ void pso_step(const PsoArgs &A, const PsoLds &L, const CityDist<DM> &
         L.inv[c] = (uint16_t)k;
     }
     TL_SYNC();
-    const uint32_t len_c = pso_swap_sequence(A.pbest + idx * n, n, L, L.la);
-    const uint32_t len_s = pso_swap_sequence(A.gbest + (size_t)run * n, n, L, L.lb);
+    const uint32_t len_c = swap_sequence_orbit(A.pbest + idx * n, n, L, L.la);
+    const uint32_t len_s = swap_sequence_orbit(A.gbest + (size_t)run * n, n, L, L.lb);
     const uint64_t ev = pso_step_event(A.epoch, P, i);
     const double r1 = pso_uniform(ga_draw_key(key, ev, kPsoSlotR1)), r2 = pso_uniform(ga_draw_key(key, ev, kPsoSlotR2));
     uint32_t ik = pso_inertia_keep(pso_weight(A.epoch, A.epochs), vl), ck = pso_pull_keep(r1, len_c), sk = pso_pull_keep(r2, len_s);
@@ -326,7 +291,7 @@ __global__ __launch_bounds__(256) void k_pso_selftest_swap_sequence(const uint16
     const uint16_t *f = from + (size_t)blockIdx.x * n, *t = to + (size_t)blockIdx.x * n;
     for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) L.inv[f[k]] = (uint16_t)k;
     TL_SYNC();
-    const uint32_t len = pso_swap_sequence(t, n, L, L.la);
+    const uint32_t len = swap_sequence_orbit(t, n, L, L.la);
     for (uint32_t k = threadIdx.x; k < len; k += blockDim.x) out_pairs[(size_t)blockIdx.x * n + k] = L.la[k];
     if (threadIdx.x == 0) out_len[blockIdx.x] = len;
 }

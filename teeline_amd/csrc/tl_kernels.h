@@ -498,6 +498,41 @@ hipError_t launch_cs_selftest_levy(const uint64_t *words, uint32_t count, uint32
 hipError_t launch_cs_selftest_reversals(const uint16_t *tours, const uint32_t *pairs, const uint32_t *lens, uint32_t n, uint32_t kcap, uint32_t count,
                                         uint16_t *out, hipStream_t s);
 
+// flower_pollination.hip — the flower pollination solver, the run a grid dimension, two launches per epoch
+struct FpaArgs {
+    const float2 *xy;       // n cities, city order (coordinate form)
+    const float *dm_full;   // the matrix expanded to row-major n x n, or nullptr
+    const uint32_t *init;   // the initial tour(s) of flower 0, or nullptr (a shuffle)
+    uint32_t init_stride;   // 0: one tour for every run, n: one per run
+    uint16_t *flower;       // [runs][flowers][n]
+    uint16_t *stage;        // [runs][flowers][n] flower i's move, staged
+    uint16_t *gbest;        // [runs][n]
+    float *cost;            // [runs][flowers] the flowers' costs
+    float *scost;           // [runs][flowers] the staged moves' costs
+    uint32_t *slen;         // [runs][flowers] the staged moves' sequence length | prefix length << 16
+    uint32_t *state;        // [runs][8] gbest cost bits, gbest improvements
+    uint32_t *out_pos;      // [runs][n] gbest after the last epoch
+    float *out_cost;        // [runs] its cost
+    uint32_t *log;          // optional: [log_cap][4] epoch, flower, cost bits, route index: the start gbest, then every improvement of run 0
+    uint32_t *route_log;    // optional: [route_cap][n] their routes
+    uint32_t *epoch_log;    // optional: [epoch_cap][4 flowers] of run 0: cost bits | kind, j, k | lengths | accepted, built again
+    uint64_t seed;
+    double switch_prob;
+    uint32_t log_cap, route_cap, epoch_cap;
+    uint32_t first_run;     // stream id of the launch's run 0
+    uint32_t n, flowers;
+    uint32_t epoch;
+    uint32_t last;          // commit: no epoch follows — write the result
+};
+size_t flower_pollination_lds_bytes(uint32_t n);  // LDS of one workgroup (every kernel)
+uint32_t flower_pollination_max_n(int lds_budget);
+int flower_pollination_threads(uint32_t n);
+hipError_t launch_fpa_init(const FpaArgs &A, uint32_t runs, hipStream_t s);    // start flowers and costs, then the first minimum
+hipError_t launch_fpa_move(const FpaArgs &A, uint32_t runs, hipStream_t s);    // every flower's move against the epoch-start state
+hipError_t launch_fpa_commit(const FpaArgs &A, uint32_t runs, hipStream_t s);  // the flowers in order (a move whose inputs have changed is built again)
+hipError_t launch_fpa_selftest_pollinate(const uint16_t *flower, const uint16_t *source, const uint16_t *target, const uint32_t *prefix, uint32_t n, uint32_t count,
+                                         uint16_t *out, uint32_t *out_len, hipStream_t s);
+
 // lk.hip
 struct LkState {           // device-side state machine of the multi-CU LK variant
     uint32_t key;            // min pair index with a valid chain in the current scan (0xFFFFFFFF: none)

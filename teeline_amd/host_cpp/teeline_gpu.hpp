@@ -1287,8 +1287,79 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const CSOptions &
 }
 }  // namespace cuckoo_search
 
+namespace flower_pollination {  // flower_pollination.rs:53-151
+// The algorithm is the reference's; its random draws and its Levy step are this project's specification (include/teeline_gpu.h).
+// The flower count is max(opts.heuristic.n_nearest, 25).  runs > 1: runs 0 .. runs-1 of the seed at once, the best one returned
+// (lowest cost, then lowest run).  With a progress callback the reference's messages — PathUpdate(start gbest), per epoch a
+// PathUpdate per gbest improvement in the order they happen and EpochUpdate(epoch), then Done (flower_pollination.rs:113-115,133-136,142-149)
+// — are replayed from that run's improvement log.
+struct FPAOptions {  // mod.rs:998-1026
+    HeuristicOptions heuristic;
+    float mutation_probability = 0.001f;
+    std::string validate() const
+    {
+        if (!std::isfinite(mutation_probability) || mutation_probability < 0.0f || mutation_probability > 1.0f)
+            return "mutation_probability must be in [0, 1] (got " + std::to_string(mutation_probability) + ")";
+        return "";
+    }
+};
+inline Solution solve(Context &ctx, const TspProblem &problem, const FPAOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
+                      uint64_t seed = 1, uint32_t runs = 1)
+{
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size();
+    const tl_fpa_opts o{(uint32_t)opts.heuristic.epochs, (uint32_t)std::min<size_t>(opts.heuristic.n_nearest, 0xFFFFFFFFu), opts.mutation_probability};
+    std::vector<uint32_t> init, out(n);
+    if (init_tour) init = problem.positions_of(*init_tour);
+    const uint32_t *ip = init_tour ? init.data() : nullptr;
+    float cost = 0.f;
+    tl_stats st{};
+    uint32_t run = 0;
+    if (runs > 1) {
+        std::vector<uint32_t> outs((size_t)runs * n);
+        std::vector<float> costs(runs);
+        ctx.check(tl_flower_pollination_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, runs, &o, seed, outs.data(), costs.data(),
+                                               nullptr, &run, &st));
+        std::copy(outs.begin() + (size_t)run * n, outs.begin() + (size_t)(run + 1) * n, out.begin());
+        cost = costs[run];
+        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
+    } else if (!(progress_tx && *progress_tx)) {
+        ctx.check(tl_flower_pollination(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, out.data(), &cost, &st));
+        return detail::finish(problem, out, cost, st, nullptr);
+    }
+    uint32_t rows = 0, cap = 64;
+    std::vector<uint32_t> log, routes;
+    for (;;) {  // the log holds every improvement: ask again with the count where 64 records were too few
+        log.assign((size_t)cap * 4, 0u);
+        routes.assign((size_t)cap * std::max(n, 1u), 0u);
+        ctx.check(tl_flower_pollination_trace(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, run, out.data(), &cost, &st, log.data(), cap, &rows,
+                                          routes.data(), cap, nullptr, 0u));
+        if (rows <= cap) break;
+        cap = rows;
+    }
+    std::vector<size_t> route(n);
+    const auto path_update = [&](uint32_t k) {
+        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[routes[(size_t)k * n + q]].id;
+        float d;
+        std::memcpy(&d, &log[(size_t)k * 4 + 2], 4);
+        (*progress_tx)(ProgressKind::PathUpdate, route, d);
+    };
+    if (rows > 0) {
+        path_update(0);
+        uint32_t k = 1;
+        for (uint32_t e = 0; e < o.epochs; ++e) {
+            for (; k < rows && log[(size_t)k * 4] == e; ++k) path_update(k);
+            (*progress_tx)(ProgressKind::EpochUpdate, std::vector<size_t>{e}, 0.0f);
+        }
+    }
+    Solution s = detail::finish(problem, out, cost, st, nullptr);
+    (*progress_tx)(ProgressKind::Done, s.route_, cost);
+    return s;
+}
+}  // namespace flower_pollination
+
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
-enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch };
+enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch, FlowerPollination };
 
 inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
 {
@@ -1310,9 +1381,10 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
     else if (s == "ant_colony") out = Solvers::AntColony;  // (the alias `aco` likewise)
     else if (s == "particle_swarm") out = Solvers::ParticleSwarm;  // (the alias `pso` likewise)
     else if (s == "cuckoo_search") out = Solvers::CuckooSearch;  // (the alias `cs` likewise)
+    else if (s == "flower_pollination") out = Solvers::FlowerPollination;  // (the alias `fpa` likewise)
     else {
         static const char *cpu_only[] = {"aco", "branch_bound",
-                                         "cs", "fpa", "flower_pollination", "fourier", "ga", "gsa",
+                                         "cs", "fpa", "fourier", "ga", "gsa",
                                          "gravitational_search", "pso", "sa",
                                          "som", "kohonen", "kohonen_som", "stochastic_hill", "tabu"};
         for (const char *c : cpu_only)
@@ -1323,6 +1395,7 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
                 if (s == "aco") why += "; the seeded ant colony of this build is `ant_colony`";
                 if (s == "pso") why += "; the seeded particle swarm of this build is `particle_swarm`";
                 if (s == "cs") why += "; the seeded cuckoo search of this build is `cuckoo_search`";
+                if (s == "fpa") why += "; the seeded flower pollination of this build is `flower_pollination`";
                 return false;
             }
         why = "unknown solver";  // FromStr's Err (mod.rs:588)
@@ -1349,6 +1422,7 @@ inline const char *solver_name(Solvers s)
         case Solvers::AntColony: return "ant_colony";
         case Solvers::ParticleSwarm: return "particle_swarm";
         case Solvers::CuckooSearch: return "cuckoo_search";
+        case Solvers::FlowerPollination: return "flower_pollination";
         default: return "shuffle";
     }
 }
@@ -1368,6 +1442,8 @@ struct StageOptions {
     uint32_t pso_runs = 1;  // a particle_swarm stage runs this many swarms and keeps the best
     float cs_mutation_probability = 0.001f;  // CSOptions::mutation_probability (mod.rs:922)
     uint32_t cs_runs = 1;  // a cuckoo_search stage runs this many runs and keeps the best
+    float fpa_mutation_probability = 0.001f;  // FPAOptions::mutation_probability (mod.rs:1007)
+    uint32_t fpa_runs = 1;  // a flower_pollination stage runs this many runs and keeps the best
     uint64_t seed = 1;  // LK kicks, shuffle, SA, tabu and GA draws
     const ProgressFn *progress = nullptr;  // handed to every stage's solve() (the reference's CLI passes None; teeline-qt a sender)
 };
@@ -1435,6 +1511,7 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             case Solvers::AntColony: sol = ant_colony::solve(ctx, problem, o.aco, o.progress, init, o.seed, o.aco_runs); break;
             case Solvers::ParticleSwarm: sol = particle_swarm::solve(ctx, problem, o.heuristic, o.progress, init, o.seed, o.pso_runs); break;
             case Solvers::CuckooSearch: sol = cuckoo_search::solve(ctx, problem, cuckoo_search::CSOptions{o.heuristic, o.cs_mutation_probability}, o.progress, init, o.seed, o.cs_runs); break;
+            case Solvers::FlowerPollination: sol = flower_pollination::solve(ctx, problem, flower_pollination::FPAOptions{o.heuristic, o.fpa_mutation_probability}, o.progress, init, o.seed, o.fpa_runs); break;
         }
         const auto t1 = std::chrono::steady_clock::now();
         const uint64_t ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();
