@@ -205,7 +205,10 @@ def test_lk_max_depth_beyond_the_register_build(ctx):
     """the reference's max_depth is an unbounded usize (mod.rs:1252, recursion lin_kernighan.rs:265-340); up to 6
     the chain lives in registers (lk.hip), 7..16 run the same kernels built with larger chain arrays (lk_deep.hip).  Limit + 1 and
     beyond against the oracle on small instances with large options: every form of the scan (fused pick with parked walks at
-    k (k+1)^2 <= 1024, the flat form beyond, the chip-wide step from n = 1500, the single-workgroup cross-check)."""
+    k (k+1)^2 <= 1024, the flat form beyond, the chip-wide step from n = 1500, the single-workgroup cross-check).  (n = 300 is below
+    the LDS form's cut-over, but k_lk_ils does not apply to these options — k^(max_depth-1) nodes do not fit its level queues,
+    lk_ils_qcap returns 0 — so the default context runs the chip-wide scans here.  All from the NN seed, whose chains stay short:
+    start tours whose first move is a chain of 1..16 exchanges are filed in tests/golden/goldens_lk_chains.json.)"""
     import teeline_amd as TA
     from test_gpu_lk import assert_same, gpu_lk, lattice
     xy = O.synth_xy(300, seed=21)
