@@ -936,6 +936,77 @@ int tl_flower_pollination_plan(uint32_t n, uint32_t n_nearest, uint32_t count, i
 int tl_fpa_selftest_pollinate(tl_ctx *ctx, const uint32_t *flower, const uint32_t *source, const uint32_t *target, const uint32_t *prefix, uint32_t n,
                               uint32_t count, uint32_t *out, uint32_t *out_len);
 
+/* ---- the gravitational search solver (src/tsp/gravitational_search.rs:23-145) ------------------ */
+/* The reference's gravitational search with its quirks kept.  N = max(n_nearest, 25) agents; agent 0 starts on init_pos if given,
+ * every other agent (and agent 0 without init_pos) on a Fisher-Yates shuffle of city order; costs are tour_length as everywhere
+ * here (closing edge first, sequential f32).  gbest is a COPY of the FIRST minimum agent.
+ * Epoch e, from the costs at its start: worst = the f32 maximum; sum_fitness = the f64 sum in agent order of (double)(worst - c),
+ * the subtraction in f32; below f64::EPSILON every mass is 1 / N, else mass_a = (double)(worst - c_a) / sum_fitness.  kbest: the
+ * first ceil(N / 2) agents by descending mass.  g = 20 exp(-(1.0 e) / max(epochs, 1)).  Then the agents IN INDEX ORDER: INERTIA_W
+ * is 0, nothing of the old velocity is kept; for j in kbest order, j != i: n_swaps = round((r g) mass_j) (tl_gsa_pull_swaps: left
+ * to right, half away from zero); if not 0, the first n_swaps pairs of swap_sequence(positions[i], positions[j]) — positions[j] AS
+ * IT STANDS, an agent of a lower index has already moved in this epoch — are appended; the concatenation is cut to v_max =
+ * max(ceil(0.35 n), 1) and applied in order; costs[i] = tour_length; costs[i] < gbest_cost (strict) replaces gbest AT ONCE.  The
+ * masses and the ranking stay those of the epoch's start.  The result is gbest and its cost; epochs = 0 returns the start gbest.
+ * THREE THINGS ARE THIS PROJECT'S SPECIFICATION, NOT THE REFERENCE'S (tests/_gsa_oracle.py is the
+ * statement; csrc/gsa_spec.h the text).  The draws: tl_genetic_algorithm's stream, u(seed, run, event, slot) (tl_gsa_draw =
+ * tl_ga_draw); the pull of agent j on agent i in epoch e owns the event (e N + i) N + j — the agent index, not its rank — and r is
+ * slot 0, (u >> 11) 2^-53; start agent i owns the events 2^58 + i n + j, slot 26, as the swarm's do; a draw the reference would
+ * not have made (j == i, j outside kbest) is not read.  The order among EQUAL masses: the reference's sort_unstable_by leaves it
+ * unspecified; here ties go in ASCENDING AGENT INDEX (tl_gsa_masses).  exp: the fixed f64 sequence of the Levy step
+ * (tl_gsa_g), not libm's.  Since r < 1, g <= 20 and mass <= 1, n_swaps <= 20.
+ * On the device (csrc/gravitational_search.hip) one workgroup per run walks the agents in order; the pulls of an agent are
+ * computed at once, a wave each, and only the first n_swaps pairs of a sequence are looked for.  The schedule is one launch per
+ * span of up to 4096 epochs, or of up to opts->span_epochs where that is not 0 (1: one launch per epoch).  Same results: the
+ * cross-check form.  (It is an option and not a context flag because the 31 flag bits are all given out.)
+ * opts NULL: the defaults (10 000 epochs, n_nearest 3: HeuristicOptions::default; span_epochs 0).  n = 0 and n = 1: the reference does not
+ * panic — TL_OK, the empty route or the one city at cost 0.  A start cost that is NaN, or a mass that is NaN at an epoch's start
+ * (a cost that is not finite: only the matrix form can produce one): TL_ERR_REF_PANICS (partial_cmp(..).unwrap()), found on the
+ * device and reported after the launches; the outputs are then unspecified.  init_pos not a permutation: TL_ERR_BADARG.
+ * epochs = 2^32 - 1, more than 4096 agents, n > tl_gravitational_search_max_n and a context whose flags hold a bit no flag has:
+ * TL_ERR_UNSUPPORTED, before anything of size n is read or allocated.  dm_packed as in tl_sim_anneal.
+ * tl_gravitational_search runs run 0.  stats (optional): sweeps = epochs, candidates = moves (epochs x N), moves = gbest
+ * improvements; tl_gravitational_search_population's stats are these summed over its runs.
+ * tl_gravitational_search_trace: run `run` of the seed, the same result plus a log of 4 words per record: epoch, agent, cost bits,
+ * the index of the record's route in route_log (0xFFFFFFFF beyond route_cap).  Record 0 is the start gbest (epoch 0xFFFFFFFF, the
+ * agent it was copied from); every gbest improvement follows in the order it happened.  *log_len counts the records there are;
+ * the log holds the first log_cap, route_log (optional, route_cap x n) the routes of the first route_cap.  epoch_log (optional,
+ * epoch_cap rows of 3 N + 2 words): for the first epoch_cap epochs every agent's cost bits after its move; every agent's
+ * velocity length (after the cut to v_max); every agent's live pulls (the j of kbest other than i with n_swaps > 0, cut or not);
+ * then the bits of g, low word first.  The reference's message sequence is PathUpdate(record 0), per epoch a PathUpdate per record
+ * of that epoch and EpochUpdate(epoch), then Done.
+ * tl_gravitational_search_population: as tl_particle_swarm_population.  Run c of any batch equals first_run = c, count = 1.
+ * Host-only queries: tl_gsa_draw; tl_gsa_g; tl_gsa_pull_swaps; tl_gsa_masses — the masses of `agents` costs and out_rank, the
+ * agents by rank (1 <= agents <= 4096, else TL_ERR_BADARG; a NaN mass: TL_ERR_REF_PANICS, the masses written, the ranks not);
+ * tl_gravitational_search_plan — the agents, the threads of the epochs' workgroup and the runs one launch sequence holds (outputs
+ * optional; all 0 where n is outside 2 .. the limit or N > 4096; a flag bit no flag has: TL_ERR_UNSUPPORTED; the entries plan
+ * with 8 GiB, at most 65 535 runs a sequence).  tl_gravitational_search_max_n: the largest n (a workgroup keeps 8 n bytes in LDS).
+ * tl_gsa_selftest_pull: the DEVICE's pull on `count` given pairs of permutations of 0 .. n - 1 (count x n each) and a prefix
+ * length each (<= 20): out_len[c] = min(prefix[c], the length of swap_sequence(from, target)), out_pairs (count x 20 words) its
+ * first out_len[c] pairs, i | j << 16, then 0xFFFFFFFF (1 <= n <= the limit, 1 <= count <= 65535, else TL_ERR_BADARG). */
+typedef struct tl_gsa_opts { /* HeuristicOptions, src/tsp/mod.rs:596-611: what gravitational_search reads of it */
+    uint32_t epochs;
+    uint32_t n_nearest;
+    uint32_t span_epochs; /* not the reference's: epochs of one launch at most; 0: the default, 4096.  The result does not depend on it */
+} tl_gsa_opts;
+uint32_t tl_gravitational_search_max_n(const tl_ctx *ctx);
+int tl_gravitational_search(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_gsa_opts *opts, uint64_t seed,
+                            uint32_t *out_pos, float *out_cost, tl_stats *stats);
+int tl_gravitational_search_trace(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_gsa_opts *opts,
+                                  uint64_t seed, uint32_t run, uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *log, uint32_t log_cap,
+                                  uint32_t *log_len, uint32_t *route_log, uint32_t route_cap, uint32_t *epoch_log, uint32_t epoch_cap);
+int tl_gravitational_search_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
+                                       uint32_t first_run, uint32_t count, const tl_gsa_opts *opts, uint64_t seed, uint32_t *out_pos, float *out_costs,
+                                       uint32_t *out_moves, uint32_t *best_index, tl_stats *stats);
+uint64_t tl_gsa_draw(uint64_t seed, uint32_t run, uint64_t event, uint32_t slot);
+double tl_gsa_g(uint32_t epoch, uint32_t epochs);
+uint32_t tl_gsa_pull_swaps(double r, double g, double mass);
+int tl_gsa_masses(const float *costs, uint32_t agents, double *out_masses, uint32_t *out_rank);
+int tl_gravitational_search_plan(uint32_t n, uint32_t n_nearest, uint32_t count, int cus, int lds_bytes, uint64_t workspace_bytes, uint32_t flags,
+                                 uint32_t *agents, int *threads, uint32_t *per_launch);
+int tl_gsa_selftest_pull(tl_ctx *ctx, const uint32_t *from, const uint32_t *target, const uint32_t *prefix, uint32_t n, uint32_t count, uint32_t *out_pairs,
+                         uint32_t *out_len);
+
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts
  * first..first+count as above; seed ignored otherwise).  d_out_pos: count x n u32, d_out_cost: count f32,

@@ -75,6 +75,16 @@ pub struct FpaOpts {
     pub mutation_probability: f32,
 }
 
+/// `tl_gsa_opts`: what gravitational_search reads of HeuristicOptions (src/tsp/mod.rs:596-611); N = max(n_nearest, 25)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GsaOpts {
+    pub epochs: u32,
+    pub n_nearest: u32,
+    /// epochs of one launch at most; 0: the default.  The result does not depend on it.
+    pub span_epochs: u32,
+}
+
 /// `tl_lk_progress_fn` (include/teeline_gpu.h): called by `tl_lk_live` on the calling thread while the search runs.
 pub type LkProgressFn = unsafe extern "C" fn(user: *mut c_void, best_pos: *const u32, n: u32, best_dist: f32);
 
@@ -201,6 +211,19 @@ unsafe extern "C" {
     fn tl_fpa_global_swaps(levy: f64, len: u32) -> u32;
     fn tl_fpa_local_swaps(epsilon: f64, len: u32) -> u32;
     fn tl_fpa_partners(seed: u64, run: u32, epoch: u32, i: u32, flowers: u32, j: *mut u32, k: *mut u32) -> i32;
+    fn tl_gravitational_search_max_n(ctx: *const TlCtx) -> u32;
+    fn tl_gravitational_search(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, opts: *const GsaOpts, seed: u64,
+                               out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats) -> i32;
+    fn tl_gravitational_search_trace(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, opts: *const GsaOpts, seed: u64,
+                                     run: u32, out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats, log: *mut u32, log_cap: u32, log_len: *mut u32,
+                                     route_log: *mut u32, route_cap: u32, epoch_log: *mut u32, epoch_cap: u32) -> i32;
+    fn tl_gravitational_search_population(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, init_count: u32,
+                                          first_run: u32, count: u32, opts: *const GsaOpts, seed: u64, out_pos: *mut u32, out_costs: *mut f32,
+                                          out_moves: *mut u32, best_index: *mut u32, stats: *mut Stats) -> i32;
+    fn tl_gsa_draw(seed: u64, run: u32, event: u64, slot: u32) -> u64;
+    fn tl_gsa_g(epoch: u32, epochs: u32) -> f64;
+    fn tl_gsa_pull_swaps(r: f64, g: f64, mass: f64) -> u32;
+    fn tl_gsa_masses(costs: *const f32, agents: u32, out_masses: *mut f64, out_rank: *mut u32) -> i32;
     fn tl_nearest_neighbor(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, n_nearest: u32,
                            out_pos: *mut u32, out_cost: *mut f32) -> c_int;
     fn tl_greedy_edge(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
@@ -743,6 +766,28 @@ impl Context {
             tl_flower_pollination(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), &opts, seed, t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats)
         };
         self.check(rc).map(|_| t)
+    }
+
+    /// `gravitational_search::solve` (gravitational_search.rs:23-145), run 0 of `seed`, max(n_nearest, 25) agents.  The algorithm is
+    /// the reference's; its random draws, the order among equal masses and its exp are the library's own specification
+    /// (include/teeline_gpu.h).  (Written against the header; not compiled here: no Rust toolchain on the build machine, see
+    /// scripts/check_rust.sh.)
+    pub fn gravitational_search(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, epochs: u32, n_nearest: u32, seed: u64) -> Result<Tour, Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let opts = GsaOpts { epochs, n_nearest, span_epochs: 0 };
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        // SAFETY: the slices hold n cities / n positions (check_inputs); the outputs are sized for n.
+        let rc = unsafe {
+            tl_gravitational_search(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), &opts, seed, t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats)
+        };
+        self.check(rc).map(|_| t)
+    }
+
+    /// Largest n of `gravitational_search` (a workgroup keeps 8 n bytes in LDS).
+    pub fn gravitational_search_max_n(&self) -> u32 {
+        // SAFETY: a live context.
+        unsafe { tl_gravitational_search_max_n(self.raw) }
     }
 
     /// Largest n of `flower_pollination` (a workgroup keeps 10 n bytes in LDS).

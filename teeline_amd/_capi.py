@@ -71,6 +71,8 @@ SYMBOLS = [
     "tl_cs_draw", "tl_levy_from_words", "tl_cs_flight_length", "tl_cs_pa", "tl_cs_selftest_levy", "tl_cs_selftest_reversals",
     "tl_flower_pollination", "tl_flower_pollination_trace", "tl_flower_pollination_population", "tl_flower_pollination_max_n", "tl_flower_pollination_plan",
     "tl_fpa_draw", "tl_fpa_switch_prob", "tl_fpa_global_swaps", "tl_fpa_local_swaps", "tl_fpa_partners", "tl_fpa_selftest_pollinate",
+    "tl_gravitational_search", "tl_gravitational_search_trace", "tl_gravitational_search_population", "tl_gravitational_search_max_n",
+    "tl_gravitational_search_plan", "tl_gsa_draw", "tl_gsa_g", "tl_gsa_pull_swaps", "tl_gsa_masses", "tl_gsa_selftest_pull",
 ]
 
 
@@ -105,6 +107,11 @@ class TlCsOpts(C.Structure):
 class TlFpaOpts(C.Structure):
     """tl_fpa_opts: what flower_pollination reads of FPAOptions (src/tsp/mod.rs:998-1010)"""
     _fields_ = [("epochs", C.c_uint32), ("n_nearest", C.c_uint32), ("mutation_probability", C.c_float)]
+
+
+class TlGsaOpts(C.Structure):
+    """tl_gsa_opts: what gravitational_search reads of HeuristicOptions (src/tsp/mod.rs:596-611), and the epochs of one launch (0: the default)"""
+    _fields_ = [("epochs", C.c_uint32), ("n_nearest", C.c_uint32), ("span_epochs", C.c_uint32)]
 
 
 # tl_lk_progress_fn: void (*)(void *user, const uint32_t *best_pos, uint32_t n, float best_dist)
@@ -285,5 +292,20 @@ def load():
     L.tl_fpa_partners.argtypes = [u64, u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
     L.tl_flower_pollination_plan.argtypes = [u32, u32, u32, i32, i32, u64, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
     L.tl_fpa_selftest_pollinate.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, vp]
+    L.tl_gravitational_search_max_n.argtypes = [vp]
+    L.tl_gravitational_search_max_n.restype = u32
+    L.tl_gravitational_search.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlGsaOpts), u64, vp, f32p, C.POINTER(TlStats)]
+    L.tl_gravitational_search_trace.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlGsaOpts), u64, u32, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32), vp, u32,
+                                                vp, u32]
+    L.tl_gravitational_search_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, C.POINTER(TlGsaOpts), u64, vp, vp, vp, C.POINTER(u32), C.POINTER(TlStats)]
+    L.tl_gsa_draw.argtypes = [u64, u32, u64, u32]
+    L.tl_gsa_draw.restype = u64
+    L.tl_gsa_g.argtypes = [u32, u32]
+    L.tl_gsa_g.restype = C.c_double
+    L.tl_gsa_pull_swaps.argtypes = [C.c_double, C.c_double, C.c_double]
+    L.tl_gsa_pull_swaps.restype = u32
+    L.tl_gsa_masses.argtypes = [vp, u32, vp, vp]
+    L.tl_gravitational_search_plan.argtypes = [u32, u32, u32, i32, i32, u64, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
+    L.tl_gsa_selftest_pull.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
     _lib = L
     return L

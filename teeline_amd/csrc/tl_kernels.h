@@ -533,8 +533,40 @@ hipError_t launch_fpa_commit(const FpaArgs &A, uint32_t runs, hipStream_t s);  /
 hipError_t launch_fpa_selftest_pollinate(const uint16_t *flower, const uint16_t *source, const uint16_t *target, const uint32_t *prefix, uint32_t n, uint32_t count,
                                          uint16_t *out, uint32_t *out_len, hipStream_t s);
 
+// gravitational_search.hip — the gravitational search solver, the run a grid dimension, a span of epochs per launch
+struct GsaArgs {
+    const float2 *xy;       // n cities, city order (coordinate form)
+    const float *dm_full;   // the matrix expanded to row-major n x n, or nullptr
+    const uint32_t *init;   // the initial tour(s) of agent 0, or nullptr (a shuffle)
+    uint32_t init_stride;   // 0: one tour for every run, n: one per run
+    uint16_t *pos;          // [runs][agents][n] the positions
+    uint16_t *gbest;        // [runs][n]
+    float *cost;            // [runs][agents] the agents' costs
+    double *mass;           // [runs][agents] the masses of the epoch being walked
+    uint16_t *kbest;        // [runs][agents] the agents by rank; the first ceil(agents / 2) are read
+    uint32_t *state;        // [runs][8] gbest cost bits, gbest improvements, 1 where the reference would have panicked
+    uint32_t *out_pos;      // [runs][n] gbest after the last epoch
+    float *out_cost;        // [runs] its cost
+    uint32_t *log;          // optional: [log_cap][4] epoch, agent, cost bits, route index: the start gbest, then every improvement of run 0
+    uint32_t *route_log;    // optional: [route_cap][n] their routes
+    uint32_t *epoch_log;    // optional: [epoch_cap][3 agents + 2] of run 0: cost bits | velocity length | live pulls | g's bits, low word first
+    uint64_t seed;
+    uint32_t log_cap, route_cap, epoch_cap;
+    uint32_t first_run;     // stream id of the launch's run 0
+    uint32_t n, agents, vmax;
+    uint32_t e0, e1, epochs;  // the span [e0, e1) of the schedule of `epochs` epochs
+    uint32_t last;          // no launch follows — write the result
+};
+size_t gravitational_search_lds_bytes(uint32_t n);  // LDS of one workgroup (every kernel)
+uint32_t gravitational_search_max_n(int lds_budget);
+int gravitational_search_threads(uint32_t n);
+hipError_t launch_gsa_init(const GsaArgs &A, uint32_t runs, hipStream_t s);    // start positions and costs, then the first minimum
+hipError_t launch_gsa_epochs(const GsaArgs &A, uint32_t runs, hipStream_t s);  // the epochs [e0, e1): one workgroup per run, the agents in order
+hipError_t launch_gsa_selftest_pull(const uint16_t *from, const uint16_t *to, const uint32_t *want, uint32_t n, uint32_t count, uint32_t *out_pairs,
+                                    uint32_t *out_len, hipStream_t s);
+
 // lk.hip
-struct LkState {           // device-side state machine of the multi-CU LK variant
+struct LkState {          // device-side state machine of the multi-CU LK variant
     uint32_t key;            // min pair index with a valid chain in the current scan (0xFFFFFFFF: none)
     uint32_t finished;
     uint32_t stage;          // 0: initial lk_pass, 1: ILS epochs

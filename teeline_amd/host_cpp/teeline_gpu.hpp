@@ -1358,8 +1358,69 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const FPAOptions 
 }
 }  // namespace flower_pollination
 
+namespace gravitational_search {  // gravitational_search.rs:23-145
+// The algorithm is the reference's; its random draws, the order among equal masses and its exp are this project's specification
+// (include/teeline_gpu.h).  The agent count is max(opts.n_nearest, 25).  runs > 1: runs 0 .. runs-1 of the seed at once, the best one returned (lowest
+// cost, then lowest run).  With a progress callback the reference's messages — PathUpdate(start gbest), per epoch a PathUpdate per
+// gbest improvement in agent order and EpochUpdate(epoch), then Done (gravitational_search.rs:72-74,127-143) — are replayed from that
+// run's improvement log.
+inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
+                      uint64_t seed = 1, uint32_t runs = 1)
+{
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size();
+    const tl_gsa_opts o{(uint32_t)opts.epochs, (uint32_t)std::min<size_t>(opts.n_nearest, 0xFFFFFFFFu), 0u};
+    std::vector<uint32_t> init, out(n);
+    if (init_tour) init = problem.positions_of(*init_tour);
+    const uint32_t *ip = init_tour ? init.data() : nullptr;
+    float cost = 0.f;
+    tl_stats st{};
+    uint32_t run = 0;
+    if (runs > 1) {
+        std::vector<uint32_t> outs((size_t)runs * n);
+        std::vector<float> costs(runs);
+        ctx.check(tl_gravitational_search_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, runs, &o, seed, outs.data(), costs.data(),
+                                               nullptr, &run, &st));
+        std::copy(outs.begin() + (size_t)run * n, outs.begin() + (size_t)(run + 1) * n, out.begin());
+        cost = costs[run];
+        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
+    } else if (!(progress_tx && *progress_tx)) {
+        ctx.check(tl_gravitational_search(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, out.data(), &cost, &st));
+        return detail::finish(problem, out, cost, st, nullptr);
+    }
+    uint32_t rows = 0, cap = 64;
+    std::vector<uint32_t> log, routes;
+    for (;;) {  // the log holds every improvement: ask again with the count where 64 records were too few
+        log.assign((size_t)cap * 4, 0u);
+        routes.assign((size_t)cap * std::max(n, 1u), 0u);
+        ctx.check(tl_gravitational_search_trace(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, run, out.data(), &cost, &st, log.data(), cap, &rows,
+                                          routes.data(), cap, nullptr, 0u));
+        if (rows <= cap) break;
+        cap = rows;
+    }
+    std::vector<size_t> route(n);
+    const auto path_update = [&](uint32_t k) {
+        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[routes[(size_t)k * n + q]].id;
+        float d;
+        std::memcpy(&d, &log[(size_t)k * 4 + 2], 4);
+        (*progress_tx)(ProgressKind::PathUpdate, route, d);
+    };
+    if (rows > 0) {
+        path_update(0);
+        uint32_t k = 1;
+        for (uint32_t e = 0; e < o.epochs; ++e) {
+            for (; k < rows && log[(size_t)k * 4] == e; ++k) path_update(k);
+            (*progress_tx)(ProgressKind::EpochUpdate, std::vector<size_t>{e}, 0.0f);
+        }
+    }
+    Solution s = detail::finish(problem, out, cost, st, nullptr);
+    (*progress_tx)(ProgressKind::Done, s.route_, cost);
+    return s;
+}
+}  // namespace gravitational_search
+
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
-enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch, FlowerPollination };
+enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch, FlowerPollination, GravitationalSearch };
 
 inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
 {
@@ -1382,10 +1443,11 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
     else if (s == "particle_swarm") out = Solvers::ParticleSwarm;  // (the alias `pso` likewise)
     else if (s == "cuckoo_search") out = Solvers::CuckooSearch;  // (the alias `cs` likewise)
     else if (s == "flower_pollination") out = Solvers::FlowerPollination;  // (the alias `fpa` likewise)
+    else if (s == "gravitational_search") out = Solvers::GravitationalSearch;  // (the alias `gsa` likewise)
     else {
         static const char *cpu_only[] = {"aco", "branch_bound",
                                          "cs", "fpa", "fourier", "ga", "gsa",
-                                         "gravitational_search", "pso", "sa",
+                                         "pso", "sa",
                                          "som", "kohonen", "kohonen_som", "stochastic_hill", "tabu"};
         for (const char *c : cpu_only)
             if (s == c) {
@@ -1396,6 +1458,7 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
                 if (s == "pso") why += "; the seeded particle swarm of this build is `particle_swarm`";
                 if (s == "cs") why += "; the seeded cuckoo search of this build is `cuckoo_search`";
                 if (s == "fpa") why += "; the seeded flower pollination of this build is `flower_pollination`";
+                if (s == "gsa") why += "; the seeded gravitational search of this build is `gravitational_search`";
                 return false;
             }
         why = "unknown solver";  // FromStr's Err (mod.rs:588)
@@ -1423,6 +1486,7 @@ inline const char *solver_name(Solvers s)
         case Solvers::ParticleSwarm: return "particle_swarm";
         case Solvers::CuckooSearch: return "cuckoo_search";
         case Solvers::FlowerPollination: return "flower_pollination";
+        case Solvers::GravitationalSearch: return "gravitational_search";
         default: return "shuffle";
     }
 }
@@ -1444,6 +1508,7 @@ struct StageOptions {
     uint32_t cs_runs = 1;  // a cuckoo_search stage runs this many runs and keeps the best
     float fpa_mutation_probability = 0.001f;  // FPAOptions::mutation_probability (mod.rs:1007)
     uint32_t fpa_runs = 1;  // a flower_pollination stage runs this many runs and keeps the best
+    uint32_t gsa_runs = 1;  // a gravitational_search stage runs this many runs and keeps the best
     uint64_t seed = 1;  // LK kicks, shuffle, SA, tabu and GA draws
     const ProgressFn *progress = nullptr;  // handed to every stage's solve() (the reference's CLI passes None; teeline-qt a sender)
 };
@@ -1512,6 +1577,7 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             case Solvers::ParticleSwarm: sol = particle_swarm::solve(ctx, problem, o.heuristic, o.progress, init, o.seed, o.pso_runs); break;
             case Solvers::CuckooSearch: sol = cuckoo_search::solve(ctx, problem, cuckoo_search::CSOptions{o.heuristic, o.cs_mutation_probability}, o.progress, init, o.seed, o.cs_runs); break;
             case Solvers::FlowerPollination: sol = flower_pollination::solve(ctx, problem, flower_pollination::FPAOptions{o.heuristic, o.fpa_mutation_probability}, o.progress, init, o.seed, o.fpa_runs); break;
+            case Solvers::GravitationalSearch: sol = gravitational_search::solve(ctx, problem, o.heuristic, o.progress, init, o.seed, o.gsa_runs); break;
         }
         const auto t1 = std::chrono::steady_clock::now();
         const uint64_t ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();

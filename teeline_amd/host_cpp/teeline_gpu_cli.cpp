@@ -27,6 +27,9 @@
 //               max(--n-nearest, 25) flowers and --mutation-probability P (FPAOptions, mod.rs:998-1010: switch_prob = 0.8 where P < 0.01,
 //               else P); --runs K (K runs of the seed at once, the best kept); `solve flower_pollination` alone is
 //               pipeline(shuffle, flower_pollination) (mod.rs:2155)
+//     gravity  : gravitational_search (long name only: `gsa` stays refused) runs --epochs epochs (default 10000) of seeded draws (--seed)
+//               with max(--n-nearest, 25) agents; --runs K (K runs of the seed at once, the best kept); `solve gravitational_search`
+//               alone is pipeline(shuffle, gravitational_search) (mod.rs:2157)
 //     solve   : 2opt / 3opt / or_opt / lk auto-expand to pipeline(nn, solver) unless --no-seed (main.rs:387-397, mod.rs:129-139);
 //               gec (greedy_edge), sav (savings) and chr (christofides) are constructions and run alone; so does bhk (bellman_karp),
 //               the exact solver (n <= 26, mod.rs:2137) — as a later pipeline stage it ignores its seed
@@ -64,7 +67,7 @@ struct Args {
 {
     if (why) std::fprintf(stderr, "error: %s\n", why);
     std::fprintf(stderr,
-                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|genetic_algorithm|ant_colony|particle_swarm|cuckoo_search|flower_pollination|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
+                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|genetic_algorithm|ant_colony|particle_swarm|cuckoo_search|flower_pollination|gravitational_search|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
                  "                         [--optimal-tour FILE] [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P]\n"
                  "                         [--n_nearest K] [--max-depth D] [--seed S] [--best-sweep] [--device N] [--stats]\n"
                  "                         [--progress-digest] [--exact-walk]\n"
@@ -135,7 +138,7 @@ Args parse(int argc, char **argv)
         else if (s == "--beta") a.opt.aco.beta = std::stof(val());
         else if (s == "--evaporation-rate" || s == "--evaporation_rate") a.opt.aco.evaporation_rate = std::stof(val());
         else if (s == "--num-ants" || s == "--num_ants") a.opt.aco.num_ants = parse_usize(s, val());
-        else if (s == "--runs") a.opt.aco_runs = a.opt.pso_runs = a.opt.cs_runs = a.opt.fpa_runs = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
+        else if (s == "--runs") a.opt.aco_runs = a.opt.pso_runs = a.opt.cs_runs = a.opt.fpa_runs = a.opt.gsa_runs = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--chains") a.opt.sa_chains = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--platoo_epochs" || s == "--platoo-epochs") a.opt.heuristic.platoo_epochs = a.opt.lk.heuristic.platoo_epochs = parse_usize(s, val());
         else if (s == "--n_nearest" || s == "--n-nearest") a.opt.heuristic.n_nearest = a.opt.lk.heuristic.n_nearest = parse_usize(s, val());
@@ -278,7 +281,7 @@ int run(int argc, char **argv)
                 // auto_expand_with_nn (mod.rs:129-139): deterministic local searches are seeded with a nearest-neighbour stage
                 const bool expand = s == Solvers::TwoOpt || s == Solvers::ThreeOpt || s == Solvers::LinKernighan || s == Solvers::OrOpt || s == Solvers::TabuSearch;
                 if (!a.no_seed && expand) stages = {Solvers::NearestNeighbor, s};
-                else if (!a.no_seed && (s == Solvers::SimulatedAnnealing || s == Solvers::GeneticAlgorithm || s == Solvers::AntColony || s == Solvers::ParticleSwarm || s == Solvers::CuckooSearch || s == Solvers::FlowerPollination)) stages = {Solvers::RandomShuffle, s};  // mod.rs:144-157
+                else if (!a.no_seed && (s == Solvers::SimulatedAnnealing || s == Solvers::GeneticAlgorithm || s == Solvers::AntColony || s == Solvers::ParticleSwarm || s == Solvers::CuckooSearch || s == Solvers::FlowerPollination || s == Solvers::GravitationalSearch)) stages = {Solvers::RandomShuffle, s};  // mod.rs:144-157
                 else stages = {s};
             }
         } else {
@@ -376,7 +379,7 @@ int run(int argc, char **argv)
         if (a.progress_digest) {
             std::fprintf(stderr, "progress: path_updates=%llu city_changes=%llu done=%llu digest=%016llx", (unsigned long long)dg.n[0],
                          (unsigned long long)dg.n[1], (unsigned long long)dg.n[2], (unsigned long long)dg.h);
-            if (dg.n[3]) std::fprintf(stderr, " epoch_updates=%llu", (unsigned long long)dg.n[3]);  // (ant_colony, particle_swarm, cuckoo_search and flower_pollination stages only)
+            if (dg.n[3]) std::fprintf(stderr, " epoch_updates=%llu", (unsigned long long)dg.n[3]);  // (ant_colony, particle_swarm, cuckoo_search, flower_pollination and gravitational_search stages only)
             std::fprintf(stderr, "\n");
         }
         const Solution &tour = outcomes.back().solution;
