@@ -1007,6 +1007,76 @@ int tl_gravitational_search_plan(uint32_t n, uint32_t n_nearest, uint32_t count,
 int tl_gsa_selftest_pull(tl_ctx *ctx, const uint32_t *from, const uint32_t *target, const uint32_t *prefix, uint32_t n, uint32_t count, uint32_t *out_pairs,
                          uint32_t *out_len);
 
+/* ---- the Kohonen self-organising map solver (src/tsp/som.rs:12-186) ---------------------------- */
+/* The reference's SOM with its quirks kept.  n < 2: the trivial route.  A start tour is ignored (the entries take none).  The
+ * cities are normalised per axis in f64 with span max(max - min, 1e-9); the centroid is a sequential f64 sum in city order;
+ * M = n neuron_multiplier neurons start on a circle of radius 0.1 around it.  For t = 1 .. epochs: eta = eta0 exp(-t / epochs),
+ * sigma = max(sigma0 exp(-t / epochs), 1.0) with sigma0 = radius_fraction M; one city is drawn with replacement; the BMU is the
+ * FIRST minimum of (nx - cx)^2 + (ny - cy)^2; every neuron at ring distance d = min(|i - bmu|, M - |i - bmu|) gets
+ * h = exp(((-d) d) / (2 sigma^2)), is skipped when h < 1e-3, else neuron += (eta h) (city - neuron) per axis, in place.  The tour:
+ * every city's first-minimum neuron, the cities sorted by (neuron, distance, city index).  The cost: the f32 sequential
+ * tour_length (tl_tour_length), from dm_packed where one is given, else from xy.
+ * THREE THINGS ARE THIS PROJECT'S SPECIFICATION, NOT THE REFERENCE'S (tests/_som_oracle.py is the
+ * statement; csrc/som_spec.h the text) — the reference draws from an unseeded RNG and calls libm, so no run of it can be
+ * reproduced.  The draw: the city of epoch t of run r is position(u(seed, r, event t, slot 0), n) on tl_genetic_algorithm's stream
+ * (tl_som_draw).  exp: the fixed f64 sequence of the Levy step, for the schedule and for h; a neuron with
+ * y = ((-d) d) / two_sigma_sq < -8.0 is skipped without an exp (exp(-8) = 3.4e-4 is below the cut) (tl_som_h, tl_som_schedule).
+ * The start ring: cos and sin of 2 pi (i / M) from the Levy step's exact quadrant reduction and its two polynomials
+ * (tl_som_ring_init).  All f64, no fused multiply-add.
+ * The map trains on the COORDINATES: xy is required, dm_packed (optional) only prices the tour.  xy NULL, a coordinate that is
+ * not finite, or options outside SOMOptions::validate (epochs >= 1, learning_rate and radius_fraction in (0, 1],
+ * neuron_multiplier >= 1; also form > 2 or reserved != 0): TL_ERR_BADARG, before anything is launched.  epochs = 2^32 - 1, more than
+ * 65 536 neurons, form = 1 with a ring that does not fit the LDS, and a context whose flags hold a bit no flag has:
+ * TL_ERR_UNSUPPORTED.  opts NULL: the defaults (100 000 epochs, learning_rate 0.8, radius_fraction 0.1, neuron_multiplier 8).
+ * On the device (csrc/kohonen_som.hip) one workgroup per run keeps the ring in LDS (form 1: 512 + 16 M bytes) or, where it does
+ * not fit, in the run's workspace block (form 2) — the same kernel body and the same result; opts->form forces either.
+ * tl_kohonen_som runs run 0.  stats (optional): sweeps = epochs, candidates = epochs x M, summed over the runs of a population.
+ * tl_kohonen_som_trace: run `run` of the seed, the same result plus log (optional, log_cap rows of 2 words): (city, bmu) of epoch
+ * t at row t - 1; out_ring (optional): the final ring, x[M] then y[M]; and one record per progress message pair of the reference
+ * (som.rs:117-145), in its order: with checkpoint = max(epochs / 10, 1), for every t with t % checkpoint == 0 the record
+ * (cp_epochs = t, the tour extracted then, its cost bits) — EpochUpdate(t) then PathUpdate —, and where epochs % checkpoint != 0
+ * one last record with cp_epochs = 0xFFFFFFFF: the final PathUpdate.  Then Done.  *cp_len counts the records there are (at most
+ * 19); cp_epochs, cp_tours (cp_cap x n) and cp_cost_bits hold the first cp_cap.
+ * tl_kohonen_som_population: runs first_run .. first_run + count - 1 of the seed at once; out_pos count x n, out_costs and
+ * best_index (lowest cost, then lowest index) optional.  Run c of any batch equals first_run = c, count = 1.
+ * Host-only queries: tl_som_draw — the city of an epoch; tl_som_schedule — eta, sigma, two_sigma_sq and the update's radius of
+ * epoch 1 <= t <= epochs for 1 <= M <= 65 536 (else TL_ERR_BADARG; outputs optional); tl_som_h — 1 and h where a neuron at ring
+ * distance d is moved, 0 where it is skipped (h = 0 where no exp was taken); tl_som_ring_init — the start ring (x[M] then y[M]) and
+ * optionally the normalised cities (x[n] then y[n]); tl_kohonen_som_plan — the neurons, the threads of the training workgroup
+ * (about eight neurons a lane in whole waves: clamp(round_up(ceil(M / 8), 64), 64, 1024)), the form and the runs one launch
+ * sequence holds (outputs optional; all 0 where n < 2, M > 65 536, form 1 does not fit or the workspace holds no run; the entries
+ * plan with opts->work_bytes, 8 GiB where that is 0, at most 65 535 runs a sequence); tl_kohonen_som_max_n — the largest n for a
+ * multiplier and a form (0 or 2: the cap on M; 1: the LDS).
+ * tl_som_selftest_bmu: the DEVICE's BMU as the training finds it (out_bmu, n words: one reduction per given city, `threads` lanes,
+ * 0: the plan's) and as the extraction finds it (out_extract_bmu, optional), and the extraction's tour (out_tour, optional), on a
+ * ring (x[M] then y[M]) and normalised cities (x[n] then y[n]) given by the caller: how exact ties are planted. */
+typedef struct tl_som_opts { /* SOMOptions, src/tsp/mod.rs:1465-1499 */
+    uint32_t epochs;
+    uint32_t neuron_multiplier;
+    double learning_rate;
+    double radius_fraction;
+    uint32_t form;       /* not the reference's: 0 the plan decides, 1 the ring in LDS, 2 the ring in the workspace.  Same result */
+    uint32_t reserved;   /* 0 */
+    uint64_t work_bytes; /* not the reference's: the workspace one launch sequence plans with; 0: 8 GiB.  Same result */
+} tl_som_opts;
+uint32_t tl_kohonen_som_max_n(const tl_ctx *ctx, uint32_t neuron_multiplier, uint32_t form);
+int tl_kohonen_som(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const tl_som_opts *opts, uint64_t seed, uint32_t *out_pos, float *out_cost,
+                   tl_stats *stats);
+int tl_kohonen_som_trace(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const tl_som_opts *opts, uint64_t seed, uint32_t run,
+                         uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *log, uint32_t log_cap, double *out_ring, uint32_t *cp_epochs,
+                         uint32_t *cp_tours, uint32_t *cp_cost_bits, uint32_t cp_cap, uint32_t *cp_len);
+int tl_kohonen_som_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, uint32_t first_run, uint32_t count, const tl_som_opts *opts,
+                              uint64_t seed, uint32_t *out_pos, float *out_costs, uint32_t *best_index, tl_stats *stats);
+uint32_t tl_som_draw(uint64_t seed, uint32_t run, uint32_t epoch, uint32_t n);
+int tl_som_schedule(uint32_t epoch, uint32_t epochs, uint32_t neurons, double learning_rate, double radius_fraction, double *eta, double *sigma,
+                    double *two_sigma_sq, uint32_t *radius);
+int tl_som_h(double d, double two_sigma_sq, double *h);
+int tl_som_ring_init(const float *xy, uint32_t n, uint32_t neuron_multiplier, double *out_ring, double *out_cities);
+int tl_kohonen_som_plan(uint32_t n, uint32_t neuron_multiplier, uint32_t form, uint32_t count, int cus, int lds_bytes, uint64_t workspace_bytes, uint32_t flags,
+                        uint32_t *neurons, int *threads, uint32_t *form_out, uint32_t *per_launch);
+int tl_som_selftest_bmu(tl_ctx *ctx, const double *ring, uint32_t neurons, const double *cities, uint32_t n, int threads, uint32_t form, uint32_t *out_bmu,
+                        uint32_t *out_extract_bmu, uint32_t *out_tour);
+
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts
  * first..first+count as above; seed ignored otherwise).  d_out_pos: count x n u32, d_out_cost: count f32,

@@ -75,6 +75,20 @@ pub struct FpaOpts {
     pub mutation_probability: f32,
 }
 
+/// `tl_som_opts`: SOMOptions (src/tsp/mod.rs:1465-1499), the form of the ring (0: the plan decides, 1: LDS, 2: workspace) and the
+/// workspace one launch sequence plans with (0: the default).  The result depends on neither of the last two.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SomOpts {
+    pub epochs: u32,
+    pub neuron_multiplier: u32,
+    pub learning_rate: f64,
+    pub radius_fraction: f64,
+    pub form: u32,
+    pub reserved: u32,
+    pub work_bytes: u64,
+}
+
 /// `tl_gsa_opts`: what gravitational_search reads of HeuristicOptions (src/tsp/mod.rs:596-611); N = max(n_nearest, 25)
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -224,6 +238,19 @@ unsafe extern "C" {
     fn tl_gsa_g(epoch: u32, epochs: u32) -> f64;
     fn tl_gsa_pull_swaps(r: f64, g: f64, mass: f64) -> u32;
     fn tl_gsa_masses(costs: *const f32, agents: u32, out_masses: *mut f64, out_rank: *mut u32) -> i32;
+    fn tl_kohonen_som_max_n(ctx: *const TlCtx, neuron_multiplier: u32, form: u32) -> u32;
+    fn tl_kohonen_som(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, opts: *const SomOpts, seed: u64, out_pos: *mut u32, out_cost: *mut f32,
+                      stats: *mut Stats) -> i32;
+    fn tl_kohonen_som_trace(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, opts: *const SomOpts, seed: u64, run: u32, out_pos: *mut u32,
+                            out_cost: *mut f32, stats: *mut Stats, log: *mut u32, log_cap: u32, out_ring: *mut f64, cp_epochs: *mut u32, cp_tours: *mut u32,
+                            cp_cost_bits: *mut u32, cp_cap: u32, cp_len: *mut u32) -> i32;
+    fn tl_kohonen_som_population(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, first_run: u32, count: u32, opts: *const SomOpts, seed: u64,
+                                 out_pos: *mut u32, out_costs: *mut f32, best_index: *mut u32, stats: *mut Stats) -> i32;
+    fn tl_som_draw(seed: u64, run: u32, epoch: u32, n: u32) -> u32;
+    fn tl_som_schedule(epoch: u32, epochs: u32, neurons: u32, learning_rate: f64, radius_fraction: f64, eta: *mut f64, sigma: *mut f64, two_sigma_sq: *mut f64,
+                       radius: *mut u32) -> i32;
+    fn tl_som_h(d: f64, two_sigma_sq: f64, h: *mut f64) -> i32;
+    fn tl_som_ring_init(xy: *const f32, n: u32, neuron_multiplier: u32, out_ring: *mut f64, out_cities: *mut f64) -> i32;
     fn tl_nearest_neighbor(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, n_nearest: u32,
                            out_pos: *mut u32, out_cost: *mut f32) -> c_int;
     fn tl_greedy_edge(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
@@ -782,6 +809,26 @@ impl Context {
             tl_gravitational_search(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), &opts, seed, t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats)
         };
         self.check(rc).map(|_| t)
+    }
+
+    /// `som::solve` (som.rs:12-186), run 0 of `seed`.  The algorithm is the reference's; the city drawn in an epoch, exp (with a cut
+    /// at -8 before it) and the start ring's cos and sin are the library's own specification (include/teeline_gpu.h).  The map trains
+    /// on the coordinates; `dm_packed` only prices the tour.  (Written against the header; not compiled here: no Rust toolchain on
+    /// the build machine, see scripts/check_rust.sh.)
+    pub fn kohonen_som(&self, xy: &[f32], dm_packed: Option<&[f32]>, epochs: u32, learning_rate: f64, radius_fraction: f64, neuron_multiplier: u32, seed: u64) -> Result<Tour, Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, None);
+        let opts = SomOpts { epochs, neuron_multiplier, learning_rate, radius_fraction, form: 0, reserved: 0, work_bytes: 0 };
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        // SAFETY: the slices hold n cities (check_inputs); the outputs are sized for n.
+        let rc = unsafe { tl_kohonen_som(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), &opts, seed, t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats) };
+        self.check(rc).map(|_| t)
+    }
+
+    /// Largest n of `kohonen_som` for a multiplier and a form (0 or 2: the cap of 65 536 neurons; 1: the ring in LDS).
+    pub fn kohonen_som_max_n(&self, neuron_multiplier: u32, form: u32) -> u32 {
+        // SAFETY: a live context.
+        unsafe { tl_kohonen_som_max_n(self.raw, neuron_multiplier, form) }
     }
 
     /// Largest n of `gravitational_search` (a workgroup keeps 8 n bytes in LDS).

@@ -73,6 +73,8 @@ SYMBOLS = [
     "tl_fpa_draw", "tl_fpa_switch_prob", "tl_fpa_global_swaps", "tl_fpa_local_swaps", "tl_fpa_partners", "tl_fpa_selftest_pollinate",
     "tl_gravitational_search", "tl_gravitational_search_trace", "tl_gravitational_search_population", "tl_gravitational_search_max_n",
     "tl_gravitational_search_plan", "tl_gsa_draw", "tl_gsa_g", "tl_gsa_pull_swaps", "tl_gsa_masses", "tl_gsa_selftest_pull",
+    "tl_kohonen_som", "tl_kohonen_som_trace", "tl_kohonen_som_population", "tl_kohonen_som_max_n", "tl_kohonen_som_plan",
+    "tl_som_draw", "tl_som_schedule", "tl_som_h", "tl_som_ring_init", "tl_som_selftest_bmu",
 ]
 
 
@@ -112,6 +114,13 @@ class TlFpaOpts(C.Structure):
 class TlGsaOpts(C.Structure):
     """tl_gsa_opts: what gravitational_search reads of HeuristicOptions (src/tsp/mod.rs:596-611), and the epochs of one launch (0: the default)"""
     _fields_ = [("epochs", C.c_uint32), ("n_nearest", C.c_uint32), ("span_epochs", C.c_uint32)]
+
+
+class TlSomOpts(C.Structure):
+    """tl_som_opts: SOMOptions (src/tsp/mod.rs:1465-1499), the form of the ring (0: the plan decides, 1: LDS, 2: workspace) and the
+    workspace one launch sequence plans with (0: the default)"""
+    _fields_ = [("epochs", C.c_uint32), ("neuron_multiplier", C.c_uint32), ("learning_rate", C.c_double), ("radius_fraction", C.c_double),
+                ("form", C.c_uint32), ("reserved", C.c_uint32), ("work_bytes", C.c_uint64)]
 
 
 # tl_lk_progress_fn: void (*)(void *user, const uint32_t *best_pos, uint32_t n, float best_dist)
@@ -307,5 +316,19 @@ def load():
     L.tl_gsa_masses.argtypes = [vp, u32, vp, vp]
     L.tl_gravitational_search_plan.argtypes = [u32, u32, u32, i32, i32, u64, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
     L.tl_gsa_selftest_pull.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
+    f64p = C.POINTER(C.c_double)
+    L.tl_kohonen_som_max_n.argtypes = [vp, u32, u32]
+    L.tl_kohonen_som_max_n.restype = u32
+    L.tl_kohonen_som.argtypes = [vp, vp, u32, vp, C.POINTER(TlSomOpts), u64, vp, f32p, C.POINTER(TlStats)]
+    L.tl_kohonen_som_trace.argtypes = [vp, vp, u32, vp, C.POINTER(TlSomOpts), u64, u32, vp, f32p, C.POINTER(TlStats), vp, u32, vp, vp, vp, vp, u32,
+                                       C.POINTER(u32)]
+    L.tl_kohonen_som_population.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(TlSomOpts), u64, vp, vp, C.POINTER(u32), C.POINTER(TlStats)]
+    L.tl_som_draw.argtypes = [u64, u32, u32, u32]
+    L.tl_som_draw.restype = u32
+    L.tl_som_schedule.argtypes = [u32, u32, u32, C.c_double, C.c_double, f64p, f64p, f64p, C.POINTER(u32)]
+    L.tl_som_h.argtypes = [C.c_double, C.c_double, f64p]
+    L.tl_som_ring_init.argtypes = [vp, u32, u32, vp, vp]
+    L.tl_kohonen_som_plan.argtypes = [u32, u32, u32, u32, i32, i32, u64, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32), C.POINTER(u32)]
+    L.tl_som_selftest_bmu.argtypes = [vp, vp, u32, vp, u32, i32, u32, vp, vp, vp]
     _lib = L
     return L

@@ -565,6 +565,35 @@ hipError_t launch_gsa_epochs(const GsaArgs &A, uint32_t runs, hipStream_t s);  /
 hipError_t launch_gsa_selftest_pull(const uint16_t *from, const uint16_t *to, const uint32_t *want, uint32_t n, uint32_t count, uint32_t *out_pairs,
                                     uint32_t *out_len, hipStream_t s);
 
+// kohonen_som.hip — the Kohonen self-organising map solver, the run a grid dimension, a span of epochs per launch
+struct SomEpoch;  // som_spec.h
+struct SomArgs {
+    const double *cities;   // the normalised cities: x[n] | y[n]
+    const double *ring0;    // the start ring x[M] | y[M], the same for every run
+    double *ring;           // [runs][2 M] a run's ring, x[M] | y[M]: loaded at a span's start, stored at its end
+    const SomEpoch *sched;  // [epochs] the schedule, epoch t at t - 1
+    uint32_t *log;          // optional: [log_cap][2] (city, bmu) of epoch t at row t - 1, run 0 of the launch
+    const float2 *xy;       // the extraction's cost: n cities (coordinate form)
+    const float *dm_full;   // or the matrix expanded to row-major n x n
+    uint32_t *bmu;          // [runs][n] the extraction's first-minimum neuron of every city
+    double *bdist;          // [runs][n] and its distance
+    float *edge;            // [runs][n] the tour's edge lengths
+    uint32_t *out_pos;      // [runs][n] the extracted tour
+    float *out_cost;        // [runs] its cost
+    uint64_t seed;
+    uint32_t log_cap;
+    uint32_t first_run;     // stream id of the launch's run 0
+    uint32_t n, M;
+    uint32_t t0, t1;        // the span [t0, t1) of the epochs 1 .. epochs
+    uint32_t fresh;         // the span begins the run: the ring is ring0
+};
+constexpr size_t kSomLdsFixedBytes = 512;  // the reduction's double-buffered slots of up to 16 waves
+inline size_t kohonen_som_lds_bytes(uint32_t M, bool lds_form) { return kSomLdsFixedBytes + (lds_form ? 16 * (size_t)M : 0); }
+int kohonen_som_threads(uint32_t M);
+hipError_t launch_som_train(const SomArgs &A, uint32_t runs, bool lds_form, hipStream_t s);  // the epochs [t0, t1): one workgroup per run
+hipError_t launch_som_extract(const SomArgs &A, uint32_t runs, hipStream_t s);               // every run's tour and cost from its ring
+hipError_t launch_som_selftest_bmu(const SomArgs &A, int threads, bool lds_form, hipStream_t s);  // the training's BMU of cities 0 .. n - 1 into A.bmu, on A.ring as it is
+
 // lk.hip
 struct LkState {          // device-side state machine of the multi-CU LK variant
     uint32_t key;            // min pair index with a valid chain in the current scan (0xFFFFFFFF: none)

@@ -1419,8 +1419,62 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOp
 }
 }  // namespace gravitational_search
 
+namespace kohonen_som {  // som.rs:12-186
+struct SOMOptions {  // mod.rs:1465-1482
+    size_t epochs = 100000;
+    double learning_rate = 0.8;
+    double radius_fraction = 0.1;
+    size_t neuron_multiplier = 8;
+};
+// The algorithm is the reference's; the city drawn in an epoch, exp (with a cut at -8 before it) and the start ring's cos and sin are
+// this project's specification (include/teeline_gpu.h).  init_tour is ignored, as the reference ignores it.  runs > 1: runs
+// 0 .. runs-1 of the seed at once, the best one returned (lowest cost, then lowest run).  With a progress callback the reference's
+// messages — EpochUpdate(t) then PathUpdate(snapshot) at every t % max(epochs / 10, 1) == 0, a final PathUpdate only where
+// epochs % checkpoint != 0, then Done (som.rs:117-145; nothing for n < 2) — are replayed from that run's checkpoint records.
+inline Solution solve(Context &ctx, const TspProblem &problem, const SOMOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
+                      uint64_t seed = 1, uint32_t runs = 1)
+{
+    (void)init_tour;
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size();
+    const tl_som_opts o{(uint32_t)std::min<size_t>(opts.epochs, 0xFFFFFFFFu), (uint32_t)std::min<size_t>(opts.neuron_multiplier, 0xFFFFFFFFu), opts.learning_rate,
+                        opts.radius_fraction, 0u, 0u, 0ull};
+    std::vector<uint32_t> out(n);
+    float cost = 0.f;
+    tl_stats st{};
+    uint32_t run = 0;
+    if (runs > 1) {
+        std::vector<uint32_t> outs((size_t)runs * n);
+        std::vector<float> costs(runs);
+        ctx.check(tl_kohonen_som_population(ctx.get(), xy.data(), n, problem.explicit_packed(), 0u, runs, &o, seed, outs.data(), costs.data(), &run, &st));
+        std::copy(outs.begin() + (size_t)run * n, outs.begin() + (size_t)(run + 1) * n, out.begin());
+        cost = costs[run];
+        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
+    } else if (!(progress_tx && *progress_tx)) {
+        ctx.check(tl_kohonen_som(ctx.get(), xy.data(), n, problem.explicit_packed(), &o, seed, out.data(), &cost, &st));
+        return detail::finish(problem, out, cost, st, nullptr);
+    }
+    const uint32_t cap = 20;
+    uint32_t rows = 0;
+    std::vector<uint32_t> ep(cap), tours((size_t)cap * std::max(n, 1u)), cb(cap);
+    ctx.check(tl_kohonen_som_trace(ctx.get(), xy.data(), n, problem.explicit_packed(), &o, seed, run, out.data(), &cost, &st, nullptr, 0u, nullptr, ep.data(),
+                                   tours.data(), cb.data(), cap, &rows));
+    std::vector<size_t> route(n);
+    for (uint32_t k = 0; k < rows && k < cap; ++k) {
+        if (ep[k] != 0xFFFFFFFFu) (*progress_tx)(ProgressKind::EpochUpdate, std::vector<size_t>{ep[k]}, 0.0f);
+        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[tours[(size_t)k * n + q]].id;
+        float d;
+        std::memcpy(&d, &cb[k], 4);
+        (*progress_tx)(ProgressKind::PathUpdate, route, d);
+    }
+    Solution s = detail::finish(problem, out, cost, st, nullptr);
+    if (n >= 2) (*progress_tx)(ProgressKind::Done, s.route_, cost);
+    return s;
+}
+}  // namespace kohonen_som
+
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
-enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch, FlowerPollination, GravitationalSearch };
+enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch, FlowerPollination, GravitationalSearch, KohonenSom };
 
 inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
 {
@@ -1444,11 +1498,12 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
     else if (s == "cuckoo_search") out = Solvers::CuckooSearch;  // (the alias `cs` likewise)
     else if (s == "flower_pollination") out = Solvers::FlowerPollination;  // (the alias `fpa` likewise)
     else if (s == "gravitational_search") out = Solvers::GravitationalSearch;  // (the alias `gsa` likewise)
+    else if (s == "kohonen_som") out = Solvers::KohonenSom;  // (the aliases `som` and `kohonen` likewise)
     else {
         static const char *cpu_only[] = {"aco", "branch_bound",
                                          "cs", "fpa", "fourier", "ga", "gsa",
                                          "pso", "sa",
-                                         "som", "kohonen", "kohonen_som", "stochastic_hill", "tabu"};
+                                         "som", "kohonen", "stochastic_hill", "tabu"};
         for (const char *c : cpu_only)
             if (s == c) {
                 why = "solver `" + s + "` is not accelerated by this build (nn, gec, sav, chr, bhk, 2opt, 3opt, or_opt, lk, shuffle are, and simulated_annealing under its long name)";
@@ -1459,6 +1514,7 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
                 if (s == "cs") why += "; the seeded cuckoo search of this build is `cuckoo_search`";
                 if (s == "fpa") why += "; the seeded flower pollination of this build is `flower_pollination`";
                 if (s == "gsa") why += "; the seeded gravitational search of this build is `gravitational_search`";
+                if (s == "som" || s == "kohonen") why += "; the seeded Kohonen map of this build is `kohonen_som`";
                 return false;
             }
         why = "unknown solver";  // FromStr's Err (mod.rs:588)
@@ -1487,6 +1543,7 @@ inline const char *solver_name(Solvers s)
         case Solvers::CuckooSearch: return "cuckoo_search";
         case Solvers::FlowerPollination: return "flower_pollination";
         case Solvers::GravitationalSearch: return "gravitational_search";
+        case Solvers::KohonenSom: return "kohonen_som";
         default: return "shuffle";
     }
 }
@@ -1509,6 +1566,8 @@ struct StageOptions {
     float fpa_mutation_probability = 0.001f;  // FPAOptions::mutation_probability (mod.rs:1007)
     uint32_t fpa_runs = 1;  // a flower_pollination stage runs this many runs and keeps the best
     uint32_t gsa_runs = 1;  // a gravitational_search stage runs this many runs and keeps the best
+    kohonen_som::SOMOptions som;
+    uint32_t som_runs = 1;  // a kohonen_som stage runs this many runs and keeps the best
     uint64_t seed = 1;  // LK kicks, shuffle, SA, tabu and GA draws
     const ProgressFn *progress = nullptr;  // handed to every stage's solve() (the reference's CLI passes None; teeline-qt a sender)
 };
@@ -1578,6 +1637,7 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             case Solvers::CuckooSearch: sol = cuckoo_search::solve(ctx, problem, cuckoo_search::CSOptions{o.heuristic, o.cs_mutation_probability}, o.progress, init, o.seed, o.cs_runs); break;
             case Solvers::FlowerPollination: sol = flower_pollination::solve(ctx, problem, flower_pollination::FPAOptions{o.heuristic, o.fpa_mutation_probability}, o.progress, init, o.seed, o.fpa_runs); break;
             case Solvers::GravitationalSearch: sol = gravitational_search::solve(ctx, problem, o.heuristic, o.progress, init, o.seed, o.gsa_runs); break;
+            case Solvers::KohonenSom: sol = kohonen_som::solve(ctx, problem, o.som, o.progress, init, o.seed, o.som_runs); break;
         }
         const auto t1 = std::chrono::steady_clock::now();
         const uint64_t ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();

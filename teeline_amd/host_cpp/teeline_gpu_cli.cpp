@@ -30,6 +30,10 @@
 //     gravity  : gravitational_search (long name only: `gsa` stays refused) runs --epochs epochs (default 10000) of seeded draws (--seed)
 //               with max(--n-nearest, 25) agents; --runs K (K runs of the seed at once, the best kept); `solve gravitational_search`
 //               alone is pipeline(shuffle, gravitational_search) (mod.rs:2157)
+//     kohonen  : kohonen_som (long name only: `som` and `kohonen` stay refused) trains --epochs epochs (default 100000) of seeded draws
+//               (--seed) with --learning_rate (0.8), --radius_fraction (0.1) and --neuron_multiplier (8): SOMOptions, mod.rs:1465-1499;
+//               --runs K (K runs of the seed at once, the best kept); `solve kohonen_som` runs alone: the map is constructive and
+//               ignores a start tour (it is in neither of mod.rs:129-157's lists)
 //     solve   : 2opt / 3opt / or_opt / lk auto-expand to pipeline(nn, solver) unless --no-seed (main.rs:387-397, mod.rs:129-139);
 //               gec (greedy_edge), sav (savings) and chr (christofides) are constructions and run alone; so does bhk (bellman_karp),
 //               the exact solver (n <= 26, mod.rs:2137) — as a later pipeline stage it ignores its seed
@@ -67,7 +71,7 @@ struct Args {
 {
     if (why) std::fprintf(stderr, "error: %s\n", why);
     std::fprintf(stderr,
-                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|genetic_algorithm|ant_colony|particle_swarm|cuckoo_search|flower_pollination|gravitational_search|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
+                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|genetic_algorithm|ant_colony|particle_swarm|cuckoo_search|flower_pollination|gravitational_search|kohonen_som|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
                  "                         [--optimal-tour FILE] [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P]\n"
                  "                         [--n_nearest K] [--max-depth D] [--seed S] [--best-sweep] [--device N] [--stats]\n"
                  "                         [--progress-digest] [--exact-walk]\n"
@@ -126,7 +130,7 @@ Args parse(int argc, char **argv)
         else if (s == "--output-format") a.output_format = val();
         else if (s == "--optimal-tour") a.optimal_tour = val();
         else if (s == "--distance-type") a.distance_type = val();
-        else if (s == "--epochs") a.opt.heuristic.epochs = a.opt.lk.heuristic.epochs = a.opt.sa.heuristic.epochs = a.opt.ga.heuristic.epochs = a.opt.aco.heuristic.epochs = parse_usize(s, val());
+        else if (s == "--epochs") a.opt.heuristic.epochs = a.opt.lk.heuristic.epochs = a.opt.sa.heuristic.epochs = a.opt.ga.heuristic.epochs = a.opt.aco.heuristic.epochs = a.opt.som.epochs = parse_usize(s, val());
         else if (s == "--cooling-rate" || s == "--cooling_rate") a.opt.sa.cooling_rate = std::stof(val());
         else if (s == "--min-temperature" || s == "--min_temperature") a.opt.sa.min_temperature = std::stof(val());
         else if (s == "--max-temperature" || s == "--max_temperature") a.opt.sa.max_temperature = std::stof(val());
@@ -138,7 +142,7 @@ Args parse(int argc, char **argv)
         else if (s == "--beta") a.opt.aco.beta = std::stof(val());
         else if (s == "--evaporation-rate" || s == "--evaporation_rate") a.opt.aco.evaporation_rate = std::stof(val());
         else if (s == "--num-ants" || s == "--num_ants") a.opt.aco.num_ants = parse_usize(s, val());
-        else if (s == "--runs") a.opt.aco_runs = a.opt.pso_runs = a.opt.cs_runs = a.opt.fpa_runs = a.opt.gsa_runs = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
+        else if (s == "--runs") a.opt.aco_runs = a.opt.pso_runs = a.opt.cs_runs = a.opt.fpa_runs = a.opt.gsa_runs = a.opt.som_runs = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--chains") a.opt.sa_chains = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--platoo_epochs" || s == "--platoo-epochs") a.opt.heuristic.platoo_epochs = a.opt.lk.heuristic.platoo_epochs = parse_usize(s, val());
         else if (s == "--n_nearest" || s == "--n-nearest") a.opt.heuristic.n_nearest = a.opt.lk.heuristic.n_nearest = parse_usize(s, val());
@@ -150,6 +154,9 @@ Args parse(int argc, char **argv)
         else if (s == "--device") a.device = std::stoi(val());
         else if (s == "--stats") a.stats = true;
         else if (s == "--short") a.short_list = true;
+        else if (s == "--learning_rate" || s == "--learning-rate") a.opt.som.learning_rate = std::stod(val());
+        else if (s == "--radius_fraction" || s == "--radius-fraction") a.opt.som.radius_fraction = std::stod(val());
+        else if (s == "--neuron_multiplier" || s == "--neuron-multiplier") a.opt.som.neuron_multiplier = parse_usize(s, val());
         else if (s == "--progress-digest") a.progress_digest = true;
         else if (s == "--timing") a.timing = true;
         else if (s == "--full-exit") a.full_exit = true;
