@@ -1077,6 +1077,61 @@ int tl_kohonen_som_plan(uint32_t n, uint32_t neuron_multiplier, uint32_t form, u
 int tl_som_selftest_bmu(tl_ctx *ctx, const double *ring, uint32_t neurons, const double *cities, uint32_t n, int threads, uint32_t form, uint32_t *out_bmu,
                         uint32_t *out_extract_bmu, uint32_t *out_tour);
 
+/* ---- stochastic hill climb: replaces stochastic_hill::solve (stochastic_hill.rs:7-97) ------------------ */
+/* The reference's chain, quirks kept: best = current = the start tour (init_pos, NULL: city order — the reference's own shuffle is
+ * the caller's); every epoch draws one candidate of the CURRENT tour (positions from..=to of the open path reversed, the pair by
+ * random_position_pair) and prices it with the full tour_length re-sum; the candidate is accepted iff its cost is below the BEST
+ * cost (not the current tour's): then current = best = candidate and n_stale = 0, else n_stale += 1.  After the epoch counter's
+ * increment, if platoo_epochs > 0 and n_stale > platoo_epochs the current tour is shuffled in place and n_stale = 0; the best stays
+ * (after a restart a candidate of the random tour must still beat the best cost, so restarts rarely help: the reference's
+ * behaviour).  The restart check precedes the end check, so a restart can fall on the last epoch.  epochs + 1 epochs run; the BEST
+ * route is returned, *out_cost the bits of the best cost.
+ * THE RANDOM STREAM IS THIS PROJECT'S SPECIFICATION, NOT THE REFERENCE'S (tests/_hill_oracle.py is the
+ * statement, csrc/hill_spec.h the text): the reference draws from an unseeded thread RNG.  With
+ *   u(seed, chain, event, slot) = mix(mix(seed + G (chain + 1)) + G (32 event + slot + 1))      (tl_hill_draw)
+ * the pair of epoch e is tl_sim_anneal's (event e, slots 0 .. 21), and the restart after epoch e (the index before the increment)
+ * is the Fisher-Yates pass j = n - 1 .. 1, swap(a[j], a[position(u, j + 1)]), u on slot 26 of the event 2^58 + e n + j.  No draw
+ * depends on an earlier one, so `window` consecutive epochs are evaluated at once (csrc/hill_climb.hip: one workgroup per chain,
+ * the tour in that CU's LDS); opts->window = 1 is the chain epoch after epoch, and every window gives the same result.
+ * opts NULL: the defaults (10 000 epochs, platoo_epochs 500, the plan's window).  epochs = 0 (the reference never ends) and
+ * epochs = 2^32 - 1: TL_ERR_UNSUPPORTED.  reserved != 0, window above the threads of the plan: TL_ERR_BADARG.  n < 2:
+ * TL_ERR_REF_PANICS (route.rs:87-89); n = 2 and n = 3 run (the 11th pair is taken whatever it is).  n > tl_hill_climb_lds_max_n:
+ * TL_ERR_UNSUPPORTED, before anything of size n is read or allocated (no HBM form).  init_pos not a permutation: TL_ERR_BADARG.  A
+ * context whose flags hold a bit no flag has: TL_ERR_UNSUPPORTED.  dm_packed as in tl_sim_anneal.
+ * tl_hill_climb runs chain 0.  stats (optional): sweeps = candidates = epochs run, moves = acceptances, reversed = elements moved,
+ * summed over the chains of a population.
+ * tl_hill_climb_trace: the same plus every event in order, 4 words each: an acceptance is (epoch, from, to, the bits of the new
+ * best cost), a restart (epoch, 0xFFFFFFFF, 0, 0), epoch the index before the increment — what the reference's messages are
+ * replayed from: PathUpdate(start, 0.0), PathUpdate(best, best cost) per acceptance, PathUpdate(shuffled current, 0.0) per restart,
+ * Done.  *log_len counts all events; the log holds the first log_cap.  tl_hill_climb_trace_chain: the same for chain `chain`.
+ * tl_hill_climb_population: chains first_chain .. first_chain + count - 1, each its own stream of draws, concurrently (more chains
+ * than the LDS holds at once — tl_hill_climb_plan's per_launch — run in further launches).  init_count, out_pos, out_costs,
+ * out_moves (acceptances), *best_index and its tie rule, count == 0: as tl_tabu_search_population.  Chain c of any population
+ * equals first_chain = c, count = 1.
+ * Host-only queries (no context, no device): tl_hill_draw — the u64 above; tl_hill_climb_plan — the window (window_request, or
+ * where that is 0 the threads), the threads of a chain's workgroup (256 for a chain alone on its CU, 64 once there are more chains
+ * than CUs) and the chains one launch holds (outputs optional; all 0 where n is outside 2 .. the limit; window_request above the
+ * threads: TL_ERR_BADARG, as cus < 1 or lds_bytes < 0). */
+typedef struct tl_hill_opts { /* HeuristicOptions, src/tsp/mod.rs:598-608 */
+    uint32_t epochs;
+    uint32_t platoo_epochs;
+    uint32_t window;   /* not the reference's: 0 the plan's; 1 the chain epoch after epoch; up to the plan's threads.  Same result */
+    uint32_t reserved; /* 0 */
+} tl_hill_opts;
+uint32_t tl_hill_climb_lds_max_n(const tl_ctx *ctx);
+int tl_hill_climb(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_hill_opts *opts, uint64_t seed,
+                  uint32_t *out_pos, float *out_cost, tl_stats *stats);
+int tl_hill_climb_trace(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_hill_opts *opts, uint64_t seed,
+                        uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *log, uint32_t log_cap, uint32_t *log_len);
+int tl_hill_climb_trace_chain(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_hill_opts *opts,
+                              uint64_t seed, uint32_t chain, uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *log, uint32_t log_cap,
+                              uint32_t *log_len);
+int tl_hill_climb_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
+                             uint32_t first_chain, uint32_t count, const tl_hill_opts *opts, uint64_t seed, uint32_t *out_pos, float *out_costs,
+                             uint32_t *out_moves, uint32_t *best_index, tl_stats *stats);
+uint64_t tl_hill_draw(uint64_t seed, uint32_t chain, uint64_t event, uint32_t slot);
+int tl_hill_climb_plan(uint32_t n, uint32_t count, int cus, int lds_bytes, uint32_t window_request, uint32_t *window, int *threads, uint32_t *per_launch);
+
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts
  * first..first+count as above; seed ignored otherwise).  d_out_pos: count x n u32, d_out_cost: count f32,

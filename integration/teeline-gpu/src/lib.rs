@@ -89,6 +89,23 @@ pub struct SomOpts {
     pub work_bytes: u64,
 }
 
+/// `tl_hill_opts`: HeuristicOptions' epochs and platoo_epochs (src/tsp/mod.rs:598-608) and the window (0: the plan's, 1: the chain
+/// epoch after epoch).  The result does not depend on the window.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct HillOpts {
+    pub epochs: u32,
+    pub platoo_epochs: u32,
+    pub window: u32,
+    pub reserved: u32,
+}
+
+impl Default for HillOpts {
+    fn default() -> Self {
+        HillOpts { epochs: 10_000, platoo_epochs: 500, window: 0, reserved: 0 }
+    }
+}
+
 /// `tl_gsa_opts`: what gravitational_search reads of HeuristicOptions (src/tsp/mod.rs:596-611); N = max(n_nearest, 25)
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -251,6 +268,16 @@ unsafe extern "C" {
                        radius: *mut u32) -> i32;
     fn tl_som_h(d: f64, two_sigma_sq: f64, h: *mut f64) -> i32;
     fn tl_som_ring_init(xy: *const f32, n: u32, neuron_multiplier: u32, out_ring: *mut f64, out_cities: *mut f64) -> i32;
+    fn tl_hill_climb_lds_max_n(ctx: *const TlCtx) -> u32;
+    fn tl_hill_climb(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, opts: *const HillOpts, seed: u64,
+                     out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats) -> i32;
+    fn tl_hill_climb_trace_chain(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, opts: *const HillOpts, seed: u64,
+                                 chain: u32, out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats, log: *mut u32, log_cap: u32,
+                                 log_len: *mut u32) -> i32;
+    fn tl_hill_climb_population(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, init_count: u32,
+                                first_chain: u32, count: u32, opts: *const HillOpts, seed: u64, out_pos: *mut u32, out_costs: *mut f32,
+                                out_moves: *mut u32, best_index: *mut u32, stats: *mut Stats) -> i32;
+    fn tl_hill_draw(seed: u64, chain: u32, event: u64, slot: u32) -> u64;
     fn tl_nearest_neighbor(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, n_nearest: u32,
                            out_pos: *mut u32, out_cost: *mut f32) -> c_int;
     fn tl_greedy_edge(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
@@ -293,6 +320,13 @@ pub fn sa_draw(seed: u64, chain: u32, epoch: u32, slot: u32) -> u64 {
 pub fn tabu_draw(seed: u64, chain: u32, n: u32, epoch: u32, attempt: u32, slot: u32) -> u64 {
     // SAFETY: a pure function of its arguments.
     unsafe { tl_tabu_draw(seed, chain, n, epoch, attempt, slot) }
+}
+
+/// u(seed, chain, event, slot): a draw of the hill climb's stream (host only): the pair of epoch e on event e, slots 0 .. 21; the restart
+/// after epoch e on the events 2^58 + e n + j, slot 26.
+pub fn hill_draw(seed: u64, chain: u32, event: u64, slot: u32) -> u64 {
+    // SAFETY: a pure function of its arguments.
+    unsafe { tl_hill_draw(seed, chain, event, slot) }
 }
 
 /// u(seed, run, event, slot): a draw of the genetic algorithm's stream (host only; the events are laid out in include/teeline_gpu.h).
@@ -829,6 +863,67 @@ impl Context {
     pub fn kohonen_som_max_n(&self, neuron_multiplier: u32, form: u32) -> u32 {
         // SAFETY: a live context.
         unsafe { tl_kohonen_som_max_n(self.raw, neuron_multiplier, form) }
+    }
+
+    /// `stochastic_hill::solve` (stochastic_hill.rs:7-97), chain 0 of `seed`: `epochs + 1` epochs, the best route.  The chain is the
+    /// reference's (a candidate must beat the best cost; a plateau shuffles the current tour only); its random draws are the library's
+    /// own specification (include/teeline_gpu.h).  `init_pos` None: city order.  (Written against the header; not compiled here: no
+    /// Rust toolchain on the build machine, see scripts/check_rust.sh.)
+    pub fn hill_climb(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, opts: &HillOpts, seed: u64) -> Result<Tour, Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        // SAFETY: as in two_opt.
+        let rc = unsafe { tl_hill_climb(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), opts, seed, t.pos.as_mut_ptr(), &mut t.cost, &mut t.stats) };
+        self.check(rc).map(|_| t)
+    }
+
+    /// Chain `chain` of `seed` with its events in order: an acceptance `[epoch, from, to, cost bits]`, a restart `[epoch, 0xFFFFFFFF, 0, 0]`,
+    /// from which the reference's PathUpdate messages are replayed (the shuffles through `hill_draw`).
+    pub fn hill_climb_trace(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, opts: &HillOpts, seed: u64, chain: u32)
+                            -> Result<(Tour, Vec<[u32; 4]>), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let mut t = Tour { pos: vec![0u32; n as usize], cost: 0.0, stats: Stats::default() };
+        let cap: u32 = opts.epochs.saturating_add(1);  // at most one event an epoch
+        let mut log = vec![[0u32; 4]; cap as usize];
+        let mut len: u32 = 0;
+        // SAFETY: as in two_opt; log holds cap entries of 4 words.
+        let rc = unsafe {
+            tl_hill_climb_trace_chain(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), opts, seed, chain, t.pos.as_mut_ptr(), &mut t.cost,
+                                      &mut t.stats, log.as_mut_ptr() as *mut u32, cap, &mut len)
+        };
+        self.check(rc)?;
+        log.truncate(len.min(cap) as usize);
+        Ok((t, log))
+    }
+
+    /// Chains `first_chain .. first_chain + count` of `seed` at once, every chain from `init_pos` (or city order); the best routes and
+    /// the index of the best one (lowest cost, then lowest chain).
+    pub fn hill_climb_population(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, first_chain: u32, count: u32, opts: &HillOpts,
+                                 seed: u64) -> Result<(Vec<Tour>, u32), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, init_pos);
+        let mut pos = vec![0u32; n as usize * count as usize];
+        let mut costs = vec![0f32; count as usize];
+        let mut moves = vec![0u32; count as usize];
+        let (mut best, mut st) = (0u32, Stats::default());
+        // SAFETY: as in two_opt; the output arrays hold count x n, count and count entries.
+        let rc = unsafe {
+            tl_hill_climb_population(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), opt_ptr(init_pos), if init_pos.is_some() { 1 } else { 0 }, first_chain,
+                                     count, opts, seed, pos.as_mut_ptr(), costs.as_mut_ptr(), moves.as_mut_ptr(), &mut best, &mut st)
+        };
+        self.check(rc)?;
+        let tours = (0..count as usize)
+            .map(|k| Tour { pos: pos[k * n as usize..(k + 1) * n as usize].to_vec(), cost: costs[k], stats: Stats { moves: moves[k] as u64, ..st } })
+            .collect();
+        Ok((tours, best))
+    }
+
+    /// Largest n of `hill_climb` (the current tour lives in one CU's LDS, 12 bytes per city).
+    pub fn hill_climb_lds_max_n(&self) -> u32 {
+        // SAFETY: a plain query of a live context.
+        unsafe { tl_hill_climb_lds_max_n(self.raw) }
     }
 
     /// Largest n of `gravitational_search` (a workgroup keeps 8 n bytes in LDS).

@@ -75,6 +75,8 @@ SYMBOLS = [
     "tl_gravitational_search_plan", "tl_gsa_draw", "tl_gsa_g", "tl_gsa_pull_swaps", "tl_gsa_masses", "tl_gsa_selftest_pull",
     "tl_kohonen_som", "tl_kohonen_som_trace", "tl_kohonen_som_population", "tl_kohonen_som_max_n", "tl_kohonen_som_plan",
     "tl_som_draw", "tl_som_schedule", "tl_som_h", "tl_som_ring_init", "tl_som_selftest_bmu",
+    "tl_hill_climb", "tl_hill_climb_trace", "tl_hill_climb_trace_chain", "tl_hill_climb_population", "tl_hill_climb_lds_max_n", "tl_hill_climb_plan",
+    "tl_hill_draw",
 ]
 
 
@@ -114,6 +116,12 @@ class TlFpaOpts(C.Structure):
 class TlGsaOpts(C.Structure):
     """tl_gsa_opts: what gravitational_search reads of HeuristicOptions (src/tsp/mod.rs:596-611), and the epochs of one launch (0: the default)"""
     _fields_ = [("epochs", C.c_uint32), ("n_nearest", C.c_uint32), ("span_epochs", C.c_uint32)]
+
+
+class TlHillOpts(C.Structure):
+    """tl_hill_opts: HeuristicOptions' epochs and platoo_epochs (src/tsp/mod.rs:598-608) and the window (0: the plan's, 1: the chain epoch
+    after epoch)"""
+    _fields_ = [("epochs", C.c_uint32), ("platoo_epochs", C.c_uint32), ("window", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class TlSomOpts(C.Structure):
@@ -330,5 +338,14 @@ def load():
     L.tl_som_ring_init.argtypes = [vp, u32, u32, vp, vp]
     L.tl_kohonen_som_plan.argtypes = [u32, u32, u32, u32, i32, i32, u64, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32), C.POINTER(u32)]
     L.tl_som_selftest_bmu.argtypes = [vp, vp, u32, vp, u32, i32, u32, vp, vp, vp]
+    L.tl_hill_climb_lds_max_n.argtypes = [vp]
+    L.tl_hill_climb_lds_max_n.restype = u32
+    L.tl_hill_climb.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlHillOpts), u64, vp, f32p, C.POINTER(TlStats)]
+    L.tl_hill_climb_trace.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlHillOpts), u64, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32)]
+    L.tl_hill_climb_trace_chain.argtypes = [vp, vp, u32, vp, vp, C.POINTER(TlHillOpts), u64, u32, vp, f32p, C.POINTER(TlStats), vp, u32, C.POINTER(u32)]
+    L.tl_hill_climb_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, C.POINTER(TlHillOpts), u64, vp, vp, vp, C.POINTER(u32), C.POINTER(TlStats)]
+    L.tl_hill_draw.argtypes = [u64, u32, u64, u32]
+    L.tl_hill_draw.restype = u64
+    L.tl_hill_climb_plan.argtypes = [u32, u32, i32, i32, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
     _lib = L
     return L

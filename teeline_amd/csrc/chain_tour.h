@@ -1,10 +1,10 @@
 // chain_tour.h — what the kernels of the seeded solvers share on the device (internal to libteeline_gpu): the distance between two
-// cities (sim_anneal.hip, tabu_search.hip, genetic.hip) and the minimum over a wave (sim_anneal.hip, tabu_search.hip).
+// cities (sim_anneal.hip, tabu_search.hip, hill_climb.hip, genetic.hip) and the minimum over a wave (the first three of them).
 //
-// The resident tour itself — perm | E | S, the costing walk of a reversal and its commit — is NOT in here: sim_anneal.hip and
-// tabu_search.hip each keep their copy.  Folding the two into always-inlined helpers gave kernels with the parent's registers and
-// LDS but 2–4 % more kernel time on the same box, in both forms that were measured (NOTEBOOK.md, the entry of this header), so the
-// two copies have to be changed in step until a form is found that compiles to the code they have now.
+// The resident tour itself — perm | E | S, the costing walk of a reversal and its commit — is NOT in here: sim_anneal.hip,
+// tabu_search.hip and hill_climb.hip each keep their copy.  Folding two into always-inlined helpers gave kernels with the parent's
+// registers and LDS but 2–4 % more kernel time on the same box, in both forms that were measured (NOTEBOOK.md, the entry of this
+// header), so the three copies have to be changed in step until a form is found that compiles to the code they have now.
 #pragma once
 #include "tl_kernels.h"
 

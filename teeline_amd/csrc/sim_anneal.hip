@@ -78,7 +78,7 @@ __global__ __launch_bounds__(1024) void k_sim_anneal(SaArgs A)
                 tot = S[start];
             }
         }
-        // (this costing and the commit below stand in tabu_search.hip too, character for character: change both — chain_tour.h says why)
+        // (this costing and the commit below stand in tabu_search.hip and hill_climb.hip too, character for character: change all three — chain_tour.h says why)
         // the wave's lanes walk k together from the lowest start among them
         const uint32_t k0 = wave_min_u32(start);
         const uint32_t rsum = from + to - 1u;

@@ -356,6 +356,29 @@ size_t tabu_search_lds_bytes(uint32_t n);    // LDS of one chain's workgroup (ei
 uint32_t tabu_search_lds_max_n(int lds_budget);
 hipError_t launch_tabu_search(const TabuArgs &A, uint32_t count, int threads, hipStream_t s);
 
+// hill_climb.hip — the stochastic hill climb, one workgroup per chain
+struct HillArgs {
+    const float2 *xy;       // n cities, city order (coordinate form)
+    const float *dm_full;   // the matrix expanded to row-major n x n, or nullptr
+    const uint32_t *init;   // chain b of the launch starts from init + b * init_stride (0: every chain from the same tour)
+    uint32_t *out_pos;      // [count][n] the chains' best routes
+    float *out_cost;        // [count] their tour_length
+    uint32_t *out_run;      // [count][4] acceptances, elements moved (64 bits), restarts
+    uint32_t *log;          // optional: [log_cap][4] the events of the launch's chain 0 in order: epoch, from, to, cost bits of an
+                            // acceptance; epoch, 0xFFFFFFFF, 0, 0 of a restart
+    uint64_t seed;
+    uint32_t log_cap;
+    uint32_t first_chain;   // stream id of the launch's chain 0
+    uint32_t n;
+    uint32_t init_stride;
+    uint32_t epochs;        // the epochs to run (the reference's `epochs` + 1)
+    uint32_t platoo;        // platoo_epochs (0: never a restart)
+    uint32_t window;        // epochs evaluated at once (1 .. threads)
+};
+size_t hill_climb_lds_bytes(uint32_t n);     // LDS of one chain's workgroup (either form)
+uint32_t hill_climb_lds_max_n(int lds_budget);
+hipError_t launch_hill_climb(const HillArgs &A, uint32_t count, int threads, hipStream_t s);
+
 // genetic.hip — the genetic algorithm, the run a grid dimension, two launches per generation
 struct GaArgs {
     const float2 *xy;       // n cities, city order (coordinate form)

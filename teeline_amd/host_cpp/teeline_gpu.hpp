@@ -1473,8 +1473,78 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const SOMOptions 
 }
 }  // namespace kohonen_som
 
+namespace hill_climb {  // stochastic_hill.rs:7-97
+// The chain is the reference's (a candidate is accepted iff it beats the BEST cost; a plateau shuffles the current tour and leaves the
+// best alone; epochs + 1 epochs run); its random draws (a pure function of seed, chain, event and slot) are this project's
+// specification (include/teeline_gpu.h), and the solver goes by the name `hill_climb`.  init_tour nullptr: city order (the
+// reference's own shuffle is the pipeline's shuffle stage).  chains > 1: chains 0 .. chains-1 of the seed at once, the best one
+// returned (lowest cost, then lowest chain).  With a progress callback the reference's messages — PathUpdate(start route, 0.0),
+// PathUpdate(best, distance) per acceptance, PathUpdate(shuffled current route, 0.0) per restart, then Done
+// (stochastic_hill.rs:29-31,51-56,75-77,93-95) — are replayed from the events of that chain (tl_hill_climb_trace_chain), the
+// shuffles through tl_hill_draw.  window: epochs evaluated at once (0: the plan's, 1: epoch after epoch); the same result.
+inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
+                      uint64_t seed = 1, uint32_t chains = 1, uint32_t window = 0)
+{
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size();
+    std::vector<uint32_t> init, out(n);
+    if (init_tour) init = problem.positions_of(*init_tour);
+    const uint32_t *ip = init_tour ? init.data() : nullptr;
+    const tl_hill_opts o{(uint32_t)opts.epochs, (uint32_t)opts.platoo_epochs, window, 0u};
+    float cost = 0.f;
+    tl_stats st{};
+    uint32_t chain = 0;
+    if (chains > 1) {
+        std::vector<uint32_t> outs((size_t)chains * n), moves(chains);
+        std::vector<float> costs(chains);
+        ctx.check(tl_hill_climb_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, chains, &o, seed, outs.data(), costs.data(),
+                                           moves.data(), &chain, &st));
+        std::copy(outs.begin() + (size_t)chain * n, outs.begin() + (size_t)(chain + 1) * n, out.begin());
+        cost = costs[chain];
+        st.moves = moves[chain];
+        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
+    } else if (!(progress_tx && *progress_tx)) {
+        ctx.check(tl_hill_climb(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, out.data(), &cost, &st));
+        return detail::finish(problem, out, cost, st, nullptr);
+    }
+    uint32_t cap = 1u << 14, len = 0;
+    std::vector<uint32_t> log;
+    for (;;) {
+        log.assign((size_t)cap * 4, 0u);
+        ctx.check(tl_hill_climb_trace_chain(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, chain, out.data(), &cost, &st, log.data(), cap, &len));
+        if (len <= cap) break;
+        cap = len;  // deterministic: once more with room for every event
+    }
+    std::vector<uint32_t> pos(n);
+    for (uint32_t q = 0; q < n; ++q) pos[q] = init_tour ? init[q] : q;
+    std::vector<size_t> route(n);
+    auto send = [&](float d) {
+        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[pos[q]].id;
+        (*progress_tx)(ProgressKind::PathUpdate, route, d);
+    };
+    send(0.0f);
+    for (uint32_t m = 0; m < len; ++m) {
+        if (log[4 * m + 1] == 0xFFFFFFFFu) {  // a restart: the Fisher-Yates pass of csrc/hill_spec.h on the current contents
+            for (uint32_t j = n - 1u; j >= 1u; --j) {
+                const uint64_t u = tl_hill_draw(seed, chain, (1ull << 58) + (uint64_t)log[4 * m] * n + j, 26u);
+                std::swap(pos[j], pos[(uint32_t)(((u >> 32) * (j + 1u)) >> 32)]);
+            }
+            send(0.0f);
+        } else {
+            std::reverse(pos.begin() + log[4 * m + 1], pos.begin() + log[4 * m + 2] + 1);  // swap_cities (route.rs:102-113)
+            float d;
+            std::memcpy(&d, &log[4 * m + 3], 4);
+            send(d);
+        }
+    }
+    Solution s = detail::finish(problem, out, cost, st, nullptr);
+    (*progress_tx)(ProgressKind::Done, s.route_, cost);
+    return s;
+}
+}  // namespace hill_climb
+
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
-enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch, FlowerPollination, GravitationalSearch, KohonenSom };
+enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch, FlowerPollination, GravitationalSearch, KohonenSom, HillClimb };
 
 inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
 {
@@ -1499,6 +1569,7 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
     else if (s == "flower_pollination") out = Solvers::FlowerPollination;  // (the alias `fpa` likewise)
     else if (s == "gravitational_search") out = Solvers::GravitationalSearch;  // (the alias `gsa` likewise)
     else if (s == "kohonen_som") out = Solvers::KohonenSom;  // (the aliases `som` and `kohonen` likewise)
+    else if (s == "hill_climb") out = Solvers::HillClimb;  // (the reference's `stochastic_hill` stays refused, below; `hill` stays unknown)
     else {
         static const char *cpu_only[] = {"aco", "branch_bound",
                                          "cs", "fpa", "fourier", "ga", "gsa",
@@ -1515,6 +1586,7 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
                 if (s == "fpa") why += "; the seeded flower pollination of this build is `flower_pollination`";
                 if (s == "gsa") why += "; the seeded gravitational search of this build is `gravitational_search`";
                 if (s == "som" || s == "kohonen") why += "; the seeded Kohonen map of this build is `kohonen_som`";
+                if (s == "stochastic_hill") why += "; the seeded hill climb of this build is `hill_climb`";
                 return false;
             }
         why = "unknown solver";  // FromStr's Err (mod.rs:588)
@@ -1544,6 +1616,7 @@ inline const char *solver_name(Solvers s)
         case Solvers::FlowerPollination: return "flower_pollination";
         case Solvers::GravitationalSearch: return "gravitational_search";
         case Solvers::KohonenSom: return "kohonen_som";
+        case Solvers::HillClimb: return "hill_climb";
         default: return "shuffle";
     }
 }
@@ -1568,6 +1641,7 @@ struct StageOptions {
     uint32_t gsa_runs = 1;  // a gravitational_search stage runs this many runs and keeps the best
     kohonen_som::SOMOptions som;
     uint32_t som_runs = 1;  // a kohonen_som stage runs this many runs and keeps the best
+    uint32_t hill_chains = 1;  // a hill_climb stage runs this many chains and keeps the best
     uint64_t seed = 1;  // LK kicks, shuffle, SA, tabu and GA draws
     const ProgressFn *progress = nullptr;  // handed to every stage's solve() (the reference's CLI passes None; teeline-qt a sender)
 };
@@ -1638,6 +1712,7 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             case Solvers::FlowerPollination: sol = flower_pollination::solve(ctx, problem, flower_pollination::FPAOptions{o.heuristic, o.fpa_mutation_probability}, o.progress, init, o.seed, o.fpa_runs); break;
             case Solvers::GravitationalSearch: sol = gravitational_search::solve(ctx, problem, o.heuristic, o.progress, init, o.seed, o.gsa_runs); break;
             case Solvers::KohonenSom: sol = kohonen_som::solve(ctx, problem, o.som, o.progress, init, o.seed, o.som_runs); break;
+            case Solvers::HillClimb: sol = hill_climb::solve(ctx, problem, o.heuristic, o.progress, init, o.seed, o.hill_chains); break;
         }
         const auto t1 = std::chrono::steady_clock::now();
         const uint64_t ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();

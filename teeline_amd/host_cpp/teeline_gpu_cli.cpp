@@ -34,6 +34,9 @@
 //               (--seed) with --learning_rate (0.8), --radius_fraction (0.1) and --neuron_multiplier (8): SOMOptions, mod.rs:1465-1499;
 //               --runs K (K runs of the seed at once, the best kept); `solve kohonen_som` runs alone: the map is constructive and
 //               ignores a start tour (it is in neither of mod.rs:129-157's lists)
+//     hill    : hill_climb (the reference's `stochastic_hill` stays refused, `hill` unknown) runs --epochs + 1 epochs (default 10000)
+//               of seeded draws (--seed) with --platoo_epochs (500): HeuristicOptions; --runs K (K chains of the seed at once, the best
+//               kept); `solve hill_climb` alone is pipeline(shuffle, hill_climb) (mod.rs:141-157)
 //     solve   : 2opt / 3opt / or_opt / lk auto-expand to pipeline(nn, solver) unless --no-seed (main.rs:387-397, mod.rs:129-139);
 //               gec (greedy_edge), sav (savings) and chr (christofides) are constructions and run alone; so does bhk (bellman_karp),
 //               the exact solver (n <= 26, mod.rs:2137) — as a later pipeline stage it ignores its seed
@@ -71,7 +74,7 @@ struct Args {
 {
     if (why) std::fprintf(stderr, "error: %s\n", why);
     std::fprintf(stderr,
-                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|genetic_algorithm|ant_colony|particle_swarm|cuckoo_search|flower_pollination|gravitational_search|kohonen_som|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
+                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|genetic_algorithm|ant_colony|particle_swarm|cuckoo_search|flower_pollination|gravitational_search|kohonen_som|hill_climb|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
                  "                         [--optimal-tour FILE] [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P]\n"
                  "                         [--n_nearest K] [--max-depth D] [--seed S] [--best-sweep] [--device N] [--stats]\n"
                  "                         [--progress-digest] [--exact-walk]\n"
@@ -142,7 +145,7 @@ Args parse(int argc, char **argv)
         else if (s == "--beta") a.opt.aco.beta = std::stof(val());
         else if (s == "--evaporation-rate" || s == "--evaporation_rate") a.opt.aco.evaporation_rate = std::stof(val());
         else if (s == "--num-ants" || s == "--num_ants") a.opt.aco.num_ants = parse_usize(s, val());
-        else if (s == "--runs") a.opt.aco_runs = a.opt.pso_runs = a.opt.cs_runs = a.opt.fpa_runs = a.opt.gsa_runs = a.opt.som_runs = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
+        else if (s == "--runs") a.opt.aco_runs = a.opt.pso_runs = a.opt.cs_runs = a.opt.fpa_runs = a.opt.gsa_runs = a.opt.som_runs = a.opt.hill_chains = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--chains") a.opt.sa_chains = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--platoo_epochs" || s == "--platoo-epochs") a.opt.heuristic.platoo_epochs = a.opt.lk.heuristic.platoo_epochs = parse_usize(s, val());
         else if (s == "--n_nearest" || s == "--n-nearest") a.opt.heuristic.n_nearest = a.opt.lk.heuristic.n_nearest = parse_usize(s, val());
@@ -288,7 +291,7 @@ int run(int argc, char **argv)
                 // auto_expand_with_nn (mod.rs:129-139): deterministic local searches are seeded with a nearest-neighbour stage
                 const bool expand = s == Solvers::TwoOpt || s == Solvers::ThreeOpt || s == Solvers::LinKernighan || s == Solvers::OrOpt || s == Solvers::TabuSearch;
                 if (!a.no_seed && expand) stages = {Solvers::NearestNeighbor, s};
-                else if (!a.no_seed && (s == Solvers::SimulatedAnnealing || s == Solvers::GeneticAlgorithm || s == Solvers::AntColony || s == Solvers::ParticleSwarm || s == Solvers::CuckooSearch || s == Solvers::FlowerPollination || s == Solvers::GravitationalSearch)) stages = {Solvers::RandomShuffle, s};  // mod.rs:144-157
+                else if (!a.no_seed && (s == Solvers::SimulatedAnnealing || s == Solvers::GeneticAlgorithm || s == Solvers::AntColony || s == Solvers::ParticleSwarm || s == Solvers::CuckooSearch || s == Solvers::FlowerPollination || s == Solvers::GravitationalSearch || s == Solvers::HillClimb)) stages = {Solvers::RandomShuffle, s};  // mod.rs:144-157
                 else stages = {s};
             }
         } else {
