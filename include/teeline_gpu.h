@@ -1132,6 +1132,58 @@ int tl_hill_climb_population(tl_ctx *ctx, const float *xy, uint32_t n, const flo
 uint64_t tl_hill_draw(uint64_t seed, uint32_t chain, uint64_t event, uint32_t slot);
 int tl_hill_climb_plan(uint32_t n, uint32_t count, int cus, int lds_bytes, uint32_t window_request, uint32_t *window, int *threads, uint32_t *per_launch);
 
+/* ---- Fourier curve: replaces fourier::solve (fourier.rs:10-312) ----------------------------------------- */
+/* A closed curve gamma(s) = sum_k c_k e^{2 pi i k s}, |k| <= k_max, sampled at m points, descends towards the cities: k_max stages
+ * (stage s frees the modes |k| <= s + 1) of `epochs` gradient steps, lambda multiplied by lambda_decay after each stage; the tour is
+ * the cities in the order of their nearest sample (a stable sort: ties in city order), priced by tour_length.  The reference's
+ * quirks are kept: n < 2 is the trivial tour; a start tour is ignored and no progress is sent; the centroid, the radius and every
+ * coefficient's gradient are sequential f64 sums in city order; only the modes |k| <= k_active are updated.  xy is required (the
+ * curve descends on the coordinates); dm_packed, where given, only prices the tour.
+ * The solver draws nothing, so there is no seed: a batch is a list of option sets on one problem, one workgroup each.  Job j of a
+ * batch equals the single call with opts[j] bit for bit; *best_index is the job of the lowest cost, the lowest index among equals.
+ * This project's specification (csrc/fourier_spec.h) departs from the reference in five places: the basis is one
+ * table E[(k j) mod m] from an exact quadrant reduction instead of libm's cos and sin of a rounded angle; |z| is sqrt(re re + im im)
+ * instead of hypot; the nearest sample is the least f32 sqrt(dx dx + dy dy), the LOWEST index among equal roots (the reference:
+ * whichever its kd-tree visits first); (2 pi k)^2 is t t with t = 6.283185307179586 k; lambda is the running product.
+ * opts NULL (single call only): the defaults (k_max 4, m 200, lambda 0.05, lambda_decay 0.5, lr 0.05, epochs 400).  What
+ * FourierOptions::validate refuses (k_max < 1, m < 2, lambda <= 0, lambda_decay outside (0, 1), lr <= 0, epochs < 1) is
+ * TL_ERR_BADARG, as are a coordinate that is not finite, launch parameters that differ inside a batch and a coeff_stride below the
+ * largest job's 2 (2 k_max + 1).  The limits are TL_ERR_UNSUPPORTED: k_max > 32, m > 4096, n > 65 536, k_max x epochs >= 2^32, more
+ * than 65 535 jobs, a context whose flags hold a bit no flag has.
+ * out_pos: jobs x n positions; out_costs (optional): jobs f32; out_coeffs (optional): job j's final coefficients, (re, im) pairs for
+ * k = -k_max .. k_max, at out_coeffs + j coeff_stride doubles (the single call: 2 (2 k_max + 1) doubles), the rest zero.  Evidence
+ * of job 0 (optional): log — log_cap x n words, every city's nearest sample at step t (of k_max x epochs) in row t; stage_coeffs —
+ * k_max x 2 (2 k_max + 1) doubles, the coefficients at the end of every stage.  stats: sweeps = steps of all jobs, candidates =
+ * (city, sample) pairs searched.
+ * Host-only: tl_fourier_basis — the table E of m (2 m doubles); tl_fourier_init — the start coefficients; tl_fourier_nearest —
+ * every city's nearest sample on a given curve (m pairs of f64) by the specification's rule; tl_fourier_curve_plan — the threads of
+ * a workgroup, the form (1: everything in LDS, 2: basis, cities and sample indices in the workspace), the chunk and the span a call
+ * would run with; tl_fourier_curve_work_bytes — the device workspace such a call takes (0 where it would be refused or n < 2).
+ * tl_fourier_selftest_search: the DEVICE's search of the gradient step alone, on a curve given by the caller. */
+typedef struct tl_fourier_opts { /* FourierOptions, src/tsp/mod.rs:1341-1384 */
+    uint32_t k_max;
+    uint32_t m;
+    uint32_t epochs;
+    uint32_t chunk;      /* not the reference's: cities whose gradient terms are formed at once; 0: 64.  Same result */
+    double lambda;
+    double lambda_decay;
+    double lr;
+    uint32_t span_steps; /* not the reference's: gradient steps of one launch; 0: 65 536.  Same result */
+    uint32_t threads;    /* not the reference's: lanes of a workgroup, a multiple of 64 in 64 .. 1024, >= 2 (2 k_max + 1); 0: the plan's.  Same result */
+} tl_fourier_opts;
+int tl_fourier_curve(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const tl_fourier_opts *opts, uint32_t *out_pos, float *out_cost,
+                     double *out_coeffs, tl_stats *stats);
+int tl_fourier_curve_batch(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const tl_fourier_opts *opts, uint32_t jobs, uint32_t *out_pos,
+                           float *out_costs, double *out_coeffs, uint32_t coeff_stride, uint32_t *best_index, tl_stats *stats, uint32_t *log, uint32_t log_cap,
+                           double *stage_coeffs);
+uint64_t tl_fourier_curve_work_bytes(uint32_t n, const tl_fourier_opts *opts, uint32_t jobs, uint32_t log_cap);
+int tl_fourier_curve_plan(uint32_t n, const tl_fourier_opts *opts, uint32_t jobs, int lds_bytes, int *threads, uint32_t *form, uint32_t *chunk,
+                          uint32_t *span_steps);
+int tl_fourier_basis(uint32_t m, double *out);
+int tl_fourier_init(const float *xy, uint32_t n, uint32_t k_max, double *out_coeffs);
+int tl_fourier_nearest(const double *gamma, uint32_t m, const float *xy, uint32_t n, uint32_t *out_idx);
+int tl_fourier_selftest_search(tl_ctx *ctx, const double *gamma, uint32_t m, const float *xy, uint32_t n, int threads, uint32_t *out_idx);
+
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts
  * first..first+count as above; seed ignored otherwise).  d_out_pos: count x n u32, d_out_cost: count f32,

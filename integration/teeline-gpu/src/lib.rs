@@ -89,6 +89,28 @@ pub struct SomOpts {
     pub work_bytes: u64,
 }
 
+/// `tl_fourier_opts`: FourierOptions (src/tsp/mod.rs:1341-1384) and the launch parameters (0: the plan's), on none of which the
+/// result depends: the chunk of cities whose gradient terms are formed at once, the steps of one launch, the lanes of a workgroup.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct FourierOpts {
+    pub k_max: u32,
+    pub m: u32,
+    pub epochs: u32,
+    pub chunk: u32,
+    pub lambda: f64,
+    pub lambda_decay: f64,
+    pub lr: f64,
+    pub span_steps: u32,
+    pub threads: u32,
+}
+
+impl Default for FourierOpts {
+    fn default() -> Self {
+        FourierOpts { k_max: 4, m: 200, epochs: 400, chunk: 0, lambda: 0.05, lambda_decay: 0.5, lr: 0.05, span_steps: 0, threads: 0 }
+    }
+}
+
 /// `tl_hill_opts`: HeuristicOptions' epochs and platoo_epochs (src/tsp/mod.rs:598-608) and the window (0: the plan's, 1: the chain
 /// epoch after epoch).  The result does not depend on the window.
 #[repr(C)]
@@ -278,6 +300,10 @@ unsafe extern "C" {
                                 first_chain: u32, count: u32, opts: *const HillOpts, seed: u64, out_pos: *mut u32, out_costs: *mut f32,
                                 out_moves: *mut u32, best_index: *mut u32, stats: *mut Stats) -> i32;
     fn tl_hill_draw(seed: u64, chain: u32, event: u64, slot: u32) -> u64;
+    fn tl_fourier_curve_batch(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, opts: *const FourierOpts, jobs: u32, out_pos: *mut u32,
+                              out_costs: *mut f32, out_coeffs: *mut f64, coeff_stride: u32, best_index: *mut u32, stats: *mut Stats, log: *mut u32,
+                              log_cap: u32, stage_coeffs: *mut f64) -> i32;
+    fn tl_fourier_curve_work_bytes(n: u32, opts: *const FourierOpts, jobs: u32, log_cap: u32) -> u64;
     fn tl_nearest_neighbor(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, n_nearest: u32,
                            out_pos: *mut u32, out_cost: *mut f32) -> c_int;
     fn tl_greedy_edge(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
@@ -918,6 +944,40 @@ impl Context {
             .map(|k| Tour { pos: pos[k * n as usize..(k + 1) * n as usize].to_vec(), cost: costs[k], stats: Stats { moves: moves[k] as u64, ..st } })
             .collect();
         Ok((tours, best))
+    }
+
+    /// `fourier::solve` (fourier.rs:10-312) for every option set of `jobs` at once, one workgroup each: the tours and the index of
+    /// the best one (lowest cost, then lowest index).  The solver draws nothing, so there is no seed; job j equals the call with
+    /// `jobs[j]` alone bit for bit.  The basis table, sqrt for hypot, the lowest index among samples at one f32 distance, (2 pi k)^2
+    /// as t t and lambda as the running product are the library's own specification (include/teeline_gpu.h).  The curve descends on
+    /// the coordinates; `dm_packed` only prices the tour.  (Written against the header; not compiled here: no Rust toolchain on the
+    /// build machine, see scripts/check_rust.sh.)
+    pub fn fourier_curve_batch(&self, xy: &[f32], dm_packed: Option<&[f32]>, jobs: &[FourierOpts]) -> Result<(Vec<Tour>, u32), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, None);
+        let count = jobs.len();
+        let mut pos = vec![0u32; (n as usize).max(1) * count];
+        let mut costs = vec![0f32; count];
+        let (mut best, mut st) = (0u32, Stats::default());
+        // SAFETY: the slices hold n cities (check_inputs); the outputs hold count x n and count entries; the optional outputs are null.
+        let rc = unsafe {
+            tl_fourier_curve_batch(self.raw, xy.as_ptr(), n, opt_ptr(dm_packed), jobs.as_ptr(), count as u32, pos.as_mut_ptr(), costs.as_mut_ptr(),
+                                   ptr::null_mut(), 0, &mut best, &mut st, ptr::null_mut(), 0, ptr::null_mut())
+        };
+        self.check(rc)?;
+        let tours = (0..count).map(|k| Tour { pos: pos[k * n as usize..(k + 1) * n as usize].to_vec(), cost: costs[k], stats: st }).collect();
+        Ok((tours, best))
+    }
+
+    /// One job of `fourier_curve_batch`.
+    pub fn fourier_curve(&self, xy: &[f32], dm_packed: Option<&[f32]>, opts: &FourierOpts) -> Result<Tour, Error> {
+        self.fourier_curve_batch(xy, dm_packed, std::slice::from_ref(opts)).map(|(mut t, _)| t.remove(0))
+    }
+
+    /// The device workspace a `fourier_curve_batch` of these jobs takes (0 where it would be refused, or n < 2).
+    pub fn fourier_curve_work_bytes(n: u32, jobs: &[FourierOpts]) -> u64 {
+        // SAFETY: a host-only query over the slice.
+        unsafe { tl_fourier_curve_work_bytes(n, jobs.as_ptr(), jobs.len() as u32, 0) }
     }
 
     /// Largest n of `hill_climb` (the current tour lives in one CU's LDS, 12 bytes per city).

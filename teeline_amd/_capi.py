@@ -77,6 +77,8 @@ SYMBOLS = [
     "tl_som_draw", "tl_som_schedule", "tl_som_h", "tl_som_ring_init", "tl_som_selftest_bmu",
     "tl_hill_climb", "tl_hill_climb_trace", "tl_hill_climb_trace_chain", "tl_hill_climb_population", "tl_hill_climb_lds_max_n", "tl_hill_climb_plan",
     "tl_hill_draw",
+    "tl_fourier_curve", "tl_fourier_curve_batch", "tl_fourier_curve_work_bytes", "tl_fourier_curve_plan",
+    "tl_fourier_basis", "tl_fourier_init", "tl_fourier_nearest", "tl_fourier_selftest_search",
 ]
 
 
@@ -129,6 +131,13 @@ class TlSomOpts(C.Structure):
     workspace one launch sequence plans with (0: the default)"""
     _fields_ = [("epochs", C.c_uint32), ("neuron_multiplier", C.c_uint32), ("learning_rate", C.c_double), ("radius_fraction", C.c_double),
                 ("form", C.c_uint32), ("reserved", C.c_uint32), ("work_bytes", C.c_uint64)]
+
+
+class TlFourierOpts(C.Structure):
+    """tl_fourier_opts: FourierOptions (src/tsp/mod.rs:1341-1384) and the launch parameters (0: the plan's): the chunk of cities whose
+    gradient terms are formed at once, the steps of one launch, the lanes of a workgroup"""
+    _fields_ = [("k_max", C.c_uint32), ("m", C.c_uint32), ("epochs", C.c_uint32), ("chunk", C.c_uint32), ("lam", C.c_double),
+                ("lambda_decay", C.c_double), ("lr", C.c_double), ("span_steps", C.c_uint32), ("threads", C.c_uint32)]
 
 
 # tl_lk_progress_fn: void (*)(void *user, const uint32_t *best_pos, uint32_t n, float best_dist)
@@ -347,5 +356,15 @@ def load():
     L.tl_hill_draw.argtypes = [u64, u32, u64, u32]
     L.tl_hill_draw.restype = u64
     L.tl_hill_climb_plan.argtypes = [u32, u32, i32, i32, u32, C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]
+    fo = C.POINTER(TlFourierOpts)
+    L.tl_fourier_curve.argtypes = [vp, vp, u32, vp, fo, vp, f32p, vp, C.POINTER(TlStats)]
+    L.tl_fourier_curve_batch.argtypes = [vp, vp, u32, vp, fo, u32, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(TlStats), vp, u32, vp]
+    L.tl_fourier_curve_work_bytes.argtypes = [u32, fo, u32, u32]
+    L.tl_fourier_curve_work_bytes.restype = u64
+    L.tl_fourier_curve_plan.argtypes = [u32, fo, u32, i32, C.POINTER(i32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.tl_fourier_basis.argtypes = [u32, vp]
+    L.tl_fourier_init.argtypes = [vp, u32, u32, vp]
+    L.tl_fourier_nearest.argtypes = [vp, u32, vp, u32, vp]
+    L.tl_fourier_selftest_search.argtypes = [vp, vp, u32, vp, u32, i32, vp]
     _lib = L
     return L

@@ -617,6 +617,41 @@ hipError_t launch_som_train(const SomArgs &A, uint32_t runs, bool lds_form, hipS
 hipError_t launch_som_extract(const SomArgs &A, uint32_t runs, hipStream_t s);               // every run's tour and cost from its ring
 hipError_t launch_som_selftest_bmu(const SomArgs &A, int threads, bool lds_form, hipStream_t s);  // the training's BMU of cities 0 .. n - 1 into A.bmu, on A.ring as it is
 
+// fourier_curve.hip — the Fourier-curve solver, the job (an option set) a grid dimension, a span of gradient steps per launch
+struct FourierJob {          // one option set of a batch
+    double lambda, lambda_decay, lr_over_n;
+    uint32_t k_max, m, epochs;
+    uint32_t total;          // k_max epochs: the job's steps
+    uint32_t off_c;          // where the job's 2 (2 k_max + 1) coefficient doubles begin in FourierArgs::coeffs
+    uint32_t off_m;          // where its m samples begin in FourierArgs::basis (pairs of f64) and ::g32 (pairs of f32)
+};
+struct FourierArgs {
+    const FourierJob *jobs;  // [J]
+    const float2 *cities;    // n cities as the solver reads them
+    double *coeffs;          // every job's coefficients (re, im pairs): loaded at a span's start, stored at its end
+    double *basis;           // every job's table E: the workspace form's (and the decode's) copy
+    float2 *g32;             // every job's curve as f32: the decode's (and the self-test's) samples
+    uint32_t *sidx;          // [J][n] every city's nearest sample: the workspace form's array, the decode's in either form
+    const float2 *xy;        // the decode's cost: n cities (coordinate form)
+    const float *dm_full;    // or the matrix expanded to row-major n x n
+    float *edge;             // [J][n] the tour's edge lengths
+    uint32_t *out_pos;       // [J][n] the decoded tour
+    float *out_cost;         // [J] its cost
+    uint32_t *log;           // optional: [log_cap][n] every city's sample index at step t, job 0 of the launch
+    double *stage_c;         // optional: [k_max][2 L] job 0's coefficients at the end of every stage
+    const double *gamma_in;  // the self-test's curve: m pairs
+    uint32_t log_cap;
+    uint32_t n;
+    uint32_t s0, s1;         // the span [s0, s1) of the steps; a job runs what of it lies below its total
+    uint32_t chunk;          // cities whose gradient terms are formed at once
+    uint32_t max_l, max_m;   // the largest 2 k_max + 1 and m of the launch: the LDS layout
+};
+size_t fourier_curve_lds_bytes(uint32_t n, uint32_t max_l, uint32_t max_m, uint32_t chunk, bool lds_form);
+int fourier_curve_threads(uint32_t n, uint32_t m);  // about 32 (city, sample) pairs a lane in whole waves, 256 .. 1024
+hipError_t launch_fourier_steps(const FourierArgs &A, uint32_t jobs, int threads, bool lds_form, hipStream_t s);  // the steps [s0, s1): one workgroup per job
+hipError_t launch_fourier_decode(const FourierArgs &A, uint32_t jobs, hipStream_t s);                                // every job's tour and cost from its coefficients
+hipError_t launch_fourier_selftest_search(const FourierArgs &A, int threads, hipStream_t s);  // the steps' search alone on A.gamma_in (m = max_m) into A.sidx
+
 // lk.hip
 struct LkState {          // device-side state machine of the multi-CU LK variant
     uint32_t key;            // min pair index with a valid chain in the current scan (0xFFFFFFFF: none)

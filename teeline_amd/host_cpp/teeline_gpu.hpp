@@ -1543,8 +1543,51 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOp
 }
 }  // namespace hill_climb
 
+namespace fourier_curve {  // fourier.rs:10-312
+struct FourierOptions {  // mod.rs:1341-1352
+    size_t k_max = 4;
+    size_t m = 200;
+    double lambda = 0.05;
+    double lambda_decay = 0.5;
+    double lr = 0.05;
+    size_t epochs = 400;
+};
+inline tl_fourier_opts c_opts(const FourierOptions &o)
+{
+    return tl_fourier_opts{(uint32_t)std::min<size_t>(o.k_max, 0xFFFFFFFFu), (uint32_t)std::min<size_t>(o.m, 0xFFFFFFFFu), (uint32_t)std::min<size_t>(o.epochs, 0xFFFFFFFFu),
+                           0u, o.lambda, o.lambda_decay, o.lr, 0u, 0u};
+}
+// The algorithm is the reference's; the basis table, sqrt for hypot, the lowest index among samples at one f32 distance, (2 pi k)^2
+// as t t and lambda as the running product are this project's specification (include/teeline_gpu.h).  The solver draws nothing: a
+// batch is a list of option sets, all at once, the best kept (lowest cost, then lowest index; *best_job names it).  progress_tx and
+// init_tour are ignored, as the reference ignores them.
+inline Solution solve_many(Context &ctx, const TspProblem &problem, const std::vector<FourierOptions> &jobs, uint32_t *best_job = nullptr)
+{
+    if (jobs.empty()) throw std::runtime_error("fourier_curve: no option set");
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size(), J = (uint32_t)jobs.size();
+    std::vector<tl_fourier_opts> o;
+    for (const FourierOptions &j : jobs) o.push_back(c_opts(j));
+    std::vector<uint32_t> outs((size_t)J * std::max(n, 1u)), out(n);
+    std::vector<float> costs(J);
+    tl_stats st{};
+    uint32_t best = 0;
+    ctx.check(tl_fourier_curve_batch(ctx.get(), xy.data(), n, problem.explicit_packed(), o.data(), J, outs.data(), costs.data(), nullptr, 0u, &best, &st, nullptr, 0u,
+                                     nullptr));
+    std::copy(outs.begin() + (size_t)best * n, outs.begin() + (size_t)(best + 1) * n, out.begin());
+    if (best_job) *best_job = best;
+    return detail::finish(problem, out, costs[best], st, nullptr);
+}
+inline Solution solve(Context &ctx, const TspProblem &problem, const FourierOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour)
+{
+    (void)progress_tx;
+    (void)init_tour;
+    return solve_many(ctx, problem, std::vector<FourierOptions>{opts});
+}
+}  // namespace fourier_curve
+
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
-enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch, FlowerPollination, GravitationalSearch, KohonenSom, HillClimb };
+enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch, FlowerPollination, GravitationalSearch, KohonenSom, HillClimb, FourierCurve };
 
 inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
 {
@@ -1570,6 +1613,7 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
     else if (s == "gravitational_search") out = Solvers::GravitationalSearch;  // (the alias `gsa` likewise)
     else if (s == "kohonen_som") out = Solvers::KohonenSom;  // (the aliases `som` and `kohonen` likewise)
     else if (s == "hill_climb") out = Solvers::HillClimb;  // (the reference's `stochastic_hill` stays refused, below; `hill` stays unknown)
+    else if (s == "fourier_curve") out = Solvers::FourierCurve;  // (the reference's `fourier` stays refused, below)
     else {
         static const char *cpu_only[] = {"aco", "branch_bound",
                                          "cs", "fpa", "fourier", "ga", "gsa",
@@ -1587,6 +1631,7 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
                 if (s == "gsa") why += "; the seeded gravitational search of this build is `gravitational_search`";
                 if (s == "som" || s == "kohonen") why += "; the seeded Kohonen map of this build is `kohonen_som`";
                 if (s == "stochastic_hill") why += "; the seeded hill climb of this build is `hill_climb`";
+                if (s == "fourier") why += "; the Fourier-curve solver of this build is `fourier_curve`";
                 return false;
             }
         why = "unknown solver";  // FromStr's Err (mod.rs:588)
@@ -1617,6 +1662,7 @@ inline const char *solver_name(Solvers s)
         case Solvers::GravitationalSearch: return "gravitational_search";
         case Solvers::KohonenSom: return "kohonen_som";
         case Solvers::HillClimb: return "hill_climb";
+        case Solvers::FourierCurve: return "fourier_curve";
         default: return "shuffle";
     }
 }
@@ -1642,6 +1688,8 @@ struct StageOptions {
     kohonen_som::SOMOptions som;
     uint32_t som_runs = 1;  // a kohonen_som stage runs this many runs and keeps the best
     uint32_t hill_chains = 1;  // a hill_climb stage runs this many chains and keeps the best
+    fourier_curve::FourierOptions fourier;
+    std::vector<fourier_curve::FourierOptions> fourier_jobs;  // not empty: a fourier_curve stage runs these option sets at once and keeps the best
     uint64_t seed = 1;  // LK kicks, shuffle, SA, tabu and GA draws
     const ProgressFn *progress = nullptr;  // handed to every stage's solve() (the reference's CLI passes None; teeline-qt a sender)
 };
@@ -1713,6 +1761,9 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             case Solvers::GravitationalSearch: sol = gravitational_search::solve(ctx, problem, o.heuristic, o.progress, init, o.seed, o.gsa_runs); break;
             case Solvers::KohonenSom: sol = kohonen_som::solve(ctx, problem, o.som, o.progress, init, o.seed, o.som_runs); break;
             case Solvers::HillClimb: sol = hill_climb::solve(ctx, problem, o.heuristic, o.progress, init, o.seed, o.hill_chains); break;
+            case Solvers::FourierCurve:
+                sol = o.fourier_jobs.empty() ? fourier_curve::solve(ctx, problem, o.fourier, o.progress, init) : fourier_curve::solve_many(ctx, problem, o.fourier_jobs);
+                break;
         }
         const auto t1 = std::chrono::steady_clock::now();
         const uint64_t ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();

@@ -37,6 +37,10 @@
 //     hill    : hill_climb (the reference's `stochastic_hill` stays refused, `hill` unknown) runs --epochs + 1 epochs (default 10000)
 //               of seeded draws (--seed) with --platoo_epochs (500): HeuristicOptions; --runs K (K chains of the seed at once, the best
 //               kept); `solve hill_climb` alone is pipeline(shuffle, hill_climb) (mod.rs:141-157)
+//     fourier : fourier_curve (the reference's `fourier` stays refused) descends a closed Fourier curve: --k-max (4), --m (200), --lambda
+//               (0.05), --lambda-decay (0.5), --lr (0.05), --epochs (400): FourierOptions, mod.rs:1341-1384; --lambda and --lr take
+//               comma lists whose product runs as one batch, the best kept; no seed (the solver draws nothing); `solve fourier_curve`
+//               runs alone and ignores a start tour
 //     solve   : 2opt / 3opt / or_opt / lk auto-expand to pipeline(nn, solver) unless --no-seed (main.rs:387-397, mod.rs:129-139);
 //               gec (greedy_edge), sav (savings) and chr (christofides) are constructions and run alone; so does bhk (bellman_karp),
 //               the exact solver (n <= 26, mod.rs:2137) — as a later pipeline stage it ignores its seed
@@ -68,13 +72,14 @@ struct Args {
     bool no_seed = false, best = false, exact_walk = false, stats = false, short_list = false, progress_digest = false, timing = false, full_exit = false;
     int device = 0, repeat = 1;
     pipeline::StageOptions opt;
+    std::vector<double> fourier_lambdas, fourier_lrs;  // --lambda / --lr comma lists: their product is a fourier_curve batch
 };
 
 [[noreturn]] void usage_exit(const char *why)
 {
     if (why) std::fprintf(stderr, "error: %s\n", why);
     std::fprintf(stderr,
-                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|genetic_algorithm|ant_colony|particle_swarm|cuckoo_search|flower_pollination|gravitational_search|kohonen_som|hill_climb|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
+                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|genetic_algorithm|ant_colony|particle_swarm|cuckoo_search|flower_pollination|gravitational_search|kohonen_som|hill_climb|fourier_curve|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
                  "                         [--optimal-tour FILE] [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P]\n"
                  "                         [--n_nearest K] [--max-depth D] [--seed S] [--best-sweep] [--device N] [--stats]\n"
                  "                         [--progress-digest] [--exact-walk]\n"
@@ -133,7 +138,7 @@ Args parse(int argc, char **argv)
         else if (s == "--output-format") a.output_format = val();
         else if (s == "--optimal-tour") a.optimal_tour = val();
         else if (s == "--distance-type") a.distance_type = val();
-        else if (s == "--epochs") a.opt.heuristic.epochs = a.opt.lk.heuristic.epochs = a.opt.sa.heuristic.epochs = a.opt.ga.heuristic.epochs = a.opt.aco.heuristic.epochs = a.opt.som.epochs = parse_usize(s, val());
+        else if (s == "--epochs") a.opt.heuristic.epochs = a.opt.lk.heuristic.epochs = a.opt.sa.heuristic.epochs = a.opt.ga.heuristic.epochs = a.opt.aco.heuristic.epochs = a.opt.som.epochs = a.opt.fourier.epochs = parse_usize(s, val());
         else if (s == "--cooling-rate" || s == "--cooling_rate") a.opt.sa.cooling_rate = std::stof(val());
         else if (s == "--min-temperature" || s == "--min_temperature") a.opt.sa.min_temperature = std::stof(val());
         else if (s == "--max-temperature" || s == "--max_temperature") a.opt.sa.max_temperature = std::stof(val());
@@ -160,6 +165,19 @@ Args parse(int argc, char **argv)
         else if (s == "--learning_rate" || s == "--learning-rate") a.opt.som.learning_rate = std::stod(val());
         else if (s == "--radius_fraction" || s == "--radius-fraction") a.opt.som.radius_fraction = std::stod(val());
         else if (s == "--neuron_multiplier" || s == "--neuron-multiplier") a.opt.som.neuron_multiplier = parse_usize(s, val());
+        else if (s == "--k-max" || s == "--k_max") a.opt.fourier.k_max = parse_usize(s, val());
+        else if (s == "--m") a.opt.fourier.m = parse_usize(s, val());
+        else if (s == "--lambda-decay" || s == "--lambda_decay") a.opt.fourier.lambda_decay = std::stod(val());
+        else if (s == "--lambda" || s == "--lr") {
+            std::vector<double> &list = s == "--lambda" ? a.fourier_lambdas : a.fourier_lrs;
+            const std::string v = val();
+            list.clear();
+            for (size_t at = 0; at <= v.size();) {
+                const size_t comma = std::min(v.find(',', at), v.size());
+                list.push_back(std::stod(v.substr(at, comma - at)));
+                at = comma + 1;
+            }
+        }
         else if (s == "--progress-digest") a.progress_digest = true;
         else if (s == "--timing") a.timing = true;
         else if (s == "--full-exit") a.full_exit = true;
@@ -167,6 +185,19 @@ Args parse(int argc, char **argv)
         else usage_exit(("unexpected argument " + s).c_str());
     }
     if (a.output_format != "text" && a.output_format != "json") usage_exit("--output-format: text or json");
+    if (!a.fourier_lambdas.empty()) a.opt.fourier.lambda = a.fourier_lambdas[0];
+    if (!a.fourier_lrs.empty()) a.opt.fourier.lr = a.fourier_lrs[0];
+    if (a.fourier_lambdas.size() > 1 || a.fourier_lrs.size() > 1) {  // the grid, lambda the outer index: one job each, the best kept
+        const std::vector<double> las = a.fourier_lambdas.empty() ? std::vector<double>{a.opt.fourier.lambda} : a.fourier_lambdas;
+        const std::vector<double> lrs = a.fourier_lrs.empty() ? std::vector<double>{a.opt.fourier.lr} : a.fourier_lrs;
+        for (double la : las)
+            for (double lr : lrs) {
+                fourier_curve::FourierOptions o = a.opt.fourier;
+                o.lambda = la;
+                o.lr = lr;
+                a.opt.fourier_jobs.push_back(o);
+            }
+    }
     if (a.opt.heuristic.n_nearest == 0) {  // HeuristicOptions::validate (mod.rs:677-682), through solve_with_context
         std::fprintf(stderr, "error: n_nearest must be >= 1\n");
         std::exit(1);
