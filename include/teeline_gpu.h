@@ -409,6 +409,59 @@ int tl_christofides(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32
 int tl_bellman_karp(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, uint32_t *out_pos, float *out_cost,
                     float *out_optimal, uint32_t *out_is_tour, tl_stats *stats);
 
+/* ---- branch and bound: the second exact solver, to 64 cities --------------------- */
+/* A depth-first branch and bound with the bound of branch_bound.rs:240-268 — the running cost, the next edge, a minimum spanning
+ * tree over the start and the unvisited cities — under a specification of this project's own; the reference's search order (a
+ * HashSet's iteration order) is not reproduced, and the name `branch_bound` stays refused.
+ * D(a, b): the distance of positions a, b in either input form, with tl_bellman_karp's bits, D(a, a) = +0.0.  L(p): tl_tour_length's
+ * sum (the closing edge first, then the n - 1 edges in order, sequential f32).  S: every permutation p of 0..n-1 with p[0] =
+ * opts->start; with n_nearest = K, 0 < K < n, p[k] must also lie in N_K(p[k-1]) wherever N_K(p[k-1]) holds an unvisited position
+ * (any unvisited position where it holds none, branch_bound.rs:231-235).  N_K(c) is c itself and the K - 1 positions j != c with the
+ * smallest (D(c, j), j).  K = 0 or K >= n: no restriction, the exact solver.
+ * The result R is the argmin over S of (L(p), p), p compared as a sequence of positions.  init_pos NULL: R is returned, *out_improved
+ * = 1.  init_pos given (a permutation, else TL_ERR_BADARG): R if L(R) < L(init_pos as given), else init_pos as given with
+ * *out_improved = 0 (branch_bound.rs:84-90).  *out_cost = L(out_pos).  With *out_proved = 1 the result is exactly that, whatever
+ * the launch parameters, the device and the run.  max_nodes / time_limit_ms (0: none) are checked between launches; when either
+ * ends the search the status is TL_OK, *out_proved = 0 and the result the best tour found so far (or init_pos, or start followed by
+ * the other positions in order): a valid tour, never longer than init_pos, otherwise unspecified.
+ * A child is cut only if running cost + next edge + MST, summed in f64, exceeds (double)bound x (1 + (n + 1) 2^-23): no tour of
+ * length <= bound is ever cut, equal lengths included (DESIGN.md §4.27 has the proof).
+ * n > TL_BNB_MAX_N: TL_ERR_UNSUPPORTED before anything is allocated.  A distance between two of the n positions that is NaN, has its
+ * sign bit set (-0.0 included) or is >= f32::MAX: TL_ERR_UNSUPPORTED; so is an instance none of whose tours has a length <=
+ * f32::MAX.  opts->start >= n (n >= 1): TL_ERR_BADARG.  n = 0 and n = 1 as tl_bellman_karp.  opts NULL: all zero.
+ * tl_branch_and_bound_host is the sequential restatement on the CPU (no context, no device): the same contract, the frontier
+ * builder of the device entry, the tests' oracle for large cases and the timing baseline; its budgets are checked at every node.
+ * tl_branch_and_bound_plan: the launch parameters the device entry takes for n on a device of `cus` compute units and `lds_bytes`
+ * of LDS per workgroup (each output optional; cus < 1 or lds_bytes < 0: TL_ERR_BADARG; n > TL_BNB_MAX_N: TL_ERR_UNSUPPORTED). */
+#define TL_BNB_MAX_N 64u
+typedef struct tl_bnb_opts {
+    uint32_t start;            /* p[0]; the mirrors pass the position of the smallest id (route.sort(), branch_bound.rs:35)  */
+    uint32_t n_nearest;        /* K; 0 or >= n: exact                                                                        */
+    uint64_t max_nodes;        /* 0: no limit                                                                                */
+    uint32_t time_limit_ms;    /* 0: no limit                                                                                */
+    uint32_t nodes_per_launch; /* nodes and leaves a wave takes per launch (0: the plan's)                                   */
+    uint32_t frontier_depth;   /* positions behind start that the host places before the device takes over (0: the plan's)  */
+    uint32_t workgroups;       /* 0: the plan's                                                                              */
+} tl_bnb_opts;
+typedef struct tl_bnb_stats {
+    uint64_t nodes;              /* prefixes whose bound was computed, host frontier included                                */
+    uint64_t leaves;             /* complete tours whose length was computed                                                 */
+    uint64_t launches;
+    uint64_t queue_start;        /* subtrees the host's frontier queued                                                      */
+    uint64_t queue_end;          /* ... plus those split off unfinished subtrees at launch boundaries                        */
+    uint64_t wave_launches;      /* launches x waves                                                                         */
+    uint64_t idle_wave_launches; /* of those, the ones that ended with no subtree and an empty queue                         */
+    double kernel_ms;            /* the launches, HIP events                                                                 */
+    double max_launch_ms;        /* the longest launch-and-poll interval seen by the host                                    */
+    double total_ms;
+} tl_bnb_stats;
+int tl_branch_and_bound(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, const uint32_t *init_pos, const tl_bnb_opts *opts,
+                        uint32_t *out_pos, float *out_cost, uint32_t *out_proved, uint32_t *out_improved, tl_bnb_stats *stats);
+int tl_branch_and_bound_host(const float *xy, const float *dm_packed, uint32_t n, const uint32_t *init_pos, const tl_bnb_opts *opts,
+                             uint32_t *out_pos, float *out_cost, uint32_t *out_proved, uint32_t *out_improved, tl_bnb_stats *stats);
+int tl_branch_and_bound_plan(uint32_t n, int cus, int lds_bytes, int *threads, int *workgroups, uint32_t *frontier_depth,
+                             uint32_t *nodes_per_launch);
+
 /* ---- multi-start 2-opt (north-star config 4; no counterpart in the reference) ---------------- */
 /* Runs restarts [first, first+count) — restart r starts from the Fisher–Yates permutation drawn
  * from splitmix64(seed + r) (specification: DESIGN.md / oracle tlo_restart_perm) — one descent per

@@ -39,6 +39,7 @@ TL_FLAG_3OPT_POP_FORCE_WG = 1 << 28  # tl_three_opt_population: one workgroup pe
 TL_FLAG_SA_NO_SPECULATION = 1 << 29  # tl_sim_anneal*: a window of one epoch (the chain epoch after epoch) instead of speculative windows
 TL_FLAG_TABU_FULL_COMPARE = 1 << 30  # tl_tabu_search*: every tabu-list membership test compares whole routes (the cross-check form)
 TL_BHK_MAX_N = 26  # tl_bellman_karp: largest n (a table of 2^(n-1) rows of 128 bytes: 4 GiB)
+TL_BNB_MAX_N = 64  # tl_branch_and_bound: largest n (one wave's lanes, one 64-bit mask)
 TL_FLAG_LK_SMALL = 1 << 9  # tl_lk: the LDS-resident single-workgroup form wherever it fits
 TL_FLAG_COUNT_WORK = 1 << 8  # the LDS 2-opt kernel also counts the work of its cascade (stats words 5..8); ~8 % slower
 TL_DM_PACKED_LOWER, TL_DM_FULL = 0, 1
@@ -79,6 +80,7 @@ SYMBOLS = [
     "tl_hill_draw",
     "tl_fourier_curve", "tl_fourier_curve_batch", "tl_fourier_curve_work_bytes", "tl_fourier_curve_plan",
     "tl_fourier_basis", "tl_fourier_init", "tl_fourier_nearest", "tl_fourier_selftest_search",
+    "tl_branch_and_bound", "tl_branch_and_bound_host", "tl_branch_and_bound_plan",
 ]
 
 
@@ -138,6 +140,22 @@ class TlFourierOpts(C.Structure):
     gradient terms are formed at once, the steps of one launch, the lanes of a workgroup"""
     _fields_ = [("k_max", C.c_uint32), ("m", C.c_uint32), ("epochs", C.c_uint32), ("chunk", C.c_uint32), ("lam", C.c_double),
                 ("lambda_decay", C.c_double), ("lr", C.c_double), ("span_steps", C.c_uint32), ("threads", C.c_uint32)]
+
+
+class TlBnbOpts(C.Structure):
+    """tl_bnb_opts: the start position, K (0: exact), the budgets (0: none) and the launch parameters (0: the plan's)"""
+    _fields_ = [("start", C.c_uint32), ("n_nearest", C.c_uint32), ("max_nodes", C.c_uint64), ("time_limit_ms", C.c_uint32),
+                ("nodes_per_launch", C.c_uint32), ("frontier_depth", C.c_uint32), ("workgroups", C.c_uint32)]
+
+
+class TlBnbStats(C.Structure):
+    """tl_bnb_stats"""
+    _fields_ = [("nodes", C.c_uint64), ("leaves", C.c_uint64), ("launches", C.c_uint64), ("queue_start", C.c_uint64), ("queue_end", C.c_uint64),
+                ("wave_launches", C.c_uint64), ("idle_wave_launches", C.c_uint64), ("kernel_ms", C.c_double), ("max_launch_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 # tl_lk_progress_fn: void (*)(void *user, const uint32_t *best_pos, uint32_t n, float best_dist)
@@ -366,5 +384,9 @@ def load():
     L.tl_fourier_init.argtypes = [vp, u32, u32, vp]
     L.tl_fourier_nearest.argtypes = [vp, u32, vp, u32, vp]
     L.tl_fourier_selftest_search.argtypes = [vp, vp, u32, vp, u32, i32, vp]
+    bo, bs = C.POINTER(TlBnbOpts), C.POINTER(TlBnbStats)
+    L.tl_branch_and_bound.argtypes = [vp, vp, vp, u32, vp, bo, vp, f32p, C.POINTER(u32), C.POINTER(u32), bs]
+    L.tl_branch_and_bound_host.argtypes = [vp, vp, u32, vp, bo, vp, f32p, C.POINTER(u32), C.POINTER(u32), bs]
+    L.tl_branch_and_bound_plan.argtypes = [u32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(u32), C.POINTER(u32)]
     _lib = L
     return L

@@ -829,4 +829,44 @@ hipError_t launch_bhk_init(const BhkWs &w, const float2 *xy, const float *dm, ui
 hipError_t launch_bhk_layer(const BhkWs &w, uint32_t n, uint32_t p, uint32_t count, int cus, hipStream_t s);
 hipError_t launch_bhk_walk(const BhkWs &w, uint32_t n, bool exact, uint32_t *out_pos, hipStream_t s);
 
+// branch_and_bound.hip — the depth-first branch and bound, 4 <= n <= TL_BNB_MAX_N: a wave per subtree, a lane per
+// city and per level of the search, a bounded number of nodes per launch.  The host (tl_api_bnb.hip) owns the queue and the splits.
+constexpr int kBnbThreads = 256;                   // 4 waves share a workgroup's copy of the matrix
+constexpr uint32_t kBnbWavesPerGroup = kBnbThreads / 64;
+struct BnbItem {        // a subtree: the prefix path[0..depth-1], 1 <= depth <= n - 1
+    uint8_t path[64];
+    uint32_t depth, pad;
+};
+struct BnbWaveHdr {     // a wave's search between launches
+    uint32_t active;    // 0: no subtree
+    uint32_t k;         // the level whose untried children are next: the prefix path[0..k-1] stands
+    uint32_t base;      // the depth of the subtree's root: the subtree is done when level `base` has no child left
+    uint32_t rec_has, rec_bits;  // the wave's record: a leaf was kept, the bits of its length
+    uint32_t pad[3];
+};
+struct BnbCtrl {
+    uint32_t ub_bits;   // the shared upper bound: the bits of a non-negative f32, lowered with atomicMin
+    uint32_t ticket;    // the next queue item
+    uint32_t queue_len, pad;
+    unsigned long long nodes, leaves, idle;  // summed over every launch; idle: waves that ended a launch with no subtree and no item
+};
+struct BnbWs {
+    float *D;           // [64][64] the distances, +0.0 on the diagonal and outside the instance
+    uint64_t *nk;       // [64] the candidate masks N_K(c) (every position where K does not restrict)
+    BnbCtrl *ctrl;
+    BnbItem *queue;     // [queue_cap]
+    BnbWaveHdr *hdr;    // [waves]
+    // per wave and lane l: level l of the search
+    uint32_t *path;     // [waves][64] the position placed at level l
+    uint64_t *untried;  // [waves][64] the children of the prefix path[0..l-1] not yet tried
+    double *cost;       // [waves][64] the f64 sum of the edges of path[0..l]
+    double *mst;        // [waves][64] the spanning tree's weight at the prefix path[0..l-1]
+    uint32_t *rec;      // [waves][64] the recorded tour
+};
+size_t bnb_ws_bytes(uint32_t waves, uint32_t queue_cap);
+BnbWs bnb_ws_layout(void *ws, uint32_t waves, uint32_t queue_cap);
+// one launch: every wave takes at most `slice` nodes and leaves, then stores its search.  factor: the prune's 1 + (n + 1) 2^-23
+hipError_t launch_bnb(const BnbWs &w, uint32_t n, uint32_t start, uint32_t slice, uint32_t workgroups, uint32_t ub0_bits, bool has_start,
+                      double factor, hipStream_t s);
+
 }  // namespace tl

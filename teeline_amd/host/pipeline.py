@@ -16,7 +16,7 @@ SOLVER_NAMES = {"nn": "nearest_neighbor", "nearest_neighbor": "nearest_neighbor"
                 "simulated_annealing": "simulated_annealing", "tabu_search": "tabu_search",
                 "genetic_algorithm": "genetic_algorithm", "ant_colony": "ant_colony", "particle_swarm": "particle_swarm", "cuckoo_search": "cuckoo_search",
                 "flower_pollination": "flower_pollination", "gravitational_search": "gravitational_search", "kohonen_som": "kohonen_som",
-                "hill_climb": "hill_climb", "fourier_curve": "fourier_curve"}  # (the stochastic hill climb, DESIGN.md §4.25, goes by `hill_climb`: `stochastic_hill` and `hill` stay unknown; the aliases `sa`, `tabu`, `ga`, `aco`, `pso`, `cs`, `fpa`, `gsa`, `som` and `kohonen` stay refused: below)
+                "hill_climb": "hill_climb", "fourier_curve": "fourier_curve", "branch_and_bound": "branch_and_bound"}  # (the branch and bound, DESIGN.md §4.27, goes by `branch_and_bound`: the reference's `branch_bound` stays unknown; the stochastic hill climb, DESIGN.md §4.25, goes by `hill_climb`: `stochastic_hill` and `hill` stay unknown; the aliases `sa`, `tabu`, `ga`, `aco`, `pso`, `cs`, `fpa`, `gsa`, `som` and `kohonen` stay refused: below)
 PRESETS = {"fast": ["nn", "2opt"], "classic": ["nn", "2opt", "simulated_annealing"], "thorough": ["nn", "3opt", "simulated_annealing"]}  # resolve_preset (main.rs:354-369)
 # The reference's short alias `sa` is NOT taken: callers of earlier versions rely on `sa` being refused (it named the reference's unseeded,
 # unreproducible chain), and this build's annealing is a seeded chain of its own specification.  Ask for it by its long name.
@@ -31,7 +31,7 @@ REFUSED_HINTS = {"sa": "the seeded annealing of this build is", "tabu": "the see
                  "som": "the seeded Kohonen map of this build is", "kohonen": "the seeded Kohonen map of this build is",
                  "fourier": "the Fourier-curve solver of this build is"}
 AUTO_EXPAND_WITH_SHUFFLE = {"simulated_annealing", "genetic_algorithm", "ant_colony", "particle_swarm", "cuckoo_search", "flower_pollination", "gravitational_search", "hill_climb"}  # mod.rs:144-157: `solve simulated_annealing` alone is shuffle -> simulated_annealing (ant_colony: mod.rs:2158, cuckoo_search: mod.rs:2154, flower_pollination: mod.rs:2155)
-AUTO_EXPAND_WITH_NN = {"two_opt", "three_opt", "or_opt", "lin_kernighan", "tabu_search"}  # mod.rs:129-139 (greedy_edge, savings and christofides are seeds: `solve gec` / `solve sav` / `solve chr` run alone; so does the exact solver `solve bhk`, mod.rs:2137, and so does `solve kohonen_som`: the map is in neither list and ignores a start tour; `solve fourier_curve` likewise)
+AUTO_EXPAND_WITH_NN = {"two_opt", "three_opt", "or_opt", "lin_kernighan", "tabu_search", "branch_and_bound"}  # mod.rs:127-139 (the branch and bound takes the seed's length as its first upper bound; greedy_edge, savings and christofides are seeds: `solve gec` / `solve sav` / `solve chr` run alone; so does the exact solver `solve bhk`, mod.rs:2137, and so does `solve kohonen_som`: the map is in neither list and ignores a start tour; `solve fourier_curve` likewise)
 
 
 def _unknown(name):
@@ -96,13 +96,14 @@ class StageOutcome:
         self.name, self.solution, self.duration_ms = name, solution, duration_ms
 
 
-def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact_walk=False, init_tour=None, sa_chains=1, tabu_chains=1, ga_runs=1, aco_runs=1, pso_runs=1, cs_runs=1, fpa_runs=1, gsa_runs=1, som_runs=1, hill_chains=1, fourier_jobs=None):
-    """steps: iterable of solver names ("nn", "gec", "sav", "chr", "bhk", "2opt", "3opt", "or_opt", "lk", "simulated_annealing", "tabu_search", "genetic_algorithm", "ant_colony", "particle_swarm", "cuckoo_search", "flower_pollination", "gravitational_search", "kohonen_som", "hill_climb", "fourier_curve", "shuffle"); opts: {name: options} (optional).
+def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact_walk=False, init_tour=None, sa_chains=1, tabu_chains=1, ga_runs=1, aco_runs=1, pso_runs=1, cs_runs=1, fpa_runs=1, gsa_runs=1, som_runs=1, hill_chains=1, fourier_jobs=None, bnb_max_nodes=0, bnb_time_limit_ms=0):
+    """steps: iterable of solver names ("nn", "gec", "sav", "chr", "bhk", "2opt", "3opt", "or_opt", "lk", "simulated_annealing", "tabu_search", "genetic_algorithm", "ant_colony", "particle_swarm", "cuckoo_search", "flower_pollination", "gravitational_search", "kohonen_som", "hill_climb", "fourier_curve", "branch_and_bound", "shuffle"); opts: {name: options} (optional).
     A `simulated_annealing` stage draws from the stream of lk_seed (the pipeline's one seed) and runs sa_chains chains, keeping the best;
     a `tabu_search` stage likewise, with tabu_chains chains, a `genetic_algorithm` stage with ga_runs runs an `ant_colony` stage with aco_runs runs a `particle_swarm` stage with pso_runs runs a `cuckoo_search` stage with cs_runs runs a `flower_pollination` stage with fpa_runs runs and a `gravitational_search` stage with gsa_runs runs.  A `kohonen_som` stage runs som_runs runs and ignores its seed tour.  A `hill_climb` stage runs hill_chains chains.  A `fourier_curve` stage ignores its seed tour too; fourier_jobs, a list of FourierOptions, makes it a batch of which the best is kept.
+    A `branch_and_bound` stage takes the previous stage's tour as its start tour and is exact unless opts names a HeuristicOptions for it (then its n_nearest restricts the candidates); bnb_max_nodes / bnb_time_limit_ms are its budgets (0: none).
     exact_walk: a `bhk` stage reads its route back by exact equality (bellman_karp.solve) instead of the reference's tolerance walk,
     whose result can fail validate_tour below.  init_tour: the seed of the first stage (city ids; default: that stage's own seeding)."""
-    from . import (HeuristicOptions, LKOptions, ant_colony, bellman_karp, christofides, cuckoo_search, flower_pollination, genetic_algorithm, gravitational_search, fourier_curve, greedy_edge, hill_climb, kohonen_som, lin_kernighan, nearest_neighbor, or_opt, particle_swarm, savings, simulated_annealing,
+    from . import (HeuristicOptions, LKOptions, ant_colony, bellman_karp, branch_and_bound, christofides, cuckoo_search, flower_pollination, genetic_algorithm, gravitational_search, fourier_curve, greedy_edge, hill_climb, kohonen_som, lin_kernighan, nearest_neighbor, or_opt, particle_swarm, savings, simulated_annealing,
                    tabu_search, three_opt, two_opt, validate_tour)
     mods = {"nearest_neighbor": nearest_neighbor, "two_opt": two_opt, "three_opt": three_opt, "or_opt": or_opt,
             "lin_kernighan": lin_kernighan, "greedy_edge": greedy_edge, "savings": savings, "christofides": christofides,
@@ -147,6 +148,8 @@ def run_pipeline_stages(problem, steps, opts=None, *, ctx=None, lk_seed=1, exact
                 sol = fourier_curve.solve_many(problem, list(fourier_jobs), ctx=ctx)
             else:
                 sol = fourier_curve.solve(problem, opts.get(step) or fourier_curve.FourierOptions(), None, init, ctx=ctx)
+        elif name == "branch_and_bound":
+            sol = branch_and_bound.solve(problem, opts.get(step), None, init, ctx=ctx, max_nodes=bnb_max_nodes, time_limit_ms=bnb_time_limit_ms)
         elif name == "bellman_karp":
             sol = mods[name].solve(problem, opts.get(step) or HeuristicOptions(), None, init, ctx=ctx, exact_walk=exact_walk)
         else:

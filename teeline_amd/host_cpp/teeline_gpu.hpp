@@ -1586,8 +1586,58 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const FourierOpti
 }
 }  // namespace fourier_curve
 
+namespace branch_and_bound {  // the depth-first branch and bound of DESIGN.md §4.27 (the bound of branch_bound.rs:240-268, a result of this project's specification)
+struct BnbOptions {
+    size_t n_nearest = 0;  // K; 0 or >= n: the exact solver.  0 < K < n restricts a city's successors to its K nearest (itself counted): a heuristic
+    uint64_t max_nodes = 0;  // budgets, checked between launches (0: none)
+    uint32_t time_limit_ms = 0;
+    uint32_t nodes_per_launch = 0, frontier_depth = 0, workgroups = 0;  // 0: the plan's; a proved result does not depend on them
+};
+struct BnbOutcome {
+    bool proved = false, improved = false;
+    tl_bnb_stats stats{};
+};
+// The search starts at the smallest id (route.sort(), :35).  init_tour: the start tour, which comes back as given unless a strictly
+// shorter tour exists (:84-90).  progress_tx gets the sorted route, the result and Done; the reference's per-move messages are not
+// reproduced.  Solution::stats: sweeps = launches, candidates = nodes, moves = leaves.
+inline Solution solve(Context &ctx, const TspProblem &problem, const BnbOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
+                      BnbOutcome *outcome = nullptr)
+{
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size();
+    std::vector<uint32_t> init, out(n);
+    if (init_tour) init = problem.positions_of(*init_tour);
+    uint32_t start = 0;
+    for (uint32_t p = 1; p < n; ++p)
+        if (problem.cities[p].id < problem.cities[start].id) start = p;
+    const tl_bnb_opts o{start, (uint32_t)std::min<size_t>(opts.n_nearest, 0xFFFFFFFFu), opts.max_nodes, opts.time_limit_ms, opts.nodes_per_launch, opts.frontier_depth,
+                        opts.workgroups};
+    float cost = 0.f;
+    uint32_t proved = 0, improved = 0;
+    tl_bnb_stats bs{};
+    ctx.check(tl_branch_and_bound(ctx.get(), xy.data(), problem.explicit_packed(), n, init_tour ? init.data() : nullptr, &o, out.data(), &cost, &proved, &improved, &bs));
+    if (outcome) *outcome = BnbOutcome{proved != 0, improved != 0, bs};
+    tl_stats st{};
+    st.sweeps = bs.launches;
+    st.candidates = bs.nodes;
+    st.moves = bs.leaves;
+    st.kernel_ms = bs.kernel_ms;
+    st.total_ms = bs.total_ms;
+    Solution s = detail::finish(problem, out, cost, st, nullptr);
+    if (progress_tx && *progress_tx) {
+        std::vector<size_t> sorted_ids;
+        for (auto &c : problem.cities) sorted_ids.push_back(c.id);
+        std::sort(sorted_ids.begin(), sorted_ids.end());
+        (*progress_tx)(ProgressKind::PathUpdate, sorted_ids, 0.0f);
+        (*progress_tx)(ProgressKind::PathUpdate, s.route_, cost);
+        (*progress_tx)(ProgressKind::Done, s.route_, cost);
+    }
+    return s;
+}
+}  // namespace branch_and_bound
+
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
-enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch, FlowerPollination, GravitationalSearch, KohonenSom, HillClimb, FourierCurve };
+enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch, FlowerPollination, GravitationalSearch, KohonenSom, HillClimb, FourierCurve, BranchAndBound };
 
 inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
 {
@@ -1614,6 +1664,7 @@ inline bool solver_from_str(std::string s, Solvers &out, std::string &why)
     else if (s == "kohonen_som") out = Solvers::KohonenSom;  // (the aliases `som` and `kohonen` likewise)
     else if (s == "hill_climb") out = Solvers::HillClimb;  // (the reference's `stochastic_hill` stays refused, below; `hill` stays unknown)
     else if (s == "fourier_curve") out = Solvers::FourierCurve;  // (the reference's `fourier` stays refused, below)
+    else if (s == "branch_and_bound") out = Solvers::BranchAndBound;  // (the reference's `branch_bound` stays refused, below: its result depends on a HashSet's order)
     else {
         static const char *cpu_only[] = {"aco", "branch_bound",
                                          "cs", "fpa", "fourier", "ga", "gsa",
@@ -1663,6 +1714,7 @@ inline const char *solver_name(Solvers s)
         case Solvers::KohonenSom: return "kohonen_som";
         case Solvers::HillClimb: return "hill_climb";
         case Solvers::FourierCurve: return "fourier_curve";
+        case Solvers::BranchAndBound: return "branch_and_bound";
         default: return "shuffle";
     }
 }
@@ -1690,6 +1742,7 @@ struct StageOptions {
     uint32_t hill_chains = 1;  // a hill_climb stage runs this many chains and keeps the best
     fourier_curve::FourierOptions fourier;
     std::vector<fourier_curve::FourierOptions> fourier_jobs;  // not empty: a fourier_curve stage runs these option sets at once and keeps the best
+    branch_and_bound::BnbOptions bnb;  // a branch_and_bound stage: exact unless bnb.n_nearest restricts it
     uint64_t seed = 1;  // LK kicks, shuffle, SA, tabu and GA draws
     const ProgressFn *progress = nullptr;  // handed to every stage's solve() (the reference's CLI passes None; teeline-qt a sender)
 };
@@ -1764,6 +1817,14 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             case Solvers::FourierCurve:
                 sol = o.fourier_jobs.empty() ? fourier_curve::solve(ctx, problem, o.fourier, o.progress, init) : fourier_curve::solve_many(ctx, problem, o.fourier_jobs);
                 break;
+            case Solvers::BranchAndBound: {
+                branch_and_bound::BnbOutcome bo;
+                sol = branch_and_bound::solve(ctx, problem, o.bnb, o.progress, init, &bo);
+                if (!bo.proved)
+                    std::fprintf(stderr, "branch_and_bound: proved=0 (the budget ended the search after %llu nodes; the tour is the best found, not a proved optimum)\n",
+                                 (unsigned long long)bo.stats.nodes);
+                break;
+            }
         }
         const auto t1 = std::chrono::steady_clock::now();
         const uint64_t ms = (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();

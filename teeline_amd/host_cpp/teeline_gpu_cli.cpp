@@ -41,6 +41,10 @@
 //               (0.05), --lambda-decay (0.5), --lr (0.05), --epochs (400): FourierOptions, mod.rs:1341-1384; --lambda and --lr take
 //               comma lists whose product runs as one batch, the best kept; no seed (the solver draws nothing); `solve fourier_curve`
 //               runs alone and ignores a start tour
+//     exact   : branch_and_bound (the reference's `branch_bound` stays refused) is the depth-first branch and bound to 64 cities,
+//               exact unless --n-nearest is given explicitly (a departure: the reference's default of 3 makes its default run a
+//               heuristic); --max-nodes N and --time-limit-ms T are budgets, and a search they end says `proved=0` on stderr;
+//               `solve branch_and_bound` alone is pipeline(nn, branch_and_bound) (mod.rs:127-135)
 //     solve   : 2opt / 3opt / or_opt / lk auto-expand to pipeline(nn, solver) unless --no-seed (main.rs:387-397, mod.rs:129-139);
 //               gec (greedy_edge), sav (savings) and chr (christofides) are constructions and run alone; so does bhk (bellman_karp),
 //               the exact solver (n <= 26, mod.rs:2137) — as a later pipeline stage it ignores its seed
@@ -79,13 +83,14 @@ struct Args {
 {
     if (why) std::fprintf(stderr, "error: %s\n", why);
     std::fprintf(stderr,
-                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|genetic_algorithm|ant_colony|particle_swarm|cuckoo_search|flower_pollination|gravitational_search|kohonen_som|hill_climb|fourier_curve|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
+                 "usage: teeline-gpu solve <nn|gec|sav|chr|bhk|2opt|3opt|or_opt|lk|simulated_annealing|tabu_search|genetic_algorithm|ant_colony|particle_swarm|cuckoo_search|flower_pollination|gravitational_search|kohonen_som|hill_climb|fourier_curve|branch_and_bound|shuffle|fast|classic|thorough> [-i FILE] [--no-seed] [--output-format text|json]\n"
                  "                         [--optimal-tour FILE] [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P]\n"
                  "                         [--n_nearest K] [--max-depth D] [--seed S] [--best-sweep] [--device N] [--stats]\n"
                  "                         [--progress-digest] [--exact-walk]\n"
                  "                         [--cooling-rate C] [--min-temperature LO] [--max-temperature HI] [--chains K] [--tabu-chains K]\n"
                  "                         [--mutation-probability P] [--n-elite N] [--ga-runs K]\n"
                  "                         [--alpha A] [--beta B] [--evaporation-rate R] [--num-ants N] [--runs K]\n"
+                 "                         [--max-nodes N] [--time-limit-ms T]\n"
                  "       teeline-gpu pipeline --steps=nn,2opt,... | --steps=greedy_edge,2opt,... | --steps=savings,2opt,... | --steps=christofides,lk,... [-i FILE] [options as above]\n"
                  "       teeline-gpu solvers [--short]\n");
     std::exit(2);  // clap's usage-error exit code
@@ -153,7 +158,9 @@ Args parse(int argc, char **argv)
         else if (s == "--runs") a.opt.aco_runs = a.opt.pso_runs = a.opt.cs_runs = a.opt.fpa_runs = a.opt.gsa_runs = a.opt.som_runs = a.opt.hill_chains = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--chains") a.opt.sa_chains = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--platoo_epochs" || s == "--platoo-epochs") a.opt.heuristic.platoo_epochs = a.opt.lk.heuristic.platoo_epochs = parse_usize(s, val());
-        else if (s == "--n_nearest" || s == "--n-nearest") a.opt.heuristic.n_nearest = a.opt.lk.heuristic.n_nearest = parse_usize(s, val());
+        else if (s == "--n_nearest" || s == "--n-nearest") a.opt.heuristic.n_nearest = a.opt.lk.heuristic.n_nearest = a.opt.bnb.n_nearest = parse_usize(s, val());  // (branch_and_bound: only an explicit K restricts it)
+        else if (s == "--max-nodes" || s == "--max_nodes") a.opt.bnb.max_nodes = parse_usize(s, val());
+        else if (s == "--time-limit-ms" || s == "--time_limit_ms") a.opt.bnb.time_limit_ms = (uint32_t)std::min<size_t>(parse_usize(s, val()), 0xFFFFFFFFu);
         else if (s == "--max-depth") a.opt.lk.max_depth = parse_usize(s, val());
         else if (s == "-v" || s == "--verbose") a.opt.heuristic.verbose = true;
         else if (s == "--seed") a.opt.seed = std::stoull(val());
@@ -320,7 +327,7 @@ int run(int argc, char **argv)
                     return why == "unknown solver" ? 2 : 1;
                 }
                 // auto_expand_with_nn (mod.rs:129-139): deterministic local searches are seeded with a nearest-neighbour stage
-                const bool expand = s == Solvers::TwoOpt || s == Solvers::ThreeOpt || s == Solvers::LinKernighan || s == Solvers::OrOpt || s == Solvers::TabuSearch;
+                const bool expand = s == Solvers::TwoOpt || s == Solvers::ThreeOpt || s == Solvers::LinKernighan || s == Solvers::OrOpt || s == Solvers::TabuSearch || s == Solvers::BranchAndBound;
                 if (!a.no_seed && expand) stages = {Solvers::NearestNeighbor, s};
                 else if (!a.no_seed && (s == Solvers::SimulatedAnnealing || s == Solvers::GeneticAlgorithm || s == Solvers::AntColony || s == Solvers::ParticleSwarm || s == Solvers::CuckooSearch || s == Solvers::FlowerPollination || s == Solvers::GravitationalSearch || s == Solvers::HillClimb)) stages = {Solvers::RandomShuffle, s};  // mod.rs:144-157
                 else stages = {s};
