@@ -26,7 +26,7 @@
 //                    ant, so each cell's adds happen in the reference's order, without atomics); W = aco_pow(tau, alpha) eta.
 //                    With `pre` it is the deposit of the initial tour before epoch 0: one ant (or none), no evaporation.
 #include "aco_spec.h"
-#include "chain_tour.h"
+#include "swarm_tour.h"
 #include "tl_kernels.h"
 
 #pragma clang fp contract(off)
@@ -487,31 +487,22 @@ uint32_t ant_colony_max_n(int lds_budget)
 
 int ant_colony_threads() { return (int)kAcoThreads; }
 
-template <class K, class... Args>
-static hipError_t aco_launch(K kern, dim3 grid, int threads, size_t lds, hipStream_t s, Args... args)
-{
-    hipError_t e = allow_max_lds(reinterpret_cast<const void *>(kern));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, args...);
-    return hipGetLastError();
-}
-
 hipError_t launch_aco_init(const AcoArgs &A, uint32_t runs, hipStream_t s)
 {
-    hipError_t e = aco_launch(A.dm_full ? k_aco_init<true> : k_aco_init<false>, dim3(runs), 256, (size_t)A.n * 6 + 16, s, A);
+    hipError_t e = launch_max_lds(A.dm_full ? k_aco_init<true> : k_aco_init<false>, dim3(runs), 256, (size_t)A.n * 6 + 16, s, A);
     if (e != hipSuccess) return e;
-    return aco_launch(A.dm_full ? k_aco_fill<true> : k_aco_fill<false>, dim3(A.n, runs), 256, 0, s, A);
+    return launch_max_lds(A.dm_full ? k_aco_fill<true> : k_aco_fill<false>, dim3(A.n, runs), 256, 0, s, A);
 }
 
 hipError_t launch_aco_construct(const AcoArgs &A, uint32_t runs, hipStream_t s)
 {
-    return aco_launch(A.dm_full ? k_aco_construct<true> : k_aco_construct<false>, dim3((A.num_ants + 63u) / 64u, runs), (int)kAcoThreads, ant_colony_lds_bytes(A.n),
+    return launch_max_lds(A.dm_full ? k_aco_construct<true> : k_aco_construct<false>, dim3((A.num_ants + 63u) / 64u, runs), (int)kAcoThreads, ant_colony_lds_bytes(A.n),
                       s, A);
 }
 
 hipError_t launch_aco_best(const AcoArgs &A, uint32_t runs, hipStream_t s)
 {
-    return aco_launch(k_aco_best, dim3(runs), 256, 64 + (size_t)A.num_ants * 2 + 16, s, A);
+    return launch_max_lds(k_aco_best, dim3(runs), 256, 64 + (size_t)A.num_ants * 2 + 16, s, A);
 }
 
 hipError_t launch_aco_update(const AcoArgs &A, uint32_t runs, int lds_budget, hipStream_t s)
@@ -519,12 +510,12 @@ hipError_t launch_aco_update(const AcoArgs &A, uint32_t runs, int lds_budget, hi
     const size_t budget = (size_t)lds_budget < (48u << 10) ? (size_t)lds_budget : (48u << 10);
     size_t rows = budget / ((size_t)A.n * 4);
     rows = rows < 1 ? 1 : rows > 16 ? 16 : rows;  // (one row is 4 n bytes <= the construct kernel's 12 n: it fits wherever that does)
-    return aco_launch(k_aco_update, dim3((uint32_t)((A.n + rows - 1) / rows), runs), 256, rows * (size_t)A.n * 4, s, A, (uint32_t)rows);
+    return launch_max_lds(k_aco_update, dim3((uint32_t)((A.n + rows - 1) / rows), runs), 256, rows * (size_t)A.n * 4, s, A, (uint32_t)rows);
 }
 
 hipError_t launch_aco_selftest_select(const float *weights, const float *eta, const uint32_t *visited, uint32_t n, float r1, float r2, uint32_t *out, hipStream_t s)
 {
-    return aco_launch(k_aco_selftest_select, dim3(1), (int)kAcoThreads, ant_colony_lds_bytes(n), s, weights, eta, visited, n, r1, r2, out);
+    return launch_max_lds(k_aco_selftest_select, dim3(1), (int)kAcoThreads, ant_colony_lds_bytes(n), s, weights, eta, visited, n, r1, r2, out);
 }
 
 }  // namespace tl

@@ -1,5 +1,6 @@
 // chain_tour.h — what the kernels of the seeded solvers share on the device (internal to libteeline_gpu): the distance between two
-// cities (sim_anneal.hip, tabu_search.hip, hill_climb.hip, genetic.hip) and the minimum over a wave (the first three of them).
+// cities (sim_anneal.hip, tabu_search.hip, hill_climb.hip, and through swarm_tour.h genetic.hip and the population solvers) and the
+// minimum over a wave (the first three of them).
 //
 // The resident tour itself — perm | E | S, the costing walk of a reversal and its commit — is NOT in here: sim_anneal.hip,
 // tabu_search.hip and hill_climb.hip each keep their copy.  Folding two into always-inlined helpers gave kernels with the parent's

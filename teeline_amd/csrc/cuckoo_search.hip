@@ -26,7 +26,7 @@
 //
 //   LDS of a workgroup: 576 bytes of header and the commit's "overwritten" bits | pairs[n / 2] u32 | E[n] f32 | old[n], new[n] u16
 //   (10 n bytes).
-#include "chain_tour.h"
+#include "swarm_tour.h"
 #include "cs_spec.h"
 #include "tl_kernels.h"
 
@@ -56,41 +56,6 @@ struct CsLds {
         neu = reinterpret_cast<uint16_t *>(p + pr + wd + sh);
     }
 };
-
-// tour_length's sum (distance_matrix.rs:235-245) of the n edge lengths E[k] = d(route[k], route[k + 1]), E[n - 1] the closing edge:
-// one lane, the reference's order
-__device__ __forceinline__ float cs_sum_edges(const float *E, uint32_t n)
-{
-    if (n < 2u) return 0.0f;
-    float tot = E[n - 1u];
-    uint32_t k = 0;
-#pragma unroll 4
-    for (; k + 4u <= n - 1u; k += 4u) {
-        const float4 v = *reinterpret_cast<const float4 *>(E + k);
-        tot += v.x;
-        tot += v.y;
-        tot += v.z;
-        tot += v.w;
-    }
-    for (; k + 1u < n; ++k) tot += E[k];
-    return tot;
-}
-
-// the tour in L.neu to dst, its edge lengths by all lanes and its cost by one.  Begins behind a barrier (L.neu is whole), ends
-// behind one.
-template <bool DM>
-__device__ void cs_write_and_cost(const CsLds &L, const CityDist<DM> &D, uint32_t n, uint16_t *dst, float *cost)
-{
-    const uint32_t tid = threadIdx.x, nt = blockDim.x;
-    for (uint32_t p = tid; p < n; p += nt) {
-        const uint16_t c = L.neu[p];
-        dst[p] = c;
-        L.E[p] = D(c, L.neu[p + 1u == n ? 0u : p + 1u]);
-    }
-    TL_SYNC();
-    if (tid == 0) *cost = cs_sum_edges(L.E, n);
-    TL_SYNC();
-}
 
 // a Fisher-Yates pass over city order by one lane in L.neu, step j drawing position(u(event0 + j, slot), j + 1).  Ends behind a
 // barrier.
@@ -137,24 +102,8 @@ __device__ void cs_fly(const CsArgs &A, const CsLds &L, const CityDist<DM> &D, u
     for (uint32_t p = tid; p < n; p += nt) L.old[p] = src[p];
     TL_SYNC();
     cs_gather(L, n, k);
-    cs_write_and_cost<DM>(L, D, n, A.fly + idx * n, A.fcost + idx);
+    write_and_cost<DM>(L.neu, L.E, D, n, A.fly + idx * n, A.fcost + idx);
     if (tid == 0) A.fk[idx] = k;
-}
-
-// the row of the improvement log and its route: by every lane
-__device__ void cs_log_improvement(const CsArgs &A, uint32_t k, uint32_t epoch, uint32_t source, float cost, const uint16_t *route)
-{
-    if (A.log && k < A.log_cap && threadIdx.x == 0) {
-        uint32_t *rec = A.log + 4u * (size_t)k;
-        rec[0] = epoch;
-        rec[1] = source;
-        rec[2] = __builtin_bit_cast(uint32_t, cost);
-        rec[3] = A.route_log && k < A.route_cap ? k : 0xFFFFFFFFu;
-    }
-    if (A.route_log && k < A.route_cap) {
-        uint32_t *dst = A.route_log + (size_t)k * A.n;
-        for (uint32_t j = threadIdx.x; j < A.n; j += blockDim.x) dst[j] = route[j];
-    }
 }
 
 struct CsGivenWords {
@@ -180,7 +129,7 @@ __global__ __launch_bounds__(256) void k_cs_init(CsArgs A)
         cs_shuffle(L, n, key, ga_init_event(n, ind, 0u), kGaSlotShuffle);
     }
     const size_t idx = (size_t)run * A.nests + ind;
-    cs_write_and_cost<DM>(L, D, n, A.nest + idx * n, A.cost + idx);
+    write_and_cost<DM>(L.neu, L.E, D, n, A.nest + idx * n, A.cost + idx);
 }
 
 // best of the start: a copy of the FIRST minimum nest (min_by keeps the first of equals)
@@ -210,7 +159,7 @@ __global__ __launch_bounds__(256) void k_cs_first(CsArgs A)
         A.best[(size_t)run * n + k] = src[k];
         if (A.last) A.out_pos[(size_t)run * n + k] = src[k];
     }
-    if (run == 0u) cs_log_improvement(A, 0u, 0xFFFFFFFFu, b, pc[b], src);
+    if (run == 0u) log_improvement(A, 0u, 0xFFFFFFFFu, b, pc[b], src);
 }
 
 template <bool DM>
@@ -230,7 +179,7 @@ __global__ __launch_bounds__(256) void k_cs_fly(CsArgs A)
     if (!cs_abandoned(key, base, A.pa)) return;
     cs_shuffle(L, n, key, base + 1u, kCsSlotReplace);
     const size_t idx = (size_t)run * N + c;
-    cs_write_and_cost<DM>(L, D, n, A.repl + idx * n, A.rcost + idx);
+    write_and_cost<DM>(L.neu, L.E, D, n, A.repl + idx * n, A.rcost + idx);
 }
 
 template <bool DM>
@@ -264,7 +213,7 @@ __global__ __launch_bounds__(256) void k_cs_commit(CsArgs A)
             if (f < best) {
                 for (uint32_t k = tid; k < n; k += nt) bestr[k] = src[k];
                 ++improved;
-                if (run == 0u) cs_log_improvement(A, improved, A.epoch, c, f, src);
+                if (run == 0u) log_improvement(A, improved, A.epoch, c, f, src);
                 best = f;
             }
             TL_SYNC();  // every lane has read cost[t]; nest t is whole before a later flight reads it
@@ -286,7 +235,7 @@ __global__ __launch_bounds__(256) void k_cs_commit(CsArgs A)
         if (rc < best) {
             for (uint32_t k = tid; k < n; k += nt) bestr[k] = src[k];
             ++improved;
-            if (run == 0u) cs_log_improvement(A, improved, A.epoch, N + c, rc, src);
+            if (run == 0u) log_improvement(A, improved, A.epoch, N + c, rc, src);
             best = rc;
         }
         if (tid == 0) cost[c] = rc;
@@ -351,18 +300,9 @@ int cuckoo_search_threads(uint32_t n)
     return t < 64u ? 64 : t > 256u ? 256 : (int)t;
 }
 
-template <class K>
-static hipError_t cs_launch(K kern, dim3 grid, int threads, size_t lds, hipStream_t s, const CsArgs &A)
-{
-    hipError_t e = allow_max_lds(reinterpret_cast<const void *>(kern));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, A);
-    return hipGetLastError();
-}
-
 hipError_t launch_cs_init(const CsArgs &A, uint32_t runs, hipStream_t s)
 {
-    hipError_t e = cs_launch(A.dm_full ? k_cs_init<true> : k_cs_init<false>, dim3(A.nests, runs), cuckoo_search_threads(A.n), cuckoo_search_lds_bytes(A.n), s, A);
+    hipError_t e = launch_max_lds(A.dm_full ? k_cs_init<true> : k_cs_init<false>, dim3(A.nests, runs), cuckoo_search_threads(A.n), cuckoo_search_lds_bytes(A.n), s, A);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_cs_first, dim3(runs), dim3(cuckoo_search_threads(A.n)), 0, s, A);
     return hipGetLastError();
@@ -370,12 +310,12 @@ hipError_t launch_cs_init(const CsArgs &A, uint32_t runs, hipStream_t s)
 
 hipError_t launch_cs_fly(const CsArgs &A, uint32_t runs, hipStream_t s)
 {
-    return cs_launch(A.dm_full ? k_cs_fly<true> : k_cs_fly<false>, dim3(2u * A.nests, runs), cuckoo_search_threads(A.n), cuckoo_search_lds_bytes(A.n), s, A);
+    return launch_max_lds(A.dm_full ? k_cs_fly<true> : k_cs_fly<false>, dim3(2u * A.nests, runs), cuckoo_search_threads(A.n), cuckoo_search_lds_bytes(A.n), s, A);
 }
 
 hipError_t launch_cs_commit(const CsArgs &A, uint32_t runs, hipStream_t s)
 {
-    return cs_launch(A.dm_full ? k_cs_commit<true> : k_cs_commit<false>, dim3(runs), cuckoo_search_threads(A.n), cuckoo_search_lds_bytes(A.n), s, A);
+    return launch_max_lds(A.dm_full ? k_cs_commit<true> : k_cs_commit<false>, dim3(runs), cuckoo_search_threads(A.n), cuckoo_search_lds_bytes(A.n), s, A);
 }
 
 hipError_t launch_cs_selftest_levy(const uint64_t *words, uint32_t count, uint32_t n, uint64_t *out_bits, uint32_t *out_k, uint32_t *out_resamples, hipStream_t s)

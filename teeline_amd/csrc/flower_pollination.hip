@@ -25,7 +25,7 @@
 //
 //   LDS of a workgroup: 768 bytes of header, wave counts and the commit's "accepted" bits | pairs[n] u32 (the sequence; the edge
 //   lengths afterwards) | cur[n], inv[n], pi[n] u16  (10 n bytes).
-#include "chain_tour.h"
+#include "swarm_tour.h"
 #include "fpa_spec.h"
 #include "swap_seq.h"
 #include "tl_kernels.h"
@@ -58,41 +58,6 @@ struct FpaLds {
         pi = reinterpret_cast<uint16_t *>(p + wd + 2 * sh);
     }
 };
-
-// tour_length's sum (distance_matrix.rs:235-245) of the n edge lengths E[k] = d(route[k], route[k + 1]), E[n - 1] the closing edge:
-// one lane, the reference's order
-__device__ __forceinline__ float fpa_sum_edges(const float *E, uint32_t n)
-{
-    if (n < 2u) return 0.0f;
-    float tot = E[n - 1u];
-    uint32_t k = 0;
-#pragma unroll 4
-    for (; k + 4u <= n - 1u; k += 4u) {
-        const float4 v = *reinterpret_cast<const float4 *>(E + k);
-        tot += v.x;
-        tot += v.y;
-        tot += v.z;
-        tot += v.w;
-    }
-    for (; k + 1u < n; ++k) tot += E[k];
-    return tot;
-}
-
-// the tour in L.cur to dst, its edge lengths by all lanes and its cost by one.  Begins behind a barrier (L.cur is whole), ends
-// behind one.
-template <bool DM>
-__device__ void fpa_write_and_cost(const FpaLds &L, const CityDist<DM> &D, uint32_t n, uint16_t *dst, float *cost)
-{
-    const uint32_t tid = threadIdx.x, nt = blockDim.x;
-    for (uint32_t p = tid; p < n; p += nt) {
-        const uint16_t c = L.cur[p];
-        dst[p] = c;
-        L.E[p] = D(c, L.cur[p + 1u == n ? 0u : p + 1u]);
-    }
-    TL_SYNC();
-    if (tid == 0) *cost = fpa_sum_edges(L.E, n);
-    TL_SYNC();
-}
 
 // `flower` into L.cur, the inverse of `source` into L.inv, swap_sequence(source, target) into L.pairs: its length, to every lane.
 // Ends behind a barrier.
@@ -141,24 +106,8 @@ __device__ void fpa_build(const FpaArgs &A, const FpaLds &L, const CityDist<DM> 
     uint32_t m = 0;
     if (len) m = global ? fpa_global_swaps(fpa_levy(key, ev), len) : fpa_local_swaps(fpa_epsilon(key, ev), len);  // (the same on every lane)
     fpa_apply(L, n, m);
-    fpa_write_and_cost<DM>(L, D, n, A.stage + (row + i) * n, A.scost + row + i);
+    write_and_cost<DM>(L.cur, L.E, D, n, A.stage + (row + i) * n, A.scost + row + i);
     if (threadIdx.x == 0) A.slen[row + i] = fpa_length_word(len, m);
-}
-
-// the row of the improvement log and its route: by every lane
-__device__ void fpa_log_improvement(const FpaArgs &A, uint32_t k, uint32_t epoch, uint32_t flower, float cost, const uint16_t *route)
-{
-    if (A.log && k < A.log_cap && threadIdx.x == 0) {
-        uint32_t *rec = A.log + 4u * (size_t)k;
-        rec[0] = epoch;
-        rec[1] = flower;
-        rec[2] = __builtin_bit_cast(uint32_t, cost);
-        rec[3] = A.route_log && k < A.route_cap ? k : 0xFFFFFFFFu;
-    }
-    if (A.route_log && k < A.route_cap) {
-        uint32_t *dst = A.route_log + (size_t)k * A.n;
-        for (uint32_t j = threadIdx.x; j < A.n; j += blockDim.x) dst[j] = route[j];
-    }
 }
 
 }  // namespace
@@ -190,7 +139,7 @@ __global__ __launch_bounds__(256) void k_fpa_init(FpaArgs A)
     }
     TL_SYNC();
     const size_t idx = (size_t)run * A.flowers + ind;
-    fpa_write_and_cost<DM>(L, D, n, A.flower + idx * n, A.cost + idx);
+    write_and_cost<DM>(L.cur, L.E, D, n, A.flower + idx * n, A.cost + idx);
 }
 
 // gbest of the start: a copy of the FIRST minimum flower (min_by keeps the first of equals)
@@ -220,7 +169,7 @@ __global__ __launch_bounds__(256) void k_fpa_first(FpaArgs A)
         A.gbest[(size_t)run * n + k] = src[k];
         if (A.last) A.out_pos[(size_t)run * n + k] = src[k];
     }
-    if (run == 0u) fpa_log_improvement(A, 0u, 0xFFFFFFFFu, b, pc[b], src);
+    if (run == 0u) log_improvement(A, 0u, 0xFFFFFFFFu, b, pc[b], src);
 }
 
 template <bool DM>
@@ -271,7 +220,7 @@ __global__ __launch_bounds__(256) void k_fpa_commit(FpaArgs A)
             if (c < g) {
                 for (uint32_t p = tid; p < n; p += nt) gbest[p] = src[p];
                 ++improved;
-                if (run == 0u) fpa_log_improvement(A, improved, A.epoch, i, c, src);
+                if (run == 0u) log_improvement(A, improved, A.epoch, i, c, src);
                 g = c;
                 changed = true;
             }
@@ -331,18 +280,9 @@ int flower_pollination_threads(uint32_t n)
     return t < 64u ? 64 : t > 256u ? 256 : (int)t;
 }
 
-template <class K>
-static hipError_t fpa_launch(K kern, dim3 grid, int threads, size_t lds, hipStream_t s, const FpaArgs &A)
-{
-    hipError_t e = allow_max_lds(reinterpret_cast<const void *>(kern));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, A);
-    return hipGetLastError();
-}
-
 hipError_t launch_fpa_init(const FpaArgs &A, uint32_t runs, hipStream_t s)
 {
-    hipError_t e = fpa_launch(A.dm_full ? k_fpa_init<true> : k_fpa_init<false>, dim3(A.flowers, runs), flower_pollination_threads(A.n),
+    hipError_t e = launch_max_lds(A.dm_full ? k_fpa_init<true> : k_fpa_init<false>, dim3(A.flowers, runs), flower_pollination_threads(A.n),
                               flower_pollination_lds_bytes(A.n), s, A);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_fpa_first, dim3(runs), dim3(flower_pollination_threads(A.n)), 0, s, A);
@@ -351,13 +291,13 @@ hipError_t launch_fpa_init(const FpaArgs &A, uint32_t runs, hipStream_t s)
 
 hipError_t launch_fpa_move(const FpaArgs &A, uint32_t runs, hipStream_t s)
 {
-    return fpa_launch(A.dm_full ? k_fpa_move<true> : k_fpa_move<false>, dim3(A.flowers, runs), flower_pollination_threads(A.n), flower_pollination_lds_bytes(A.n), s,
+    return launch_max_lds(A.dm_full ? k_fpa_move<true> : k_fpa_move<false>, dim3(A.flowers, runs), flower_pollination_threads(A.n), flower_pollination_lds_bytes(A.n), s,
                       A);
 }
 
 hipError_t launch_fpa_commit(const FpaArgs &A, uint32_t runs, hipStream_t s)
 {
-    return fpa_launch(A.dm_full ? k_fpa_commit<true> : k_fpa_commit<false>, dim3(runs), flower_pollination_threads(A.n), flower_pollination_lds_bytes(A.n), s, A);
+    return launch_max_lds(A.dm_full ? k_fpa_commit<true> : k_fpa_commit<false>, dim3(runs), flower_pollination_threads(A.n), flower_pollination_lds_bytes(A.n), s, A);
 }
 
 hipError_t launch_fpa_selftest_pollinate(const uint16_t *flower, const uint16_t *source, const uint16_t *target, const uint32_t *prefix, uint32_t n, uint32_t count,

@@ -17,7 +17,7 @@
 //               two waves, at once), fitness by IEEE division, and the mutation applied to the stored genotype only.
 //
 //   LDS of a workgroup: 384 bytes of header and wave counts | E1[n], E2[n] f32 | c1[n], c2[n] u16 | fa[n], fb[n] u8 (14 n bytes).
-#include "chain_tour.h"
+#include "swarm_tour.h"
 #include "ga_spec.h"
 #include "tl_kernels.h"
 
@@ -50,25 +50,6 @@ struct GaLds {
         fb = fa + ga_up16(n);
     }
 };
-
-// tour_length's sum (distance_matrix.rs:235-245) of the n edge lengths E[k] = d(route[k], route[k + 1]), E[n - 1] the closing edge:
-// one lane, the reference's order
-__device__ __forceinline__ float ga_sum_edges(const float *E, uint32_t n)
-{
-    if (n < 2u) return 0.0f;
-    float tot = E[n - 1u];
-    uint32_t k = 0;
-#pragma unroll 4
-    for (; k + 4u <= n - 1u; k += 4u) {
-        const float4 v = *reinterpret_cast<const float4 *>(E + k);
-        tot += v.x;
-        tot += v.y;
-        tot += v.z;
-        tot += v.w;
-    }
-    for (; k + 1u < n; ++k) tot += E[k];
-    return tot;
-}
 
 __device__ __forceinline__ float ga_fitness(float len) { return len == 0.0f ? 0.0f : 1.0f / len; }
 
@@ -181,7 +162,7 @@ __global__ __launch_bounds__(256) void k_ga_init(GaArgs A)
         L.E1[k] = D(r[k], r[k + 1u == n ? 0u : k + 1u]);
     }
     TL_SYNC();
-    if (tid == 0) A.fit[0][(size_t)run * n + ind] = ga_fitness(ga_sum_edges(L.E1, n));
+    if (tid == 0) A.fit[0][(size_t)run * n + ind] = ga_fitness(sum_edges(L.E1, n));
 }
 
 // state words of a run: 0 best fitness bits of the population ranked last, 1 generations whose best improved, 2 mutations applied,
@@ -252,7 +233,7 @@ __global__ __launch_bounds__(1024) void k_ga_rank(GaArgs A)
         state[0] = __builtin_bit_cast(uint32_t, bf);
         state[4] = b;
         if (logged || A.last) {
-            const float cost = ga_sum_edges(E, n);
+            const float cost = sum_edges(E, n);
             if (logged) {
                 uint32_t *rec = A.log + 4u * (size_t)(gen - 1u);
                 rec[0] = b;
@@ -318,8 +299,8 @@ __global__ __launch_bounds__(256) void k_ga_breed(GaArgs A)
     }
     TL_SYNC();
     const uint32_t s1 = ne + 2u * p, s2 = s1 + 1u;  // (add, genetic_algorithm.rs:239-243, keeps no more than n; never reached: 2 (n / 2) <= n)
-    if (tid == 0 && s1 < n) dfit[s1] = ga_fitness(ga_sum_edges(L.E1, n));
-    if (tid == 64u && s2 < n) dfit[s2] = ga_fitness(ga_sum_edges(L.E2, n));
+    if (tid == 0 && s1 < n) dfit[s1] = ga_fitness(sum_edges(L.E1, n));
+    if (tid == 64u && s2 < n) dfit[s2] = ga_fitness(sum_edges(L.E2, n));
     // mutate (genetic_algorithm.rs:327-335) on the stored genotype: the fitness above stays
     const uint32_t m1 = L.hdr[4], f1 = L.hdr[5], t1 = L.hdr[6], m2 = L.hdr[7], f2 = L.hdr[8], t2 = L.hdr[9];
     for (uint32_t k = tid; k < n; k += nt) {

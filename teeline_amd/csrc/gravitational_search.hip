@@ -28,7 +28,7 @@
 //
 //   LDS of a workgroup: 1536 bytes (header, wave counts, 256 live pulls, 4 slots of 20 pairs) | E[n] f32 | cur[n], inv[n] u16
 //   (8 n bytes).
-#include "chain_tour.h"
+#include "swarm_tour.h"
 #include "gsa_spec.h"
 #include "tl_kernels.h"
 
@@ -66,39 +66,12 @@ struct GsaLds {
 };
 static_assert((32 + kGsaLiveChunk + kGsaMaxWaves * kGsaMaxPull + kGsaMaxWaves) * 4 <= kGsaFixedBytes, "the fixed part of the LDS holds its tables");
 
-// tour_length's sum (distance_matrix.rs:235-245) of the n edge lengths E[k] = d(route[k], route[k + 1]), E[n - 1] the closing edge:
-// one lane, the reference's order
-__device__ __forceinline__ float gsa_sum_edges(const float *E, uint32_t n)
-{
-    if (n < 2u) return 0.0f;
-    float tot = E[n - 1u];
-    uint32_t k = 0;
-#pragma unroll 4
-    for (; k + 4u <= n - 1u; k += 4u) {
-        const float4 v = *reinterpret_cast<const float4 *>(E + k);
-        tot += v.x;
-        tot += v.y;
-        tot += v.z;
-        tot += v.w;
-    }
-    for (; k + 1u < n; ++k) tot += E[k];
-    return tot;
-}
-
 // the tour in L.cur to dst, its edge lengths by all lanes and its cost by one, to every lane.  Begins behind a barrier (L.cur is
 // whole), ends behind one: dst is whole for every lane of the workgroup.
 template <bool DM>
 __device__ float gsa_write_and_cost(const GsaLds &L, const CityDist<DM> &D, uint32_t n, uint16_t *dst)
 {
-    const uint32_t tid = threadIdx.x, nt = blockDim.x;
-    for (uint32_t p = tid; p < n; p += nt) {
-        const uint16_t c = L.cur[p];
-        dst[p] = c;
-        L.E[p] = D(c, L.cur[p + 1u == n ? 0u : p + 1u]);
-    }
-    TL_SYNC();
-    if (tid == 0) L.hdr[kGsaHdrCost] = __builtin_bit_cast(uint32_t, gsa_sum_edges(L.E, n));
-    TL_SYNC();
+    write_and_cost<DM>(L.cur, L.E, D, n, dst, reinterpret_cast<float *>(L.hdr + kGsaHdrCost));
     return __builtin_bit_cast(float, L.hdr[kGsaHdrCost]);
 }
 
@@ -124,22 +97,6 @@ __device__ uint32_t gsa_pull(const uint16_t *inv, const uint16_t *target, uint32
         cnt += (uint32_t)__popcll(b);
     }
     return cnt < want ? cnt : want;
-}
-
-// the row of the improvement log and its route: by every lane
-__device__ void gsa_log_improvement(const GsaArgs &A, uint32_t k, uint32_t epoch, uint32_t agent, float cost, const uint16_t *route)
-{
-    if (A.log && k < A.log_cap && threadIdx.x == 0) {
-        uint32_t *rec = A.log + 4u * (size_t)k;
-        rec[0] = epoch;
-        rec[1] = agent;
-        rec[2] = __builtin_bit_cast(uint32_t, cost);
-        rec[3] = A.route_log && k < A.route_cap ? k : 0xFFFFFFFFu;
-    }
-    if (A.route_log && k < A.route_cap) {
-        uint32_t *dst = A.route_log + (size_t)k * A.n;
-        for (uint32_t j = threadIdx.x; j < A.n; j += blockDim.x) dst[j] = route[j];
-    }
 }
 
 }  // namespace
@@ -205,7 +162,7 @@ __global__ __launch_bounds__(256) void k_gsa_first(GsaArgs A)
         A.gbest[(size_t)run * n + k] = src[k];
         if (A.last) A.out_pos[(size_t)run * n + k] = src[k];
     }
-    if (run == 0u) gsa_log_improvement(A, 0u, 0xFFFFFFFFu, b, pc[b], src);
+    if (run == 0u) log_improvement(A, 0u, 0xFFFFFFFFu, b, pc[b], src);
 }
 
 template <bool DM>
@@ -338,7 +295,7 @@ __global__ __launch_bounds__(256) void k_gsa_epochs(GsaArgs A)
             if (c < gcost) {
                 for (uint32_t p = tid; p < n; p += nt) gbest[p] = L.cur[p];
                 ++improved;
-                if (run == 0u) gsa_log_improvement(A, improved, e, i, c, pi);
+                if (run == 0u) log_improvement(A, improved, e, i, c, pi);
                 gcost = c;
             }
         }
@@ -394,18 +351,9 @@ int gravitational_search_threads(uint32_t n)
     return t < 64u ? 64 : t > 256u ? 256 : (int)t;
 }
 
-template <class K>
-static hipError_t gsa_launch(K kern, dim3 grid, int threads, size_t lds, hipStream_t s, const GsaArgs &A)
-{
-    hipError_t e = allow_max_lds(reinterpret_cast<const void *>(kern));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, A);
-    return hipGetLastError();
-}
-
 hipError_t launch_gsa_init(const GsaArgs &A, uint32_t runs, hipStream_t s)
 {
-    hipError_t e = gsa_launch(A.dm_full ? k_gsa_init<true> : k_gsa_init<false>, dim3(A.agents, runs), gravitational_search_threads(A.n),
+    hipError_t e = launch_max_lds(A.dm_full ? k_gsa_init<true> : k_gsa_init<false>, dim3(A.agents, runs), gravitational_search_threads(A.n),
                               gravitational_search_lds_bytes(A.n), s, A);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_gsa_first, dim3(runs), dim3(gravitational_search_threads(A.n)), 0, s, A);
@@ -415,7 +363,7 @@ hipError_t launch_gsa_init(const GsaArgs &A, uint32_t runs, hipStream_t s)
 hipError_t launch_gsa_epochs(const GsaArgs &A, uint32_t runs, hipStream_t s)
 {
     // a workgroup of four waves whatever n: the ranking and the pulls are spread over the agents, not over the cities
-    return gsa_launch(A.dm_full ? k_gsa_epochs<true> : k_gsa_epochs<false>, dim3(runs), 256, gravitational_search_lds_bytes(A.n), s, A);
+    return launch_max_lds(A.dm_full ? k_gsa_epochs<true> : k_gsa_epochs<false>, dim3(runs), 256, gravitational_search_lds_bytes(A.n), s, A);
 }
 
 hipError_t launch_gsa_selftest_pull(const uint16_t *from, const uint16_t *to, const uint32_t *want, uint32_t n, uint32_t count, uint32_t *out_pairs,

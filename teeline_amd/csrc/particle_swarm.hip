@@ -22,7 +22,7 @@
 //
 //   LDS of a workgroup: 256 bytes of header and wave counts | la[n], lb[n] u32 (the two sequences; la's block holds the edge
 //   lengths afterwards) | nv[vmax] u32 | pos[n], inv[n], pi[n] u16  (14 n + 4 vmax bytes).
-#include "chain_tour.h"
+#include "swarm_tour.h"
 #include "pso_spec.h"
 #include "swap_seq.h"
 #include "tl_kernels.h"
@@ -56,25 +56,6 @@ struct PsoLds {
         pi = reinterpret_cast<uint16_t *>(p + 2 * wd + vl + 2 * sh);
     }
 };
-
-// tour_length's sum (distance_matrix.rs:235-245) of the n edge lengths E[k] = d(route[k], route[k + 1]), E[n - 1] the closing edge:
-// one lane, the reference's order
-__device__ __forceinline__ float pso_sum_edges(const float *E, uint32_t n)
-{
-    if (n < 2u) return 0.0f;
-    float tot = E[n - 1u];
-    uint32_t k = 0;
-#pragma unroll 4
-    for (; k + 4u <= n - 1u; k += 4u) {
-        const float4 v = *reinterpret_cast<const float4 *>(E + k);
-        tot += v.x;
-        tot += v.y;
-        tot += v.z;
-        tot += v.w;
-    }
-    for (; k + 1u < n; ++k) tot += E[k];
-    return tot;
-}
 
 // One particle step (particle_swarm.rs:82-105) by the whole workgroup: from pos / vel / vlen[src] of particle i, its pbest and the
 // run's gbest as they stand, to pos / vel / vlen[src ^ 1] and cost.  Ends behind a barrier.
@@ -127,26 +108,10 @@ __device__ void pso_step(const PsoArgs &A, const PsoLds &L, const CityDist<DM> &
     }
     TL_SYNC();
     if (tid == 0) {
-        A.cost[idx] = pso_sum_edges(L.E, n);
+        A.cost[idx] = sum_edges(L.E, n);
         A.vlen[A.src ^ 1u][idx] = total;
     }
     TL_SYNC();
-}
-
-// the row of the improvement log and its route: by every lane, between barriers
-__device__ void pso_log_improvement(const PsoArgs &A, uint32_t k, uint32_t epoch, uint32_t particle, float cost, const uint16_t *route)
-{
-    if (A.log && k < A.log_cap && threadIdx.x == 0) {
-        uint32_t *rec = A.log + 4u * (size_t)k;
-        rec[0] = epoch;
-        rec[1] = particle;
-        rec[2] = __builtin_bit_cast(uint32_t, cost);
-        rec[3] = A.route_log && k < A.route_cap ? k : 0xFFFFFFFFu;
-    }
-    if (A.route_log && k < A.route_cap) {
-        uint32_t *dst = A.route_log + (size_t)k * A.n;
-        for (uint32_t j = threadIdx.x; j < A.n; j += blockDim.x) dst[j] = route[j];
-    }
 }
 
 }  // namespace
@@ -187,7 +152,7 @@ __global__ __launch_bounds__(256) void k_pso_init(PsoArgs A)
     }
     TL_SYNC();
     if (tid == 0) {
-        A.pcost[idx] = pso_sum_edges(L.E, n);
+        A.pcost[idx] = sum_edges(L.E, n);
         A.vlen[0][idx] = 0u;
     }
 }
@@ -219,7 +184,7 @@ __global__ __launch_bounds__(256) void k_pso_first(PsoArgs A)
         A.gbest[(size_t)run * n + k] = src[k];
         if (A.last) A.out_pos[(size_t)run * n + k] = src[k];
     }
-    if (run == 0u) pso_log_improvement(A, 0u, 0xFFFFFFFFu, b, pc[b], src);
+    if (run == 0u) log_improvement(A, 0u, 0xFFFFFFFFu, b, pc[b], src);
 }
 
 template <bool DM>
@@ -258,7 +223,7 @@ __global__ __launch_bounds__(256) void k_pso_commit(PsoArgs A)
             if (ug) {
                 for (uint32_t k = tid; k < n; k += nt) gbest[k] = p[k];
                 ++improved;
-                if (run == 0u) pso_log_improvement(A, improved, A.epoch, i, c, p);
+                if (run == 0u) log_improvement(A, improved, A.epoch, i, c, p);
                 g = c;
                 again = true;
             }
@@ -316,18 +281,9 @@ int particle_swarm_threads(uint32_t n)
     return t < 64u ? 64 : t > 256u ? 256 : (int)t;
 }
 
-template <class K>
-static hipError_t pso_launch(K kern, dim3 grid, int threads, size_t lds, hipStream_t s, const PsoArgs &A)
-{
-    hipError_t e = allow_max_lds(reinterpret_cast<const void *>(kern));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, A);
-    return hipGetLastError();
-}
-
 hipError_t launch_pso_init(const PsoArgs &A, uint32_t runs, hipStream_t s)
 {
-    hipError_t e = pso_launch(A.dm_full ? k_pso_init<true> : k_pso_init<false>, dim3(A.particles, runs), particle_swarm_threads(A.n), particle_swarm_lds_bytes(A.n), s, A);
+    hipError_t e = launch_max_lds(A.dm_full ? k_pso_init<true> : k_pso_init<false>, dim3(A.particles, runs), particle_swarm_threads(A.n), particle_swarm_lds_bytes(A.n), s, A);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_pso_first, dim3(runs), dim3(particle_swarm_threads(A.n)), 0, s, A);
     return hipGetLastError();
@@ -335,12 +291,12 @@ hipError_t launch_pso_init(const PsoArgs &A, uint32_t runs, hipStream_t s)
 
 hipError_t launch_pso_move(const PsoArgs &A, uint32_t runs, hipStream_t s)
 {
-    return pso_launch(A.dm_full ? k_pso_move<true> : k_pso_move<false>, dim3(A.particles, runs), particle_swarm_threads(A.n), particle_swarm_lds_bytes(A.n), s, A);
+    return launch_max_lds(A.dm_full ? k_pso_move<true> : k_pso_move<false>, dim3(A.particles, runs), particle_swarm_threads(A.n), particle_swarm_lds_bytes(A.n), s, A);
 }
 
 hipError_t launch_pso_commit(const PsoArgs &A, uint32_t runs, hipStream_t s)
 {
-    return pso_launch(A.dm_full ? k_pso_commit<true> : k_pso_commit<false>, dim3(runs), particle_swarm_threads(A.n), particle_swarm_lds_bytes(A.n), s, A);
+    return launch_max_lds(A.dm_full ? k_pso_commit<true> : k_pso_commit<false>, dim3(runs), particle_swarm_threads(A.n), particle_swarm_lds_bytes(A.n), s, A);
 }
 
 hipError_t launch_pso_selftest_swap_sequence(const uint16_t *from, const uint16_t *to, uint32_t n, uint32_t count, uint32_t *out_pairs, uint32_t *out_len,

@@ -1,14 +1,11 @@
 // tl_api_aco.hip — C ABI, the ant colony solver: tl_ant_colony* (src/tsp/ant_colony.rs:97-252) over ant_colony.hip, the host-only
 // queries of its specification (tl_aco_draw, tl_aco_pow, tl_ant_colony_plan) and the device self-test of the selection.
 #include "aco_spec.h"
-#include "tl_api_chains.h"
+#include "tl_api_swarm.h"
 
 using namespace tl;
 using namespace tlapi;
 
-static constexpr uint32_t kAcoUnassignedFlags = 1u << 31;  // the one bit no flag of include/teeline_gpu.h has
-static constexpr uint64_t kAcoWorkDefault = 8ull << 30;    // the matrices and tables of one launch sequence
-static constexpr uint32_t kAcoMaxRuns = 65535u;            // the run is the grid's y
 static constexpr uint32_t kAcoMaxAnts = 4096u;             // k_aco_best keeps a 16-bit list of the improving ants in LDS
 
 // one run's share of the workspace: tau, eta^beta and W (n^2 f32 each); tour, successor, predecessor (A n u16 each); cost, start, fallbacks
@@ -20,7 +17,7 @@ static inline size_t aco_run_bytes(uint32_t n, uint32_t ants) { return 3 * aco_m
 static uint32_t aco_limit(int lds_bytes)
 {
     uint32_t top = ant_colony_max_n(lds_bytes);
-    while (top > 0u && aco_run_bytes(top, 1u) > kAcoWorkDefault) --top;  // (12 n^2 bytes per run; the LDS layout binds first on 160 KiB)
+    while (top > 0u && aco_run_bytes(top, 1u) > kSwarmWorkDefault) --top;  // (12 n^2 bytes per run; the LDS layout binds first on 160 KiB)
     return top;
 }
 
@@ -36,7 +33,7 @@ extern "C" int tl_ant_colony_plan(uint32_t n, uint32_t num_ants, uint32_t count,
     if (cus < 1 || lds_bytes < 0) return TL_ERR_BADARG;
     const bool fits = n >= 3u && n <= aco_limit(lds_bytes) && num_ants >= 1u && num_ants <= kAcoMaxAnts;
     uint64_t per = fits ? workspace_bytes / aco_run_bytes(n, num_ants) : 0u;
-    if (per > kAcoMaxRuns) per = kAcoMaxRuns;
+    if (per > kSwarmMaxRuns) per = kSwarmMaxRuns;
     if (per_launch) *per_launch = (uint32_t)per;
     if (threads) *threads = per ? ant_colony_threads() : 0;
     if (workspace_needed) *workspace_needed = per ? (uint64_t)(count < per ? count : per) * aco_run_bytes(n, num_ants) : 0u;
@@ -51,153 +48,141 @@ static float aco_host_dist(const float *xy, const float *dm_packed, uint32_t a, 
     return sqrtf(xx + yy);
 }
 
-// What the entries share.  log / route_log: the epochs and improving ants of run 0 of the call (a single run's trace), else nullptr
-static int aco_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
-                   uint32_t first_run, uint32_t count, uint32_t epochs, float alpha, float beta, float rate, uint32_t num_ants, uint64_t seed, uint32_t *out_pos,
-                   float *out_costs, uint32_t *best_index, tl_stats *stats, uint32_t *log, uint32_t log_cap, uint32_t *log_len, uint32_t *route_log,
-                   uint32_t route_cap, uint32_t *route_len)
-{
-    if (log_len) *log_len = 0;
-    if (route_len) *route_len = 0;
-    if (int rc = check_chain_call(c, who, xy, dm_packed, count, out_pos, init_pos, init_count, first_run, "run")) return rc;
-    if (count == 0) return TL_OK;
-    if (c->flags & kAcoUnassignedFlags) return fail(c, TL_ERR_UNSUPPORTED, "%s: the context's flags 0x%x hold a bit no flag has", who, c->flags);
-    // AcoOptions::validate (mod.rs:1115-1153)
-    if (!(alpha >= 0.0f) || alpha > 3.4028234663852886e38f) return fail(c, TL_ERR_BADARG, "%s: alpha must be >= 0 (got %g)", who, (double)alpha);
-    if (!(beta >= 0.0f && beta <= 6.0f)) return fail(c, TL_ERR_BADARG, "%s: beta must be in [0, 6] (got %g)", who, (double)beta);
-    if (!(rate > 0.0f && rate < 1.0f)) return fail(c, TL_ERR_BADARG, "%s: evaporation_rate must be in (0, 1) (got %g)", who, (double)rate);
-    if (num_ants == 0u) return fail(c, TL_ERR_BADARG, "%s: num_ants must be >= 1", who);
-    if (num_ants > kAcoMaxAnts) return fail(c, TL_ERR_UNSUPPORTED, "%s: num_ants=%u exceeds the limit %u", who, num_ants, kAcoMaxAnts);
-    if (n > aco_limit(c->lds_bytes))
-        return fail(c, TL_ERR_UNSUPPORTED, "%s: n=%u exceeds the limit %u (12 bytes of LDS per city)", who, n, aco_limit(c->lds_bytes));
-    if (n >= 3u && (unsigned __int128)epochs * num_ants * n > kAcoEventLimit)
-        return fail(c, TL_ERR_UNSUPPORTED, "%s: epochs x num_ants x n exceeds 2^58 draw events", who);
-    for (uint32_t r = 0; r < init_count; ++r)
-        if (!is_permutation(init_pos + (size_t)r * n, n)) return fail(c, TL_ERR_BADARG, "%s: the initial tour is not a permutation of 0..n-1", who);
-    const auto t0 = std::chrono::steady_clock::now();
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (best_index) *best_index = 0u;
-    if (n <= 2u) {  // ant_colony.rs:109-115: city order, no draw, no device; Solution::from_parts computes its tour_length
-        const float cost = n == 2u ? aco_host_dist(xy, dm_packed, 1, 0) + aco_host_dist(xy, dm_packed, 0, 1) : 0.0f;
-        for (uint32_t r = 0; r < count; ++r) {
-            for (uint32_t k = 0; k < n; ++k) out_pos[(size_t)r * n + k] = k;
-            if (out_costs) out_costs[r] = cost;
-        }
-        c->ev_valid = false;
-        if (stats) stamp_times(c, stats, t0);
+namespace {
+// What the ant colony hands the frame of tl_api_swarm.h.  Its trace is another format than Swarm4's — a row of 3 num_ants words per
+// epoch, route rows of n + 3 words, the two lengths — so the trace's steps are written here, as is the n <= 2 answer.
+struct AcoSolver {
+    using Args = AcoArgs;
+    static constexpr uint32_t kHostN = 2u;
+    uint32_t epochs;
+    float alpha, beta, rate;
+    uint32_t num_ants;
+    // log / route_log: the epochs and improving ants of run 0 of the call (a single run's trace), else nullptr
+    uint32_t *log = nullptr;
+    uint32_t log_cap = 0;
+    uint32_t *log_len = nullptr, *route_log = nullptr;
+    uint32_t route_cap = 0;
+    uint32_t *route_len = nullptr;
+    uint32_t dev_log_cap = 0, dev_route_cap = 0, held = 0;
+    size_t log_bytes = 0, route_bytes = 0;
+
+    uint32_t pop() const { return num_ants; }
+    void trace_reset() const
+    {
+        if (log_len) *log_len = 0;
+        if (route_len) *route_len = 0;
+    }
+    int check(const SwarmCall &k) const
+    {
+        tl_ctx *c = k.c;
+        const char *who = k.who;
+        // AcoOptions::validate (mod.rs:1115-1153)
+        if (!(alpha >= 0.0f) || alpha > 3.4028234663852886e38f) return fail(c, TL_ERR_BADARG, "%s: alpha must be >= 0 (got %g)", who, (double)alpha);
+        if (!(beta >= 0.0f && beta <= 6.0f)) return fail(c, TL_ERR_BADARG, "%s: beta must be in [0, 6] (got %g)", who, (double)beta);
+        if (!(rate > 0.0f && rate < 1.0f)) return fail(c, TL_ERR_BADARG, "%s: evaporation_rate must be in (0, 1) (got %g)", who, (double)rate);
+        if (num_ants == 0u) return fail(c, TL_ERR_BADARG, "%s: num_ants must be >= 1", who);
+        if (num_ants > kAcoMaxAnts) return fail(c, TL_ERR_UNSUPPORTED, "%s: num_ants=%u exceeds the limit %u", who, num_ants, kAcoMaxAnts);
+        if (k.n > aco_limit(c->lds_bytes))
+            return fail(c, TL_ERR_UNSUPPORTED, "%s: n=%u exceeds the limit %u (12 bytes of LDS per city)", who, k.n, aco_limit(c->lds_bytes));
+        if (k.n >= 3u && (unsigned __int128)epochs * num_ants * k.n > kAcoEventLimit)
+            return fail(c, TL_ERR_UNSUPPORTED, "%s: epochs x num_ants x n exceeds 2^58 draw events", who);
         return TL_OK;
     }
-    uint32_t per_launch = 0;
-    tl_ant_colony_plan(n, num_ants, count, c->cus, c->lds_bytes, kAcoWorkDefault, &per_launch, nullptr, nullptr);
-    if (per_launch == 0u)
-        return fail(c, TL_ERR_UNSUPPORTED, "%s: n=%u, num_ants=%u: one run's matrices and tables (%zu bytes) exceed the workspace limit", who, n, num_ants,
-                    aco_run_bytes(n, num_ants));
-
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    const size_t words = (size_t)count * n;
-    const uint32_t held = count < per_launch ? count : per_launch;  // runs whose matrices exist at once
-    const uint32_t dev_log_cap = log ? (log_cap < epochs ? log_cap : epochs) : 0u;
-    const uint32_t dev_route_cap = route_log ? route_cap : 0u;
-    const size_t log_bytes = up256((size_t)(dev_log_cap ? dev_log_cap : 1u) * 3 * num_ants * 4);
-    const size_t route_bytes = up256((size_t)(dev_route_cap ? dev_route_cap : 1u) * (n + 3) * 4);
-    if ((rc = ensure(c, c->init, (size_t)(init_count ? init_count : 1u) * n * 4)) || (rc = ensure(c, c->out_pos, words * 4)) ||
-        (rc = ensure(c, c->out_cost, (size_t)count * 4)) || (rc = ensure(c, c->misc, (size_t)count * 32)) ||
-        (rc = ensure(c, c->work, log_bytes + route_bytes + (size_t)held * aco_run_bytes(n, num_ants))))
-        return rc;
-    AcoArgs A{};
-    if ((rc = upload_instance_full(c, xy, dm_packed, n, &A.xy, &A.dm_full))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->misc.p, 0, (size_t)count * 32, c->stream));
-    if (init_count) {
-        HIPCHK(c, hipMemcpyAsync(c->init.p, init_pos, (size_t)init_count * n * 4, hipMemcpyHostToDevice, c->stream));
-        A.init = (const uint32_t *)c->init.p;
-        A.init_stride = init_count > 1u ? n : 0u;
-    }
-    unsigned char *w = (unsigned char *)c->work.p;
-    A.log = log ? (uint32_t *)w : nullptr;
-    A.log_cap = dev_log_cap;
-    A.route_log = route_log ? (uint32_t *)(w + log_bytes) : nullptr;
-    A.route_cap = dev_route_cap;
-    w += log_bytes + route_bytes;
-    const size_t mb = aco_mat_bytes(n), tb = aco_tab_bytes(n, num_ants), ab = aco_ant_bytes(num_ants);
-    A.tau = (float *)w;
-    A.eta = (float *)(w + (size_t)held * mb);
-    A.w = (float *)(w + 2 * (size_t)held * mb);
-    A.mat_stride = mb / 4;
-    w += 3 * (size_t)held * mb;
-    // (the tables of a run are num_ants x n entries: a run's stride is that product, so they are laid out run after run, unpadded)
-    A.tour = (uint16_t *)w;
-    A.succ = (uint16_t *)(w + (size_t)held * tb);
-    A.pred = (uint16_t *)(w + 2 * (size_t)held * tb);
-    w += 3 * (size_t)held * tb;
-    A.cost = (float *)w;
-    A.start = (uint32_t *)(w + (size_t)held * ab);
-    A.fb = (uint32_t *)(w + 2 * (size_t)held * ab);
-    A.seed = seed;
-    A.n = n;
-    A.num_ants = num_ants;
-    A.alpha = alpha;
-    A.beta = beta;
-    A.rate = rate;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    for (uint32_t b0 = 0; b0 < count; b0 += per_launch) {  // sequences on one stream follow each other: the next takes over the matrices
-        const uint32_t cnt = count - b0 < per_launch ? count - b0 : per_launch;
-        AcoArgs L = A;
-        L.first_run = first_run + b0;
-        if (L.init && L.init_stride) L.init += (size_t)b0 * n;
-        L.out_pos = (uint32_t *)c->out_pos.p + (size_t)b0 * n;
-        L.out_cost = (float *)c->out_cost.p + b0;
-        L.state = (uint32_t *)c->misc.p + 8u * (size_t)b0;
-        if (b0) L.log = L.route_log = nullptr;  // the trace is run 0's
-        HIPCHK(c, launch_aco_init(L, cnt, c->stream));
-        if (epochs == 0u) continue;
-        L.pre = 1u;
-        HIPCHK(c, launch_aco_update(L, cnt, c->lds_bytes, c->stream));
-        L.pre = 0u;
-        for (uint32_t g = 0; g < epochs; ++g) {
-            L.epoch = g;
-            HIPCHK(c, launch_aco_construct(L, cnt, c->stream));
-            HIPCHK(c, launch_aco_best(L, cnt, c->stream));
-            if (g + 1u < epochs) HIPCHK(c, launch_aco_update(L, cnt, c->lds_bytes, c->stream));  // (the last epoch's deposit is read by nobody)
+    // n <= 2 (ant_colony.rs:109-115): city order, no draw, no device; Solution::from_parts computes its tour_length
+    void host_answer(const SwarmCall &k) const
+    {
+        const float cost = k.n == 2u ? aco_host_dist(k.xy, k.dm_packed, 1, 0) + aco_host_dist(k.xy, k.dm_packed, 0, 1) : 0.0f;
+        for (uint32_t r = 0; r < k.count; ++r) {
+            for (uint32_t i = 0; i < k.n; ++i) k.out_pos[(size_t)r * k.n + i] = i;
+            if (k.out_costs) k.out_costs[r] = cost;
         }
     }
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    c->ev_valid = true;
-    std::vector<uint32_t> state;
-    std::vector<float> costs;
-    if ((rc = download_chains(c, count, n, 8u, out_pos, state, costs))) return rc;
-    if (dev_log_cap) HIPCHK(c, hipMemcpyAsync(log, A.log, (size_t)dev_log_cap * 3 * num_ants * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    uint64_t improved = 0, fallbacks = 0;
-    for (uint32_t r = 0; r < count; ++r) {
-        if (out_costs) out_costs[r] = costs[r];
-        improved += state[8u * r + 1u];
-        fallbacks += ((uint64_t)state[8u * r + 5u] << 32) | state[8u * r + 2u];
+    int plan(const SwarmCall &k, uint32_t *per_launch) const
+    {
+        tl_ant_colony_plan(k.n, num_ants, k.count, k.c->cus, k.c->lds_bytes, kSwarmWorkDefault, per_launch, nullptr, nullptr);
+        if (*per_launch == 0u)
+            return fail(k.c, TL_ERR_UNSUPPORTED, "%s: n=%u, num_ants=%u: one run's matrices and tables (%zu bytes) exceed the workspace limit", k.who, k.n,
+                        num_ants, aco_run_bytes(k.n, num_ants));
+        return TL_OK;
     }
-    if (dev_route_cap) {
-        const uint64_t rows = 1ull + state[1];
-        const uint32_t have = (uint32_t)(rows < dev_route_cap ? rows : dev_route_cap);
-        HIPCHK(c, hipMemcpy(route_log, A.route_log, (size_t)have * (n + 3) * 4, hipMemcpyDeviceToHost));
+    size_t layout(const SwarmCall &k, uint32_t held_runs)
+    {
+        held = held_runs;
+        dev_log_cap = log ? (log_cap < epochs ? log_cap : epochs) : 0u;
+        dev_route_cap = route_log ? route_cap : 0u;
+        log_bytes = up256((size_t)(dev_log_cap ? dev_log_cap : 1u) * 3 * num_ants * 4);
+        route_bytes = up256((size_t)(dev_route_cap ? dev_route_cap : 1u) * (k.n + 3) * 4);
+        return log_bytes + route_bytes + (size_t)held * aco_run_bytes(k.n, num_ants);
     }
-    if (route_len) *route_len = 1u + state[1];
-    if (best_index) *best_index = best_chain(costs, count);
-    if (log_len) *log_len = epochs;
-    if (stats) {
-        stats->sweeps = (uint64_t)epochs * count;
-        stats->candidates = (uint64_t)epochs * count * num_ants;
-        stats->moves = improved;
-        stats->reversed = fallbacks;
-        stamp_times(c, stats, t0);
+    void carve(const SwarmCall &k, Args &A, unsigned char *w) const
+    {
+        A.log = log ? (uint32_t *)w : nullptr;
+        A.log_cap = dev_log_cap;
+        A.route_log = route_log ? (uint32_t *)(w + log_bytes) : nullptr;
+        A.route_cap = dev_route_cap;
+        w += log_bytes + route_bytes;
+        const size_t mb = aco_mat_bytes(k.n), tb = aco_tab_bytes(k.n, num_ants), ab = aco_ant_bytes(num_ants);
+        A.tau = (float *)w;
+        A.eta = (float *)(w + (size_t)held * mb);
+        A.w = (float *)(w + 2 * (size_t)held * mb);
+        A.mat_stride = mb / 4;
+        w += 3 * (size_t)held * mb;
+        // (the tables of a run are num_ants x n entries: a run's stride is that product, so they are laid out run after run, unpadded)
+        A.tour = (uint16_t *)w;
+        A.succ = (uint16_t *)(w + (size_t)held * tb);
+        A.pred = (uint16_t *)(w + 2 * (size_t)held * tb);
+        w += 3 * (size_t)held * tb;
+        A.cost = (float *)w;
+        A.start = (uint32_t *)(w + (size_t)held * ab);
+        A.fb = (uint32_t *)(w + 2 * (size_t)held * ab);
+        A.num_ants = num_ants;
+        A.alpha = alpha;
+        A.beta = beta;
+        A.rate = rate;
     }
-    return TL_OK;
-}
+    void trace_off(Args &L) const { L.log = L.route_log = nullptr; }
+    hipError_t enqueue(tl_ctx *c, Args &L, uint32_t cnt) const
+    {
+        hipError_t e = launch_aco_init(L, cnt, c->stream);
+        if (epochs == 0u || e != hipSuccess) return e;
+        L.pre = 1u;
+        e = launch_aco_update(L, cnt, c->lds_bytes, c->stream);
+        L.pre = 0u;
+        for (uint32_t g = 0; g < epochs && e == hipSuccess; ++g) {
+            L.epoch = g;
+            if ((e = launch_aco_construct(L, cnt, c->stream)) == hipSuccess) e = launch_aco_best(L, cnt, c->stream);
+            if (g + 1u < epochs && e == hipSuccess) e = launch_aco_update(L, cnt, c->lds_bytes, c->stream);  // (the last epoch's deposit is read by nobody)
+        }
+        return e;
+    }
+    int trace_download(const SwarmCall &k, const Args &A) const
+    {
+        if (dev_log_cap) HIPCHK(k.c, hipMemcpyAsync(log, A.log, (size_t)dev_log_cap * 3 * num_ants * 4, hipMemcpyDeviceToHost, k.c->stream));
+        return TL_OK;
+    }
+    int verdict(const SwarmCall &, const std::vector<uint32_t> &) const { return TL_OK; }
+    int trace_finish(const SwarmCall &k, const Args &A, const std::vector<uint32_t> &state) const
+    {
+        if (dev_route_cap) {
+            const uint64_t rows = 1ull + state[1];
+            const uint32_t have = (uint32_t)(rows < dev_route_cap ? rows : dev_route_cap);
+            HIPCHK(k.c, hipMemcpy(route_log, A.route_log, (size_t)have * (k.n + 3) * 4, hipMemcpyDeviceToHost));
+        }
+        if (route_len) *route_len = 1u + state[1];
+        if (log_len) *log_len = epochs;
+        if (k.stats)  // the fallback selections of every run
+            for (uint32_t r = 0; r < k.count; ++r) k.stats->reversed += ((uint64_t)state[8u * r + 5u] << 32) | state[8u * r + 2u];
+        return TL_OK;
+    }
+};
+}  // namespace
 
 extern "C" int tl_ant_colony(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t epochs, float alpha, float beta,
                              float evaporation_rate, uint32_t num_ants, uint64_t seed, uint32_t *out_pos, float *out_cost, tl_stats *stats)
 {
     TL_ENTER(c);
-    return aco_run(c, "tl_ant_colony", xy, n, dm_packed, init_pos, init_pos ? 1u : 0u, 0u, 1u, epochs, alpha, beta, evaporation_rate, num_ants, seed, out_pos,
-                   out_cost, nullptr, stats, nullptr, 0, nullptr, nullptr, 0, nullptr);
+    return swarm_run({c, "tl_ant_colony", xy, n, dm_packed, init_pos, init_pos ? 1u : 0u, 0u, 1u, seed, out_pos, out_cost, stats},
+                     AcoSolver{epochs, alpha, beta, evaporation_rate, num_ants});
 }
 
 extern "C" int tl_ant_colony_trace(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t epochs, float alpha,
@@ -206,8 +191,8 @@ extern "C" int tl_ant_colony_trace(tl_ctx *c, const float *xy, uint32_t n, const
 {
     TL_ENTER(c);
     if (!log || !log_len) return fail(c, TL_ERR_BADARG, "tl_ant_colony_trace: NULL argument");
-    return aco_run(c, "tl_ant_colony_trace", xy, n, dm_packed, init_pos, init_pos ? 1u : 0u, 0u, 1u, epochs, alpha, beta, evaporation_rate, num_ants, seed,
-                   out_pos, out_cost, nullptr, stats, log, log_cap, log_len, route_log, route_cap, route_len);
+    return swarm_run({c, "tl_ant_colony_trace", xy, n, dm_packed, init_pos, init_pos ? 1u : 0u, 0u, 1u, seed, out_pos, out_cost, stats},
+                     AcoSolver{epochs, alpha, beta, evaporation_rate, num_ants, log, log_cap, log_len, route_log, route_cap, route_len});
 }
 
 extern "C" int tl_ant_colony_trace_run(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t epochs, float alpha,
@@ -217,8 +202,8 @@ extern "C" int tl_ant_colony_trace_run(tl_ctx *c, const float *xy, uint32_t n, c
 {
     TL_ENTER(c);
     if (!log || !log_len) return fail(c, TL_ERR_BADARG, "tl_ant_colony_trace_run: NULL argument");
-    return aco_run(c, "tl_ant_colony_trace_run", xy, n, dm_packed, init_pos, init_pos ? 1u : 0u, run, 1u, epochs, alpha, beta, evaporation_rate, num_ants, seed,
-                   out_pos, out_cost, nullptr, stats, log, log_cap, log_len, route_log, route_cap, route_len);
+    return swarm_run({c, "tl_ant_colony_trace_run", xy, n, dm_packed, init_pos, init_pos ? 1u : 0u, run, 1u, seed, out_pos, out_cost, stats},
+                     AcoSolver{epochs, alpha, beta, evaporation_rate, num_ants, log, log_cap, log_len, route_log, route_cap, route_len});
 }
 
 extern "C" int tl_ant_colony_population(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
@@ -226,8 +211,8 @@ extern "C" int tl_ant_colony_population(tl_ctx *c, const float *xy, uint32_t n, 
                                         uint64_t seed, uint32_t *out_pos, float *out_costs, uint32_t *best_index, tl_stats *stats)
 {
     TL_ENTER(c);
-    return aco_run(c, "tl_ant_colony_population", xy, n, dm_packed, init_pos, init_count, first_run, count, epochs, alpha, beta, evaporation_rate, num_ants,
-                   seed, out_pos, out_costs, best_index, stats, nullptr, 0, nullptr, nullptr, 0, nullptr);
+    return swarm_run({c, "tl_ant_colony_population", xy, n, dm_packed, init_pos, init_count, first_run, count, seed, out_pos, out_costs, stats, nullptr, best_index},
+                     AcoSolver{epochs, alpha, beta, evaporation_rate, num_ants});
 }
 
 extern "C" int tl_aco_selftest_select(tl_ctx *c, const float *weights, const float *eta, const uint32_t *visited, uint32_t n, float r1, float r2, uint32_t *out)

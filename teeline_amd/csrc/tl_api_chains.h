@@ -1,6 +1,8 @@
 // tl_api_chains.h — what the calls over seeded chains share on the host (internal to libteeline_gpu): the checks of the common
 // arguments, the instance with its full matrix, the per-CU chain count of a plan, the download of the results and the best
 // chain.  tl_api_sa.hip, tl_api_tabu.hip and tl_api_ga.hip include it; each keeps its own option checks, workspace and launches.
+// tl_api_swarm.h includes it too and builds the one host path of the population solvers (ant colony, particle swarm, cuckoo search,
+// flower pollination, gravitational search) out of these pieces.
 #pragma once
 #include "tl_api_common.h"
 

@@ -2,7 +2,9 @@
 // single-thread guard, error reporting and the grow-only device buffers.  tl_api.hip (context, matrix, tour length),
 // tl_api_two_opt.hip, tl_api_scans.hip (3-opt, Or-opt), tl_api_lk.hip (candidate lists, NN seed, Lin-Kernighan), tl_api_greedy.hip
 // (greedy-edge, savings, Christofides) and tl_api_bhk.hip (Bellman-Held-Karp) include it; tl_api_sa.hip, tl_api_tabu.hip and
-// tl_api_ga.hip (the seeded chains) through tl_api_chains.h, which adds what those three share.
+// tl_api_ga.hip (the seeded chains) through tl_api_chains.h, which adds what those three share; tl_api_aco.hip, tl_api_pso.hip,
+// tl_api_cs.hip, tl_api_fpa.hip and tl_api_gsa.hip (the population solvers) through tl_api_swarm.h, which is over tl_api_chains.h
+// and holds their whole host path.
 #pragma once
 #include "../../include/teeline_gpu.h"
 #include "tl_kernels.h"

@@ -6,19 +6,15 @@
 // fails), so the entries return the empty route or the one city at cost 0, a log of the start gbest alone and epoch rows that hold
 // each agent's live pulls with nothing applied — on the host, without a launch.
 #include "gsa_spec.h"
-#include "tl_api_chains.h"
+#include "tl_api_swarm.h"
 
 using namespace tl;
 using namespace tlapi;
 
-static constexpr uint32_t kGsaUnassignedFlags = 1u << 31;  // the one bit no flag of include/teeline_gpu.h has
-static constexpr uint64_t kGsaWorkDefault = 8ull << 30;    // the runs of one launch sequence
-static constexpr uint32_t kGsaMaxRuns = 65535u;            // the run is the grid's x of the epochs, the grid's y of the start
-static constexpr uint64_t kGsaLayoutSlack = 8 * 256;       // the arrays of a sequence each start on a 256-byte boundary
-static constexpr uint32_t kGsaSpanEpochs = 4096u;          // epochs of one launch where the options name no span, so that no launch runs without end
+static constexpr uint32_t kGsaSpanEpochs = 4096u;  // epochs of one launch where the options name no span, so that no launch runs without end
 
 // one run's share of the workspace: the positions (N n u16), gbest, the costs, the masses, the ranking
-static inline uint64_t gsa_run_bytes(uint32_t n, uint32_t N) { return 2ull * N * n + 2ull * n + 14ull * N; }
+static uint64_t gsa_run_bytes(uint32_t n, uint32_t N) { return 2ull * N * n + 2ull * n + 14ull * N; }
 
 extern "C" uint64_t tl_gsa_draw(uint64_t seed, uint32_t run, uint64_t event, uint32_t slot) { return ga_draw_key(sa_chain_key(seed, run), event, slot); }
 
@@ -43,211 +39,118 @@ extern "C" int tl_gsa_masses(const float *costs, uint32_t agents, double *out_ma
 
 extern "C" uint32_t tl_gravitational_search_max_n(const tl_ctx *c) { return c ? gravitational_search_max_n(c->lds_bytes) : 0u; }
 
+namespace {
+// what gravitational search adds to the frame of tl_api_swarm.h
+struct GsaSolver {
+    using Args = GsaArgs;
+    static constexpr const char *kMembers = "agents";
+    static constexpr uint64_t kLayoutSlack = 8 * 256;  // the arrays of a sequence each start on a 256-byte boundary
+    const tl_gsa_opts *opts;
+    uint32_t epochs = 0, N = 0;
+    size_t tab = 0, gb = 0, row4 = 0, row8 = 0, row2 = 0;
+
+    int check(const SwarmCall &k)
+    {
+        epochs = opts ? opts->epochs : 10000u;  // HeuristicOptions::default (mod.rs:604-611)
+        const uint32_t n_nearest = opts ? opts->n_nearest : 3u;
+        N = gsa_agents(n_nearest);
+        return check_swarm_sizes(k, epochs, n_nearest, N, kGsaMaxAgents, kMembers, gravitational_search_max_n(k.c->lds_bytes), "8");
+    }
+    uint32_t row_words() const { return 3u * N + 2u; }
+    uint64_t log_rows() const { return 1ull + (uint64_t)epochs * N; }  // the start gbest and at most one improvement per move
+    uint64_t run_bytes(uint32_t n) const { return gsa_run_bytes(n, N); }
+    // every cost is 0 and the masses are uniform: G and each agent's live pulls, with nothing applied
+    void host_epoch_rows(const SwarmCall &k, uint32_t *epoch_log, uint32_t rows) const
+    {
+        const uint64_t key = sa_chain_key(k.seed, k.first_run);
+        const uint32_t kb = gsa_kbest(N);
+        const double mass = 1.0 / (double)N;  // kbest is 0 .. kb - 1
+        for (uint32_t e = 0; e < rows; ++e) {
+            uint32_t *erow = epoch_log + (size_t)e * row_words();
+            const double g = gsa_g(e, epochs);
+            const uint64_t gbits = __builtin_bit_cast(uint64_t, g);
+            erow[3u * N] = (uint32_t)gbits;
+            erow[3u * N + 1u] = (uint32_t)(gbits >> 32);
+            for (uint32_t i = 0; i < N; ++i)
+                for (uint32_t j = 0; j < kb; ++j)
+                    if (j != i && gsa_pull_swaps(gsa_r(key, e, N, i, j), g, mass)) ++erow[2u * N + i];
+        }
+    }
+    size_t layout(uint32_t n, uint32_t held)
+    {
+        tab = up256((size_t)held * N * n * 2), gb = up256((size_t)held * n * 2), row4 = up256((size_t)held * N * 4);
+        row8 = up256((size_t)held * N * 8), row2 = up256((size_t)held * N * 2);
+        return tab + gb + row4 + row8 + row2;
+    }
+    void carve(Args &A, unsigned char *w, uint32_t n) const
+    {
+        A.mass = (double *)w;
+        A.pos = (uint16_t *)(w + row8);
+        A.gbest = (uint16_t *)(w + row8 + tab);
+        w += row8 + tab + gb;
+        A.cost = (float *)w;
+        A.kbest = (uint16_t *)(w + row4);
+        A.agents = N;
+        A.vmax = pso_vmax(n);
+        A.epochs = epochs;
+    }
+    hipError_t enqueue(tl_ctx *c, Args &L, uint32_t cnt) const
+    {
+        const uint32_t span = opts && opts->span_epochs ? opts->span_epochs : kGsaSpanEpochs;
+        L.last = epochs == 0u;
+        hipError_t e = launch_gsa_init(L, cnt, c->stream);
+        for (uint32_t ep = 0; ep < epochs && e == hipSuccess; ep = L.e1) {
+            L.e0 = ep;
+            L.e1 = epochs - ep > span ? ep + span : epochs;
+            L.last = L.e1 == epochs;
+            e = launch_gsa_epochs(L, cnt, c->stream);
+        }
+        return e;
+    }
+    int verdict(const SwarmCall &k, const std::vector<uint32_t> &state) const
+    {
+        for (uint32_t r = 0; r < k.count; ++r)
+            if (state[8u * r + 2u])
+                return fail(k.c, TL_ERR_REF_PANICS, "%s: run %u: a cost or a mass is NaN — the reference panics on partial_cmp(..).unwrap()", k.who,
+                            k.first_run + r);
+        return TL_OK;
+    }
+};
+}  // namespace
+
 extern "C" int tl_gravitational_search_plan(uint32_t n, uint32_t n_nearest, uint32_t count, int cus, int lds_bytes, uint64_t workspace_bytes, uint32_t flags,
                                             uint32_t *agents, int *threads, uint32_t *per_launch)
 {
-    if (agents) *agents = 0u;
-    if (threads) *threads = 0;
-    if (per_launch) *per_launch = 0u;
-    if (cus < 1 || lds_bytes < 0) return TL_ERR_BADARG;
-    if (flags & kGsaUnassignedFlags) return TL_ERR_UNSUPPORTED;
-    const uint32_t N = gsa_agents(n_nearest);
-    if (n < 2u || n > gravitational_search_max_n(lds_bytes) || N > kGsaMaxAgents) return TL_OK;
-    uint64_t per = workspace_bytes > kGsaLayoutSlack ? (workspace_bytes - kGsaLayoutSlack) / gsa_run_bytes(n, N) : 0u;
-    if (per > kGsaMaxRuns) per = kGsaMaxRuns;
     (void)count;
-    if (per == 0u) return TL_OK;
-    if (agents) *agents = N;
-    if (threads) *threads = 256;  // the epochs' workgroup: the ranking and the pulls are spread over the agents, whatever n
-    if (per_launch) *per_launch = (uint32_t)per;
-    return TL_OK;
+    // (the epochs' workgroup is 256 lanes whatever n: the ranking and the pulls are spread over the agents)
+    return swarm_plan(n, gsa_agents(n_nearest), kGsaMaxAgents, gravitational_search_max_n, [](uint32_t) { return 256; }, gsa_run_bytes, GsaSolver::kLayoutSlack,
+                      cus, lds_bytes, workspace_bytes, flags, agents, threads, per_launch);
 }
 
-// What the entries share.  log / route_log / epoch_log: run 0 of the call (a single run's trace), else nullptr
-static int gsa_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
-                   uint32_t first_run, uint32_t count, const tl_gsa_opts *opts, uint64_t seed, uint32_t *out_pos, float *out_costs, uint32_t *out_moves,
-                   uint32_t *best_index, tl_stats *stats, uint32_t *log, uint32_t log_cap, uint32_t *log_len, uint32_t *route_log, uint32_t route_cap,
-                   uint32_t *epoch_log, uint32_t epoch_cap)
-{
-    if (log_len) *log_len = 0;
-    if (int rc = check_chain_call(c, who, xy, dm_packed, count, out_pos, init_pos, init_count, first_run, "run")) return rc;
-    if (count == 0) return TL_OK;
-    if (c->flags & kGsaUnassignedFlags) return fail(c, TL_ERR_UNSUPPORTED, "%s: the context's flags 0x%x hold a bit no flag has", who, c->flags);
-    // HeuristicOptions::default (mod.rs:604-611)
-    const uint32_t epochs = opts ? opts->epochs : 10000u, n_nearest = opts ? opts->n_nearest : 3u;
-    const uint32_t N = gsa_agents(n_nearest), kb = gsa_kbest(N), row_words = 3u * N + 2u;
-    if (epochs == 0xFFFFFFFFu) return fail(c, TL_ERR_UNSUPPORTED, "%s: epochs = 2^32 - 1 is not supported", who);
-    if (N > kGsaMaxAgents) return fail(c, TL_ERR_UNSUPPORTED, "%s: n_nearest=%u: more than %u agents", who, n_nearest, kGsaMaxAgents);
-    if (n > gravitational_search_max_n(c->lds_bytes))
-        return fail(c, TL_ERR_UNSUPPORTED, "%s: n=%u exceeds the limit %u (8 bytes of LDS per city)", who, n, gravitational_search_max_n(c->lds_bytes));
-    for (uint32_t r = 0; r < init_count; ++r)
-        if (!is_permutation(init_pos + (size_t)r * n, n)) return fail(c, TL_ERR_BADARG, "%s: the initial tour is not a permutation of 0..n-1", who);
-    const auto t0 = std::chrono::steady_clock::now();
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (best_index) *best_index = 0u;
-    if (n <= 1u) {  // no edge, no device: every cost is 0, the masses are uniform, every sequence is empty, nothing improves
-        for (uint32_t r = 0; r < count; ++r) {
-            if (n) out_pos[r] = 0u;
-            if (out_costs) out_costs[r] = 0.0f;
-            if (out_moves) out_moves[r] = 0u;
-        }
-        if (log && log_cap) {  // record 0: the start gbest, agent 0 (all are equal)
-            log[0] = 0xFFFFFFFFu;
-            log[1] = log[2] = 0u;
-            log[3] = route_log && route_cap ? 0u : 0xFFFFFFFFu;
-        }
-        if (route_log && route_cap && n) route_log[0] = 0u;
-        if (epoch_log) {
-            const uint64_t key = sa_chain_key(seed, first_run);
-            const uint32_t rows = epoch_cap < epochs ? epoch_cap : epochs;
-            const double mass = 1.0 / (double)N;  // kbest is 0 .. kb - 1
-            memset(epoch_log, 0, (size_t)rows * row_words * 4);
-            for (uint32_t e = 0; e < rows; ++e) {
-                uint32_t *erow = epoch_log + (size_t)e * row_words;
-                const double g = gsa_g(e, epochs);
-                const uint64_t gb = __builtin_bit_cast(uint64_t, g);
-                erow[3u * N] = (uint32_t)gb;
-                erow[3u * N + 1u] = (uint32_t)(gb >> 32);
-                for (uint32_t i = 0; i < N; ++i)
-                    for (uint32_t j = 0; j < kb; ++j)
-                        if (j != i && gsa_pull_swaps(gsa_r(key, e, N, i, j), g, mass)) ++erow[2u * N + i];
-            }
-        }
-        if (log_len) *log_len = 1u;
-        c->ev_valid = false;
-        if (stats) {
-            stats->sweeps = (uint64_t)epochs * count;
-            stats->candidates = (uint64_t)epochs * count * N;
-            stamp_times(c, stats, t0);
-        }
-        return TL_OK;
-    }
-    uint32_t per_launch = 0;
-    tl_gravitational_search_plan(n, n_nearest, count, c->cus, c->lds_bytes, kGsaWorkDefault, 0u, nullptr, nullptr, &per_launch);
-    if (per_launch == 0u)
-        return fail(c, TL_ERR_UNSUPPORTED, "%s: n=%u, %u agents: one run's tables (%llu bytes) exceed the workspace limit", who, n, N,
-                    (unsigned long long)gsa_run_bytes(n, N));
-
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    const size_t words = (size_t)count * n;
-    const uint32_t held = count < per_launch ? count : per_launch;  // runs whose agents exist at once
-    const uint64_t most = 1ull + (uint64_t)epochs * N;               // the start gbest and at most one improvement per move
-    const uint32_t dev_log_cap = log ? (uint32_t)(log_cap < most ? log_cap : most) : 0u;
-    const uint32_t dev_route_cap = route_log ? (uint32_t)(route_cap < most ? route_cap : most) : 0u;
-    const uint32_t dev_epoch_cap = epoch_log ? (epoch_cap < epochs ? epoch_cap : epochs) : 0u;
-    const size_t log_bytes = up256((size_t)(dev_log_cap ? dev_log_cap : 1u) * 16);
-    const size_t route_bytes = up256((size_t)(dev_route_cap ? dev_route_cap : 1u) * n * 4);
-    const size_t epoch_bytes = up256((size_t)(dev_epoch_cap ? dev_epoch_cap : 1u) * row_words * 4);
-    const size_t tab = up256((size_t)held * N * n * 2), gb = up256((size_t)held * n * 2), row4 = up256((size_t)held * N * 4),
-                 row8 = up256((size_t)held * N * 8), row2 = up256((size_t)held * N * 2);
-    if ((rc = ensure(c, c->init, (size_t)(init_count ? init_count : 1u) * n * 4)) || (rc = ensure(c, c->out_pos, words * 4)) ||
-        (rc = ensure(c, c->out_cost, (size_t)count * 4)) || (rc = ensure(c, c->misc, (size_t)count * 32)) ||
-        (rc = ensure(c, c->work, log_bytes + route_bytes + epoch_bytes + tab + gb + row4 + row8 + row2)))
-        return rc;
-    GsaArgs A{};
-    if ((rc = upload_instance_full(c, xy, dm_packed, n, &A.xy, &A.dm_full))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->misc.p, 0, (size_t)count * 32, c->stream));
-    if (init_count) {
-        HIPCHK(c, hipMemcpyAsync(c->init.p, init_pos, (size_t)init_count * n * 4, hipMemcpyHostToDevice, c->stream));
-        A.init = (const uint32_t *)c->init.p;
-        A.init_stride = init_count > 1u ? n : 0u;
-    }
-    unsigned char *w = (unsigned char *)c->work.p;
-    A.log = log ? (uint32_t *)w : nullptr;
-    A.log_cap = dev_log_cap;
-    A.route_log = route_log ? (uint32_t *)(w + log_bytes) : nullptr;
-    A.route_cap = dev_route_cap;
-    A.epoch_log = epoch_log ? (uint32_t *)(w + log_bytes + route_bytes) : nullptr;
-    A.epoch_cap = dev_epoch_cap;
-    w += log_bytes + route_bytes + epoch_bytes;
-    A.mass = (double *)w;
-    A.pos = (uint16_t *)(w + row8);
-    A.gbest = (uint16_t *)(w + row8 + tab);
-    w += row8 + tab + gb;
-    A.cost = (float *)w;
-    A.kbest = (uint16_t *)(w + row4);
-    A.seed = seed;
-    A.n = n;
-    A.agents = N;
-    A.vmax = pso_vmax(n);
-    A.epochs = epochs;
-    const uint32_t span = opts && opts->span_epochs ? opts->span_epochs : kGsaSpanEpochs;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    for (uint32_t b0 = 0; b0 < count; b0 += per_launch) {  // sequences on one stream follow each other: the next takes over the tables
-        const uint32_t cnt = count - b0 < per_launch ? count - b0 : per_launch;
-        GsaArgs L = A;
-        L.first_run = first_run + b0;
-        if (L.init && L.init_stride) L.init += (size_t)b0 * n;
-        L.out_pos = (uint32_t *)c->out_pos.p + (size_t)b0 * n;
-        L.out_cost = (float *)c->out_cost.p + b0;
-        L.state = (uint32_t *)c->misc.p + 8u * (size_t)b0;
-        if (b0) L.log = L.route_log = L.epoch_log = nullptr;  // the trace is run 0's
-        L.last = epochs == 0u;
-        HIPCHK(c, launch_gsa_init(L, cnt, c->stream));
-        for (uint32_t e = 0; e < epochs;) {
-            L.e0 = e;
-            L.e1 = epochs - e > span ? e + span : epochs;
-            L.last = L.e1 == epochs;
-            HIPCHK(c, launch_gsa_epochs(L, cnt, c->stream));
-            e = L.e1;
-        }
-    }
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    c->ev_valid = true;
-    std::vector<uint32_t> state;
-    std::vector<float> costs;
-    if ((rc = download_chains(c, count, n, 8u, out_pos, state, costs))) return rc;
-    if (dev_epoch_cap) HIPCHK(c, hipMemcpyAsync(epoch_log, A.epoch_log, (size_t)dev_epoch_cap * row_words * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (uint32_t r = 0; r < count; ++r)
-        if (state[8u * r + 2u])
-            return fail(c, TL_ERR_REF_PANICS, "%s: run %u: a cost or a mass is NaN — the reference panics on partial_cmp(..).unwrap()", who, first_run + r);
-    uint64_t improved = 0;
-    for (uint32_t r = 0; r < count; ++r) {
-        if (out_costs) out_costs[r] = costs[r];
-        if (out_moves) out_moves[r] = state[8u * r + 1u];
-        improved += state[8u * r + 1u];
-    }
-    const uint64_t rows = 1ull + state[1];
-    if (dev_log_cap) HIPCHK(c, hipMemcpy(log, A.log, (size_t)(rows < dev_log_cap ? rows : dev_log_cap) * 16, hipMemcpyDeviceToHost));
-    if (dev_route_cap) HIPCHK(c, hipMemcpy(route_log, A.route_log, (size_t)(rows < dev_route_cap ? rows : dev_route_cap) * n * 4, hipMemcpyDeviceToHost));
-    if (log_len) *log_len = (uint32_t)(rows < 0xFFFFFFFFull ? rows : 0xFFFFFFFFull);
-    if (best_index) *best_index = best_chain(costs, count);
-    if (stats) {
-        stats->sweeps = (uint64_t)epochs * count;
-        stats->candidates = (uint64_t)epochs * count * N;
-        stats->moves = improved;
-        stamp_times(c, stats, t0);
-    }
-    return TL_OK;
-}
-
-extern "C" int tl_gravitational_search(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_gsa_opts *opts,
-                                       uint64_t seed, uint32_t *out_pos, float *out_cost, tl_stats *stats)
+extern "C" int tl_gravitational_search(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_gsa_opts *opts, uint64_t seed,
+                           uint32_t *out_pos, float *out_cost, tl_stats *stats)
 {
     TL_ENTER(c);
-    return gsa_run(c, "tl_gravitational_search", xy, n, dm_packed, init_pos, init_pos ? 1u : 0u, 0u, 1u, opts, seed, out_pos, out_cost, nullptr, nullptr, stats,
-                   nullptr, 0, nullptr, nullptr, 0, nullptr, 0);
+    return swarm4_run({c, "tl_gravitational_search", xy, n, dm_packed, init_pos, init_pos ? 1u : 0u, 0u, 1u, seed, out_pos, out_cost, stats}, GsaSolver{opts}, {});
 }
 
-extern "C" int tl_gravitational_search_trace(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_gsa_opts *opts,
-                                             uint64_t seed, uint32_t run, uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *log, uint32_t log_cap,
-                                             uint32_t *log_len, uint32_t *route_log, uint32_t route_cap, uint32_t *epoch_log, uint32_t epoch_cap)
+extern "C" int tl_gravitational_search_trace(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_gsa_opts *opts, uint64_t seed,
+                                 uint32_t run, uint32_t *out_pos, float *out_cost, tl_stats *stats, uint32_t *log, uint32_t log_cap, uint32_t *log_len,
+                                 uint32_t *route_log, uint32_t route_cap, uint32_t *epoch_log, uint32_t epoch_cap)
 {
     TL_ENTER(c);
     if (!log || !log_len) return fail(c, TL_ERR_BADARG, "tl_gravitational_search_trace: NULL argument");
-    return gsa_run(c, "tl_gravitational_search_trace", xy, n, dm_packed, init_pos, init_pos ? 1u : 0u, run, 1u, opts, seed, out_pos, out_cost, nullptr, nullptr,
-                   stats, log, log_cap, log_len, route_log, route_cap, epoch_log, epoch_cap);
+    return swarm4_run({c, "tl_gravitational_search_trace", xy, n, dm_packed, init_pos, init_pos ? 1u : 0u, run, 1u, seed, out_pos, out_cost, stats}, GsaSolver{opts},
+                      {log, log_cap, log_len, route_log, route_cap, epoch_log, epoch_cap});
 }
 
 extern "C" int tl_gravitational_search_population(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
-                                                  uint32_t first_run, uint32_t count, const tl_gsa_opts *opts, uint64_t seed, uint32_t *out_pos,
-                                                  float *out_costs, uint32_t *out_moves, uint32_t *best_index, tl_stats *stats)
+                                      uint32_t first_run, uint32_t count, const tl_gsa_opts *opts, uint64_t seed, uint32_t *out_pos, float *out_costs,
+                                      uint32_t *out_moves, uint32_t *best_index, tl_stats *stats)
 {
     TL_ENTER(c);
-    return gsa_run(c, "tl_gravitational_search_population", xy, n, dm_packed, init_pos, init_count, first_run, count, opts, seed, out_pos, out_costs, out_moves,
-                   best_index, stats, nullptr, 0, nullptr, nullptr, 0, nullptr, 0);
+    return swarm4_run({c, "tl_gravitational_search_population", xy, n, dm_packed, init_pos, init_count, first_run, count, seed, out_pos, out_costs, stats, out_moves, best_index},
+                      GsaSolver{opts}, {});
 }
 
 extern "C" int tl_gsa_selftest_pull(tl_ctx *c, const uint32_t *from, const uint32_t *target, const uint32_t *prefix, uint32_t n, uint32_t count,
@@ -255,7 +158,7 @@ extern "C" int tl_gsa_selftest_pull(tl_ctx *c, const uint32_t *from, const uint3
 {
     TL_ENTER(c);
     if (!c || !from || !target || !prefix || !out_pairs || !out_len) return fail(c, TL_ERR_BADARG, "tl_gsa_selftest_pull: NULL argument");
-    if (n < 1u || n > gravitational_search_max_n(c->lds_bytes) || count < 1u || count > kGsaMaxRuns)
+    if (n < 1u || n > gravitational_search_max_n(c->lds_bytes) || count < 1u || count > kSwarmMaxRuns)
         return fail(c, TL_ERR_BADARG, "tl_gsa_selftest_pull: n or count out of range");
     const size_t cells = (size_t)count * n;
     std::vector<uint16_t> h(2 * cells);

@@ -6,12 +6,10 @@ abandonment).  Two things are this project's specification instead: the random d
 cuckoo, role) — the reference's thread RNG is unseeded — and the Lévy step is a fixed sequence of f64 operations
 (include/teeline_gpu.h).
 """
-import ctypes as C
-
 import numpy as np
 
 from . import HeuristicOptions
-from ._chains import bits_to_f32, solve_chains, vp
+from ._chains import solve_swarm
 
 
 class CSOptions:
@@ -40,50 +38,7 @@ def solve(problem, opts=None, progress_tx=None, init_tour=None, *, ctx=None, see
     if isinstance(opts, HeuristicOptions):
         opts = CSOptions(opts)
     opts.validate()
-    n = len(problem)
     epochs = int(opts.heuristic.epochs)
     o = _capi.TlCsOpts(epochs, int(opts.heuristic.n_nearest), opts.mutation_probability)
-    init_pos = problem.positions_of(init_tour) if init_tour is not None else None
-    packed = problem.explicit_packed()
-    head = (ctx.handle, vp(problem.xy), n, vp(packed), vp(init_pos))
-
-    def population(count, outs, costs, moves, best, st):
-        ctx.check(ctx.lib.tl_cuckoo_search_population(*head, 0 if init_pos is None else 1, 0, count, C.byref(o), seed, vp(outs), vp(costs), vp(moves),
-                                                      C.byref(best), C.byref(st)))
-
-    def single(out, cost, st):
-        ctx.check(ctx.lib.tl_cuckoo_search(*head, C.byref(o), seed, vp(out), C.byref(cost), C.byref(st)))
-
-    def trace(run):
-        # the improvements are few but not known in advance: read the count first
-        out = np.empty(n, dtype=np.uint32)
-        cost, st, ln = C.c_float(), _capi.TlStats(), C.c_uint32()
-        cap = 64
-        while True:
-            log = np.empty((cap, 4), dtype=np.uint32)
-            routes = np.empty((cap, max(n, 1)), dtype=np.uint32)
-            ctx.check(ctx.lib.tl_cuckoo_search_trace(*head, C.byref(o), seed, run, vp(out), C.byref(cost), C.byref(st), vp(log), cap, C.byref(ln), vp(routes), cap,
-                                                     None, 0))
-            if ln.value <= cap:
-                break
-            cap = ln.value
-        return out, cost.value, (log[:ln.value], routes[:ln.value, :n]), dict(st.as_dict(), run=run)
-
-    def replay(record):
-        log, routes = record
-        ids = problem.ids
-        send = lambda k: progress_tx("PathUpdate", ([int(v) for v in ids[routes[k]]], float(bits_to_f32(log[k, 2]))))  # noqa: E731
-        if len(log):
-            send(0)
-        k = 1
-        for e in range(epochs):
-            while k < len(log) and log[k, 0] == e:
-                send(k)
-                k += 1
-            progress_tx("EpochUpdate", e)
-        progress_tx("Done", None)
-
-    sol = solve_chains(problem, progress_tx, runs, population, single, trace, replay)
-    if "chain" in sol.stats:
-        sol.stats["run"] = sol.stats.pop("chain")
-    return sol
+    lib = ctx.lib
+    return solve_swarm(problem, progress_tx, init_tour, ctx, seed, runs, epochs, o, lib.tl_cuckoo_search, lib.tl_cuckoo_search_trace, lib.tl_cuckoo_search_population, (None, 0))
