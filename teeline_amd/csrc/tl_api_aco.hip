@@ -166,7 +166,7 @@ struct AcoSolver {
         if (dev_route_cap) {
             const uint64_t rows = 1ull + state[1];
             const uint32_t have = (uint32_t)(rows < dev_route_cap ? rows : dev_route_cap);
-            HIPCHK(k.c, hipMemcpy(route_log, A.route_log, (size_t)have * (k.n + 3) * 4, hipMemcpyDeviceToHost));
+            if (int rc = download_sync(k.c, route_log, A.route_log, (size_t)have * (k.n + 3) * 4)) return rc;
         }
         if (route_len) *route_len = 1u + state[1];
         if (log_len) *log_len = epochs;

@@ -178,6 +178,16 @@ inline int upload_start_sync(tl_ctx *c, const uint32_t *init, uint32_t n, void *
     return TL_OK;
 }
 
+// A device-to-host copy whose length the call learns only from records it has already downloaded, so the host reads it at once: on
+// the context's own stream, then a synchronise.  Never a plain hipMemcpy: that one goes through the legacy default stream, and while
+// ANOTHER host thread captures a graph on its context's stream (RoundGraph) the runtime refuses it here and invalidates the capture there.
+inline int download_sync(tl_ctx *c, void *dst, const void *src, size_t bytes)
+{
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TL_OK;
+}
+
 // The ending of a call that fills tl_stats: kernel_ms between the context's event pair (0 where none is valid), total_ms since t0.
 inline void stamp_times(tl_ctx *c, tl_stats *st, std::chrono::steady_clock::time_point t0)
 {

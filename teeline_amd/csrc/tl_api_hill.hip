@@ -104,8 +104,7 @@ static int hill_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, con
     if ((rc = download_chains(c, count, n, 4u, out_pos, run, costs))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const uint64_t events = (uint64_t)run[0] + run[3];  // (at most one event an epoch: below 2^32)
-    if (move_log && dev_log_cap && events)
-        HIPCHK(c, hipMemcpy(move_log, A.log, (size_t)(events < dev_log_cap ? events : dev_log_cap) * 16, hipMemcpyDeviceToHost));
+    if (move_log && dev_log_cap && events && (rc = download_sync(c, move_log, A.log, (size_t)(events < dev_log_cap ? events : dev_log_cap) * 16))) return rc;
     if (log_len) *log_len = (uint32_t)events;
     uint64_t moves = 0, reversed = 0;
     for (uint32_t r = 0; r < count; ++r) {

@@ -185,8 +185,7 @@ static int sa_run(tl_ctx *c, const char *who, const float *xy, uint32_t n, const
     std::vector<float> costs;
     if ((rc = download_chains(c, count, n, 4u, out_pos, run, costs))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (move_log && dev_log_cap && run[0])
-        HIPCHK(c, hipMemcpy(move_log, A.log, (size_t)(run[0] < dev_log_cap ? run[0] : dev_log_cap) * 16, hipMemcpyDeviceToHost));
+    if (move_log && dev_log_cap && run[0] && (rc = download_sync(c, move_log, A.log, (size_t)(run[0] < dev_log_cap ? run[0] : dev_log_cap) * 16))) return rc;
     if (log_len) *log_len = run[0];
     uint64_t moves = 0, reversed = 0;
     for (uint32_t r = 0; r < count; ++r) {

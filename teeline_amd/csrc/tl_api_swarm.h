@@ -273,8 +273,9 @@ struct Swarm4 {
     int trace_finish(const SwarmCall &k, const Args &A, const std::vector<uint32_t> &state) const
     {
         const uint64_t rows = 1ull + state[1];
-        if (log_cap) HIPCHK(k.c, hipMemcpy(t.log, A.log, (size_t)(rows < log_cap ? rows : log_cap) * 16, hipMemcpyDeviceToHost));
-        if (route_cap) HIPCHK(k.c, hipMemcpy(t.route_log, A.route_log, (size_t)(rows < route_cap ? rows : route_cap) * k.n * 4, hipMemcpyDeviceToHost));
+        int rc;
+        if (log_cap && (rc = download_sync(k.c, t.log, A.log, (size_t)(rows < log_cap ? rows : log_cap) * 16))) return rc;
+        if (route_cap && (rc = download_sync(k.c, t.route_log, A.route_log, (size_t)(rows < route_cap ? rows : route_cap) * k.n * 4))) return rc;
         if (t.log_len) *t.log_len = (uint32_t)(rows < 0xFFFFFFFFull ? rows : 0xFFFFFFFFull);
         return TL_OK;
     }

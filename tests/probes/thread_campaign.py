@@ -1,12 +1,18 @@
 """Re-entrancy campaign: T host threads, each with its OWN tl_ctx, run a mix of the library's entry points concurrently for a
 given time — 2-opt at n = 52 / 1 002 / 4 097 / 10 000 (so that launches with different LDS sizes of the same kernel overlap:
 csrc/tl_kernels.h allow_max_lds), the matrix form, 3-opt, Or-opt, Lin-Kernighan (hipGraph capture on one stream while the others
-allocate and launch), the NN seed, candidate lists, tl_dm_build, multi-start — and every result is compared bit for bit with what
-the CPU oracle gave for the same input before the threads started.  Then two threads share ONE context: every call must come back
+allocate and launch), the NN seed, candidate lists, tl_dm_build, multi-start, and one small job of every newer solver (the table of
+tests/_context_jobs.py: constructions, exact solvers, population scans, seeded chains, the genetic algorithm, the swarm solvers, the
+ant colony, the Kohonen map, the Fourier curve) — and every result is compared bit for bit with what the CPU oracle gave for the same
+input before the threads started.  Then two threads share ONE context: every call must come back
 either right or TL_ERR_BUSY.
 
 The reference calls its solvers from arbitrary threads (teeline-api/src/services/tsp_service.rs:295,328 spawn_blocking;
 teeline-qt/src/solver_engine.rs:412-432 worker thread); SURVEY.md §8(b): "contexts are independent".
+
+Measured on the MI355X, 8 threads, 33 jobs: the first pass over all jobs takes a thread 0.9 .. 2.2 s on the product library and
+10.7 .. 17.0 s on the -DTL_JITTER build (tests/test_gpu_threads.py gives the child 400 s); in 10 s a thread makes 789 .. 991 runs on the
+product library.
 
     python tests/probes/thread_campaign.py [seconds] [threads]          (TEELINE_GPU_LIB selects the library, e.g. the jitter build)
 """
@@ -21,6 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
+import _context_jobs as CJ  # noqa: E402
 import _oracle as O  # noqa: E402
 import _tsplib as T  # noqa: E402
 import teeline_amd as TA  # noqa: E402
@@ -113,9 +120,14 @@ jobs.append(("multistart 6 x n=1002", multistart, (crc(oms[best][1]), np.asarray
 xy500 = O.synth_xy(500, seed=4)
 jobs.append(("2opt best-sweep n=500", lambda c: sol_key(TA.two_opt.solve(prob(xy500), ctx=c, mode=TA.TL_MODE_BEST_SWEEP)),
              okey(O.two_opt(xy500, None, 500, best=True))))
+# the newer solvers: the whole table of tests/_context_jobs.py (a small job per family, every host path among them; two answered on the
+# host, whose last words are the kernel time 0 in their stats and behind them)
+for j in CJ.jobs():
+    jobs.append((j.name, j.run, j.oracle()))
 print(f"{len(jobs)} jobs, oracle expectations in {time.time() - t_or:.1f} s; library: {TA._capi.LIB_PATH}", flush=True)
 
 runs = [0] * nthreads
+first_pass = [0.0] * nthreads  # seconds a thread took for its first pass over all jobs
 fails = []
 lock = threading.Lock()
 t_end = time.time() + budget
@@ -138,6 +150,8 @@ def worker(k):
                         fails.append((k, name, got, want))
                 if not first and time.time() >= t_end:
                     break
+            if first:
+                first_pass[k] = time.time() - t0
             first = False  # every thread runs every job at least once
 
 
@@ -145,6 +159,7 @@ t0 = time.time()
 th = [threading.Thread(target=worker, args=(k,)) for k in range(nthreads)]
 [t.start() for t in th]
 [t.join() for t in th]
+print(f"first pass over all jobs: {min(first_pass):.1f}..{max(first_pass):.1f} s per thread", flush=True)
 for f in fails[:10]:
     print("MISMATCH thread %d %s: got %r want %r" % f, flush=True)
 print(f"own contexts: {nthreads} threads, {sum(runs)} runs ({min(runs)}..{max(runs)} per thread), {len(fails)} mismatches, {time.time() - t0:.0f} s", flush=True)

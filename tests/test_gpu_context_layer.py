@@ -7,6 +7,9 @@
 3. (tests/test_gpu_lk.py: re-entry from the live callback of every LK form.)
 4. The matrix form's list of long cities: a late sweep that passes its capacity leaves the lists (hub instance, n = 3000).
 5. One grow-only context, a dozen jobs in several orders, behind large jobs of each kind: no result depends on what ran before.
+   (The solvers added since — the constructions, the exact solvers, the population scans, the seeded chains and populations, the
+   Kohonen map, the Fourier curve — have their order tests, the pair sequence over their host paths and their share of section 2 in
+   tests/test_gpu_context_solvers.py, which runs behind this file's fillers too.)
 
 Measured on the MI355X: the 22 tests of this file take 16 s together (6 s of them test_multistart_one_past_the_lds_limit_over_two_contexts, 3 s
 the split of n = 2000 over 1 ... 9 contexts); the three added cases of the re-entry test in tests/test_gpu_lk.py 0.2 s.
