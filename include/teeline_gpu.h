@@ -1237,6 +1237,65 @@ int tl_fourier_init(const float *xy, uint32_t n, uint32_t k_max, double *out_coe
 int tl_fourier_nearest(const double *gamma, uint32_t m, const float *xy, uint32_t n, uint32_t *out_idx);
 int tl_fourier_selftest_search(tl_ctx *ctx, const double *gamma, uint32_t m, const float *xy, uint32_t n, int threads, uint32_t *out_idx);
 
+/* ---- Held-Karp lower bound: the minimum 1-tree under node penalties, raised by subgradient ascent ----- */
+/* Not a solver and not the reference's: this project's own specification (csrc/one_tree_spec.h,
+ * tests/_one_tree_oracle.py).  The result is a LOWER bound on the length of every tour under the same f32 distances d (dist() of
+ * the coordinates, or dm_packed), as a double: L = min 1-tree weight under w(i, j) = (double)d(i, j) + (pi_i + pi_j), minus 2 sum pi.
+ * A 1-tree with special position `root`: Prim's tree over the other positions (the lowest of them first; the smallest key, the
+ * first in position order among equals; a key is lowered only where w is STRICTLY smaller) plus the root's two smallest edges
+ * (the lower position among equals).  The ascent starts at pi = 0, lambda = lambda0, and per iteration k: builds the 1-tree; a new
+ * best L is kept with its pi and its tree, else after `patience` iterations without one lambda is halved; stops where the 1-tree
+ * is a tour (every degree 2: the bound is then the optimum and the tour is written out from the root towards its first chosen
+ * neighbour), where lambda < 2^-20, where upper - L_k <= 0; else pi_i += lambda (upper - L_k) / sum g^2 x (degree_i - 2).
+ * A batch is a list of option sets on one problem, one workgroup each; job j equals the single call with opts[j] bit for bit, and
+ * neither depends on iters_per_launch.  *best_index: the first job with the largest bound.
+ * opts is required (upper has no default).  TL_ERR_BADARG: root >= n (n >= 1), iterations < 1, lambda0 not finite or <= 0,
+ * patience < 1, upper not finite or <= 0, reserved != 0, more than 65 535 jobs.  TL_ERR_UNSUPPORTED: a coordinate that is not
+ * finite or beyond 2^62 in size, a matrix entry that is not finite or is negative (-0.0 included), n > tl_one_tree_bound_max_n
+ * (before anything of size n is read).  n <= 2 is answered without a launch: bound 0 (n <= 1) or 2 d(0, 1), is_tour 1, stop 0.
+ * Outputs, each optional: results — jobs records; out_pi — jobs x n doubles, the best pi; out_parent — jobs x n, the best tree's
+ * parents (TL_ONE_TREE_NONE for the root and for Prim's start); out_tour — jobs x n positions where is_tour, else untouched; log —
+ * jobs x log_cap rows of 3 doubles (L_k, sum g^2, lambda after the iteration's halving), rows >= iterations_run untouched.
+ * stats: sweeps = iterations of all jobs, candidates = Prim rounds; kernel_ms sums the launches between event pairs and leaves out the
+ * host's look at the states after every 16th launch (tl_last_kernel_ms reports the last group of launches only).
+ * tl_one_tree_bound_host: the sequential restatement on the CPU (no context, no device), the same contract for one job, any n.
+ * tl_one_tree_bound_plan: threads of a workgroup and iterations of a launch for n; tl_one_tree_bound_max_n: the largest n whose
+ * state (24 n bytes) fits lds_bytes; tl_one_tree_bound_work_bytes: the device workspace of such a call (0 for n <= 2). */
+#define TL_ONE_TREE_NONE 0xFFFFFFFFu
+#define TL_ONE_TREE_STOP_TOUR 1u
+#define TL_ONE_TREE_STOP_LAMBDA 2u
+#define TL_ONE_TREE_STOP_UPPER 3u
+#define TL_ONE_TREE_STOP_ITERATIONS 4u
+typedef struct tl_one_tree_opts {
+    uint32_t root;             /* the 1-tree's special position */
+    uint32_t iterations;       /* default of the mirrors: 1000 */
+    uint32_t patience;         /* 10 */
+    uint32_t iters_per_launch; /* 0: the plan's.  Same result */
+    double lambda0;            /* 2.0 */
+    double upper;              /* the length of any tour */
+    uint64_t reserved;         /* 0 */
+} tl_one_tree_opts;
+typedef struct tl_one_tree_result {
+    double bound;              /* the best L */
+    double lambda;             /* at the end */
+    uint32_t best_iter;
+    uint32_t iterations_run;
+    uint32_t stop;             /* TL_ONE_TREE_STOP_* */
+    uint32_t is_tour;
+    uint32_t root_nb[2];       /* the best tree's root neighbours in the order chosen */
+    uint32_t tour_nb[2];       /* those of the 1-tree that was a tour */
+} tl_one_tree_result;
+int tl_one_tree_bound(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, const tl_one_tree_opts *opts, tl_one_tree_result *result,
+                      double *out_pi, uint32_t *out_parent, uint32_t *out_tour, double *log, uint32_t log_cap, tl_stats *stats);
+int tl_one_tree_bound_batch(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, const tl_one_tree_opts *opts, uint32_t jobs,
+                            tl_one_tree_result *results, double *out_pi, uint32_t *out_parent, uint32_t *out_tour, double *log, uint32_t log_cap,
+                            uint32_t *best_index, tl_stats *stats);
+int tl_one_tree_bound_host(const float *xy, const float *dm_packed, uint32_t n, const tl_one_tree_opts *opts, tl_one_tree_result *result, double *out_pi,
+                           uint32_t *out_parent, uint32_t *out_tour, double *log, uint32_t log_cap);
+int tl_one_tree_bound_plan(uint32_t n, int lds_bytes, int *threads, uint32_t *iters_per_launch);
+uint32_t tl_one_tree_bound_max_n(int lds_bytes);
+uint64_t tl_one_tree_bound_work_bytes(uint32_t n, uint32_t jobs, uint32_t log_cap);
+
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts
  * first..first+count as above; seed ignored otherwise).  d_out_pos: count x n u32, d_out_cost: count f32,

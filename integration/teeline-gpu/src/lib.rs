@@ -105,6 +105,56 @@ pub struct FourierOpts {
     pub threads: u32,
 }
 
+/// `tl_one_tree_opts`: one job of the Held-Karp lower bound.  `upper` is the length of any tour and has no default.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct OneTreeOpts {
+    pub root: u32,
+    pub iterations: u32,
+    pub patience: u32,
+    /// 0: the plan's; never in the result
+    pub iters_per_launch: u32,
+    pub lambda0: f64,
+    pub upper: f64,
+    pub reserved: u64,
+}
+
+impl OneTreeOpts {
+    /// The defaults (root 0, 1 000 iterations, lambda0 2, patience 10) for this upper bound.
+    pub fn with_upper(upper: f64) -> Self {
+        OneTreeOpts { root: 0, iterations: 1000, patience: 10, iters_per_launch: 0, lambda0: 2.0, upper, reserved: 0 }
+    }
+}
+
+/// `tl_one_tree_result`: stop is 1 tour, 2 lambda, 3 upper, 4 iterations (0: n <= 2).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct OneTreeResult {
+    pub bound: f64,
+    pub lambda: f64,
+    pub best_iter: u32,
+    pub iterations_run: u32,
+    pub stop: u32,
+    pub is_tour: u32,
+    pub root_nb: [u32; 2],
+    pub tour_nb: [u32; 2],
+}
+
+/// One job's outcome of `one_tree_bound_batch`: the figures, the best penalties and, where the 1-tree was a tour, that tour.
+#[derive(Clone, Debug)]
+pub struct OneTreeBound {
+    pub result: OneTreeResult,
+    pub pi: Vec<f64>,
+    pub tour: Option<Vec<u32>>,
+}
+
+impl OneTreeBound {
+    /// How far above the optimum a tour of this cost can be at most, in percent.
+    pub fn gap_pct(&self, cost: f64) -> f64 {
+        100.0 * (cost - self.result.bound) / self.result.bound
+    }
+}
+
 impl Default for FourierOpts {
     fn default() -> Self {
         FourierOpts { k_max: 4, m: 200, epochs: 400, chunk: 0, lambda: 0.05, lambda_decay: 0.5, lr: 0.05, span_steps: 0, threads: 0 }
@@ -304,6 +354,14 @@ unsafe extern "C" {
                               out_costs: *mut f32, out_coeffs: *mut f64, coeff_stride: u32, best_index: *mut u32, stats: *mut Stats, log: *mut u32,
                               log_cap: u32, stage_coeffs: *mut f64) -> i32;
     fn tl_fourier_curve_work_bytes(n: u32, opts: *const FourierOpts, jobs: u32, log_cap: u32) -> u64;
+    fn tl_one_tree_bound_batch(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, opts: *const OneTreeOpts, jobs: u32,
+                               results: *mut OneTreeResult, out_pi: *mut f64, out_parent: *mut u32, out_tour: *mut u32, log: *mut f64, log_cap: u32,
+                               best_index: *mut u32, stats: *mut Stats) -> i32;
+    fn tl_one_tree_bound_host(xy: *const f32, dm_packed: *const f32, n: u32, opts: *const OneTreeOpts, result: *mut OneTreeResult, out_pi: *mut f64,
+                              out_parent: *mut u32, out_tour: *mut u32, log: *mut f64, log_cap: u32) -> i32;
+    fn tl_one_tree_bound_plan(n: u32, lds_bytes: c_int, threads: *mut c_int, iters_per_launch: *mut u32) -> i32;
+    fn tl_one_tree_bound_max_n(lds_bytes: c_int) -> u32;
+    fn tl_one_tree_bound_work_bytes(n: u32, jobs: u32, log_cap: u32) -> u64;
     fn tl_nearest_neighbor(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, n_nearest: u32,
                            out_pos: *mut u32, out_cost: *mut f32) -> c_int;
     fn tl_greedy_edge(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
@@ -978,6 +1036,75 @@ impl Context {
     pub fn fourier_curve_work_bytes(n: u32, jobs: &[FourierOpts]) -> u64 {
         // SAFETY: a host-only query over the slice.
         unsafe { tl_fourier_curve_work_bytes(n, jobs.as_ptr(), jobs.len() as u32, 0) }
+    }
+
+    /// The Held-Karp lower bound (not a solver and not the reference's) for every option set of `jobs` at once, one
+    /// workgroup each: every job's outcome and the index of the first job with the largest bound.  The bound holds for every tour
+    /// under the same f32 distances; job j equals the call with `jobs[j]` alone bit for bit.  (Written against the header; not
+    /// compiled here: no Rust toolchain on the build machine, see scripts/check_rust.sh.)
+    pub fn one_tree_bound_batch(&self, xy: &[f32], dm_packed: Option<&[f32]>, jobs: &[OneTreeOpts]) -> Result<(Vec<OneTreeBound>, u32), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, None);
+        let (count, m) = (jobs.len(), (n as usize).max(1));
+        let mut res = vec![OneTreeResult::default(); count];
+        let mut pi = vec![0f64; m * count];
+        let mut tour = vec![0u32; m * count];
+        let (mut best, mut st) = (0u32, Stats::default());
+        // SAFETY: the slices hold n cities (check_inputs); the outputs hold count records and count x n entries; parents and log are null.
+        let rc = unsafe {
+            tl_one_tree_bound_batch(self.raw, xy.as_ptr(), opt_ptr(dm_packed), n, jobs.as_ptr(), count as u32, res.as_mut_ptr(), pi.as_mut_ptr(),
+                                    ptr::null_mut(), tour.as_mut_ptr(), ptr::null_mut(), 0, &mut best, &mut st)
+        };
+        self.check(rc)?;
+        let out = (0..count)
+            .map(|k| OneTreeBound {
+                result: res[k],
+                pi: pi[k * n as usize..(k + 1) * n as usize].to_vec(),
+                tour: if res[k].is_tour != 0 { Some(tour[k * n as usize..(k + 1) * n as usize].to_vec()) } else { None },
+            })
+            .collect();
+        Ok((out, best))
+    }
+
+    /// One job of `one_tree_bound_batch`.
+    pub fn one_tree_bound(&self, xy: &[f32], dm_packed: Option<&[f32]>, opts: &OneTreeOpts) -> Result<OneTreeBound, Error> {
+        self.one_tree_bound_batch(xy, dm_packed, std::slice::from_ref(opts)).map(|(mut b, _)| b.remove(0))
+    }
+
+    /// The sequential restatement on the CPU (no context, no device), the same contract: the library's return code on refusal.
+    pub fn one_tree_bound_host(xy: &[f32], dm_packed: Option<&[f32]>, opts: &OneTreeOpts) -> Result<OneTreeBound, i32> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, None);
+        let mut res = OneTreeResult::default();
+        let mut pi = vec![0f64; (n as usize).max(1)];
+        let mut tour = vec![0u32; (n as usize).max(1)];
+        // SAFETY: the slices hold n cities; the outputs hold one record and n entries; parents and log are null.
+        let rc = unsafe {
+            tl_one_tree_bound_host(xy.as_ptr(), opt_ptr(dm_packed), n, opts, &mut res, pi.as_mut_ptr(), ptr::null_mut(), tour.as_mut_ptr(), ptr::null_mut(), 0)
+        };
+        if rc != 0 {
+            return Err(rc);
+        }
+        pi.truncate(n as usize);
+        tour.truncate(n as usize);
+        Ok(OneTreeBound { result: res, pi, tour: if res.is_tour != 0 { Some(tour) } else { None } })
+    }
+
+    /// The largest n whose state fits `lds_bytes` of LDS, and (threads, iterations of a launch) for n, None where n is refused.
+    pub fn one_tree_bound_max_n(lds_bytes: i32) -> u32 {
+        // SAFETY: a host-only query.
+        unsafe { tl_one_tree_bound_max_n(lds_bytes) }
+    }
+    pub fn one_tree_bound_plan(n: u32, lds_bytes: i32) -> Option<(i32, u32)> {
+        let (mut t, mut span) = (0 as c_int, 0u32);
+        // SAFETY: a host-only query with two live outputs.
+        let rc = unsafe { tl_one_tree_bound_plan(n, lds_bytes, &mut t, &mut span) };
+        if rc == 0 { Some((t, span)) } else { None }
+    }
+    /// The device workspace a batch of `jobs` jobs takes (0 for n <= 2).
+    pub fn one_tree_bound_work_bytes(n: u32, jobs: u32) -> u64 {
+        // SAFETY: a host-only query.
+        unsafe { tl_one_tree_bound_work_bytes(n, jobs, 0) }
     }
 
     /// Largest n of `hill_climb` (the current tour lives in one CU's LDS, 12 bytes per city).

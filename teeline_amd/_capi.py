@@ -81,6 +81,8 @@ SYMBOLS = [
     "tl_fourier_curve", "tl_fourier_curve_batch", "tl_fourier_curve_work_bytes", "tl_fourier_curve_plan",
     "tl_fourier_basis", "tl_fourier_init", "tl_fourier_nearest", "tl_fourier_selftest_search",
     "tl_branch_and_bound", "tl_branch_and_bound_host", "tl_branch_and_bound_plan",
+    "tl_one_tree_bound", "tl_one_tree_bound_batch", "tl_one_tree_bound_host", "tl_one_tree_bound_plan", "tl_one_tree_bound_max_n",
+    "tl_one_tree_bound_work_bytes",
 ]
 
 
@@ -156,6 +158,22 @@ class TlBnbStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TlOneTreeOpts(C.Structure):
+    """tl_one_tree_opts: the 1-tree's special position, the ascent's options, the iterations of one launch (0: the plan's)"""
+    _fields_ = [("root", C.c_uint32), ("iterations", C.c_uint32), ("patience", C.c_uint32), ("iters_per_launch", C.c_uint32),
+                ("lambda0", C.c_double), ("upper", C.c_double), ("reserved", C.c_uint64)]
+
+
+class TlOneTreeResult(C.Structure):
+    """tl_one_tree_result"""
+    _fields_ = [("bound", C.c_double), ("lam", C.c_double), ("best_iter", C.c_uint32), ("iterations_run", C.c_uint32), ("stop", C.c_uint32),
+                ("is_tour", C.c_uint32), ("root_nb", C.c_uint32 * 2), ("tour_nb", C.c_uint32 * 2)]
+
+    def as_dict(self):
+        return dict(bound=self.bound, lam=self.lam, best_iter=self.best_iter, iterations_run=self.iterations_run, stop=self.stop,
+                    is_tour=self.is_tour, root_nb=tuple(self.root_nb), tour_nb=tuple(self.tour_nb))
 
 
 # tl_lk_progress_fn: void (*)(void *user, const uint32_t *best_pos, uint32_t n, float best_dist)
@@ -388,5 +406,14 @@ def load():
     L.tl_branch_and_bound.argtypes = [vp, vp, vp, u32, vp, bo, vp, f32p, C.POINTER(u32), C.POINTER(u32), bs]
     L.tl_branch_and_bound_host.argtypes = [vp, vp, u32, vp, bo, vp, f32p, C.POINTER(u32), C.POINTER(u32), bs]
     L.tl_branch_and_bound_plan.argtypes = [u32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(u32), C.POINTER(u32)]
+    oo, orr = C.POINTER(TlOneTreeOpts), C.POINTER(TlOneTreeResult)
+    L.tl_one_tree_bound.argtypes = [vp, vp, vp, u32, oo, orr, vp, vp, vp, vp, u32, C.POINTER(TlStats)]
+    L.tl_one_tree_bound_batch.argtypes = [vp, vp, vp, u32, oo, u32, orr, vp, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(TlStats)]
+    L.tl_one_tree_bound_host.argtypes = [vp, vp, u32, oo, orr, vp, vp, vp, vp, u32]
+    L.tl_one_tree_bound_plan.argtypes = [u32, i32, C.POINTER(i32), C.POINTER(u32)]
+    L.tl_one_tree_bound_max_n.argtypes = [i32]
+    L.tl_one_tree_bound_max_n.restype = u32
+    L.tl_one_tree_bound_work_bytes.argtypes = [u32, u32, u32]
+    L.tl_one_tree_bound_work_bytes.restype = u64
     _lib = L
     return L

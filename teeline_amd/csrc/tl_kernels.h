@@ -652,6 +652,27 @@ hipError_t launch_fourier_steps(const FourierArgs &A, uint32_t jobs, int threads
 hipError_t launch_fourier_decode(const FourierArgs &A, uint32_t jobs, hipStream_t s);                                // every job's tour and cost from its coefficients
 hipError_t launch_fourier_selftest_search(const FourierArgs &A, int threads, hipStream_t s);  // the steps' search alone on A.gamma_in (m = max_m) into A.sidx
 
+// one_tree_bound.hip — the Held-Karp lower bound, the job (an option set) a grid dimension, a span of ascent iterations per launch
+struct OneTreeJob;    // one_tree_spec.h
+struct OneTreeState;  // one_tree_spec.h
+struct OneTreeArgs {
+    const OneTreeJob *jobs;  // [J]
+    OneTreeState *state;     // [J] the ascent between two launches
+    const float2 *xy;        // coordinate form
+    const float *dm_full;    // matrix form: the expanded n x n matrix (then xy is not read)
+    double *pi, *best_pi;    // [J][n] the penalties between two launches; those of the best 1-tree
+    uint32_t *best_par;      // [J][n] the best 1-tree's parents
+    uint32_t *tour_par;      // [J][n] the parents of the 1-tree that was a tour
+    double *log;             // [J][log_cap][3] (L_k, sum of g^2, lambda) or nullptr
+    uint32_t log_cap;
+    uint32_t n;
+    uint32_t span;           // iterations of this launch
+};
+size_t one_tree_lds_bytes(uint32_t n);     // key, pi, parent, degree: 24 n bytes
+uint32_t one_tree_max_n(int lds_bytes);    // the largest n whose state fits
+int one_tree_threads(uint32_t n);          // n in whole waves, 64 .. 1024
+hipError_t launch_one_tree_ascent(const OneTreeArgs &A, uint32_t jobs, int threads, hipStream_t s);  // one workgroup per job
+
 // lk.hip
 struct LkState {          // device-side state machine of the multi-CU LK variant
     uint32_t key;            // min pair index with a valid chain in the current scan (0xFFFFFFFF: none)

@@ -218,5 +218,5 @@ def validate_tour(tour_ids, problem):
     return ids == sorted(int(v) for v in problem.ids)
 
 
-from . import ant_colony, bellman_karp, branch_and_bound, christofides, cuckoo_search, flower_pollination, fourier_curve, genetic_algorithm, gravitational_search, greedy_edge, hill_climb, kohonen_som, lin_kernighan, multistart, nearest_neighbor, opt_tour, or_opt, particle_swarm, pipeline, savings, simulated_annealing, synth, tabu_search, three_opt, tsplib, two_opt  # noqa: E402,F401
+from . import ant_colony, bellman_karp, branch_and_bound, christofides, cuckoo_search, flower_pollination, fourier_curve, genetic_algorithm, gravitational_search, greedy_edge, hill_climb, kohonen_som, lin_kernighan, multistart, nearest_neighbor, one_tree_bound, opt_tour, or_opt, particle_swarm, pipeline, savings, simulated_annealing, synth, tabu_search, three_opt, tsplib, two_opt  # noqa: E402,F401
 from .simulated_annealing import SAOptions  # noqa: E402,F401

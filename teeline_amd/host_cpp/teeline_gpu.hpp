@@ -1636,6 +1636,54 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const BnbOptions 
 }
 }  // namespace branch_and_bound
 
+namespace one_tree_bound {  // the Held-Karp lower bound of DESIGN.md §4.29: not a solver and not the reference's (it computes no bound)
+struct BoundOptions {
+    size_t root = 0, iterations = 1000, patience = 10;
+    double lambda0 = 2.0;
+};
+struct Bound {
+    double bound = 0.0, upper = 0.0;
+    bool is_tour = false;
+    uint32_t job = 0;                   // of a batch: the first job with the largest bound
+    std::vector<double> bounds;         // every job's
+    std::vector<double> pi;             // the best penalties
+    std::vector<size_t> route;          // city ids where the 1-tree was a tour (the bound is then the optimum), else empty
+    tl_one_tree_result result{};
+    tl_stats stats{};
+    double gap_pct(double cost) const { return 100.0 * (cost - bound) / bound; }  // how far above the optimum a tour of this cost can be at most
+};
+// upper: the length of any tour (it scales the step).  One workgroup per option set, all at once; the best job's figures come back.
+inline Bound bound_batch(Context &ctx, const TspProblem &problem, double upper, const std::vector<BoundOptions> &jobs)
+{
+    if (jobs.empty()) throw std::runtime_error("one_tree_bound: no option set");
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size(), J = (uint32_t)jobs.size();
+    std::vector<tl_one_tree_opts> o;
+    for (const BoundOptions &j : jobs)
+        o.push_back(tl_one_tree_opts{(uint32_t)std::min<size_t>(j.root, 0xFFFFFFFFu), (uint32_t)std::min<size_t>(j.iterations, 0xFFFFFFFFu),
+                                     (uint32_t)std::min<size_t>(j.patience, 0xFFFFFFFFu), 0u, j.lambda0, upper, 0u});
+    std::vector<tl_one_tree_result> res(J);
+    std::vector<double> pi((size_t)J * std::max(n, 1u));
+    std::vector<uint32_t> tour((size_t)J * std::max(n, 1u));
+    Bound b;
+    ctx.check(tl_one_tree_bound_batch(ctx.get(), xy.data(), problem.explicit_packed(), n, o.data(), J, res.data(), pi.data(), nullptr, tour.data(), nullptr, 0u, &b.job,
+                                      &b.stats));
+    b.result = res[b.job];
+    b.bound = b.result.bound;
+    b.upper = upper;
+    b.is_tour = b.result.is_tour != 0u;
+    for (const tl_one_tree_result &r : res) b.bounds.push_back(r.bound);
+    b.pi.assign(pi.begin() + (size_t)b.job * n, pi.begin() + (size_t)(b.job + 1) * n);
+    if (b.is_tour)
+        for (uint32_t k = 0; k < n; ++k) b.route.push_back(problem.cities[tour[(size_t)b.job * n + k]].id);
+    return b;
+}
+inline Bound bound(Context &ctx, const TspProblem &problem, double upper, const BoundOptions &opts = BoundOptions{})
+{
+    return bound_batch(ctx, problem, upper, std::vector<BoundOptions>{opts});
+}
+}  // namespace one_tree_bound
+
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
 enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch, FlowerPollination, GravitationalSearch, KohonenSom, HillClimb, FourierCurve, BranchAndBound };
 
@@ -1920,9 +1968,32 @@ inline std::string json_f32(float v)
 }
 
 // print_solution_json (main.rs:700-712): serde_json::Value prints object keys sorted (BTreeMap: no preserve_order), compact
-inline std::string format_solution_json(const Solution &tour, bool is_optimized, const OptimalComparison *opt)
+inline std::string json_f64(double v)
 {
-    std::string s = "{\"cost\":" + json_f32(tour.total);
+    char buf[64];
+    auto r = std::to_chars(buf, buf + sizeof(buf), v);
+    std::string s(buf, r.ptr);
+    if (s.find_first_of(".eE") == std::string::npos) s += ".0";
+    return s;
+}
+
+// --lower-bound (not the reference's): the Held-Karp bound and the gap of the tour's cost to it, in percent, as f64
+inline std::string format_lower_bound(float solver_cost, const one_tree_bound::Bound &lb)
+{
+    char buf[160];
+    std::snprintf(buf, sizeof(buf), "bound=%.17g\ngap_pct=%.4f\n", lb.bound, lb.gap_pct((double)solver_cost));
+    return std::string(buf) + (lb.is_tour ? "proved=1\n" : "");
+}
+
+// lb (--lower-bound): adds "bound" and "gap_pct" (f64); beside an optimal comparison, whose "gap_pct" keeps its key, the bound's gap
+// is "bound_gap_pct"
+inline std::string format_solution_json(const Solution &tour, bool is_optimized, const OptimalComparison *opt, const one_tree_bound::Bound *lb = nullptr)
+{
+    std::string s = "{";
+    if (lb) s += "\"bound\":" + json_f64(lb->bound) + ",";
+    if (lb && opt) s += "\"bound_gap_pct\":" + json_f64(lb->gap_pct((double)tour.total)) + ",";
+    s += "\"cost\":" + json_f32(tour.total);
+    if (lb && !opt) s += ",\"gap_pct\":" + json_f64(lb->gap_pct((double)tour.total));
     if (opt) s += ",\"gap_pct\":" + json_f32(opt->gap_pct) + ",\"optimal_cost\":" + json_f32(opt->optimal_cost);
     s += std::string(",\"optimized\":") + (is_optimized ? "true" : "false") + ",\"route\":[";
     for (size_t k = 0; k < tour.route().size(); ++k) {

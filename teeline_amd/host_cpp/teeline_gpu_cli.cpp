@@ -1,6 +1,10 @@
 // teeline-gpu — CLI façade over the GPU path, mirroring teeline-cli (teeline-cli/src/main.rs) for the solvers this build
 // accelerates: same sub-commands, same flags, byte-identical stdout.
 //
+//   teeline-gpu bound -i FILE [--upper U | --tour FILE] [--root R] [--iterations T] [--lambda L,L,..] [--patience P,P,..]
+//               [--output-format text|json]: the Held-Karp lower bound, the lists a grid of jobs; prints the best
+//               bound, its job, the upper bound used and the gap in percent, `proved=1` where the 1-tree is a tour
+//   solve / pipeline --lower-bound: the bound with the solved tour as upper; `bound` and `gap_pct` on stderr (text) or in the JSON object
 //   teeline-gpu solve <solver|preset> [-i FILE] [--no-seed] [--output-format text|json] [--optimal-tour FILE]
 //                                     [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P] [--n_nearest K] [--max-depth D]
 //   teeline-gpu pipeline --steps=nn,2opt,... [-i FILE] [same options]
@@ -77,6 +81,12 @@ struct Args {
     int device = 0, repeat = 1;
     pipeline::StageOptions opt;
     std::vector<double> fourier_lambdas, fourier_lrs;  // --lambda / --lr comma lists: their product is a fourier_curve batch
+    // `bound` (the Held-Karp lower bound) and --lower-bound on solve / pipeline
+    bool lower_bound = false;
+    double upper = 0.0;                  // --upper U; 0: from --tour FILE, else from nn -> 2opt
+    std::string tour_file;
+    one_tree_bound::BoundOptions bound_opt;
+    std::vector<double> bound_patiences;  // --patience P,P,..: with --lambda L,L,.. a grid of jobs, lambda the outer index
 };
 
 [[noreturn]] void usage_exit(const char *why)
@@ -92,6 +102,8 @@ struct Args {
                  "                         [--alpha A] [--beta B] [--evaporation-rate R] [--num-ants N] [--runs K]\n"
                  "                         [--max-nodes N] [--time-limit-ms T]\n"
                  "       teeline-gpu pipeline --steps=nn,2opt,... | --steps=greedy_edge,2opt,... | --steps=savings,2opt,... | --steps=christofides,lk,... [-i FILE] [options as above]\n"
+                 "       teeline-gpu bound -i FILE [--upper U | --tour FILE] [--root R] [--iterations T] [--lambda L,L,...] [--patience P,P,...] [--output-format text|json]\n"
+                 "       solve and pipeline also take --lower-bound: the Held-Karp bound with the solved tour as upper, `bound` and `gap_pct` on stderr or in the JSON object\n"
                  "       teeline-gpu solvers [--short]\n");
     std::exit(2);  // clap's usage-error exit code
 }
@@ -120,7 +132,7 @@ Args parse(int argc, char **argv)
         if (argc < 3 || argv[2][0] == '-') usage_exit("solve: SOLVER_NAME is required");
         a.solver = argv[2];
         i = 3;
-    } else if (a.cmd != "pipeline" && a.cmd != "solvers") {
+    } else if (a.cmd != "pipeline" && a.cmd != "solvers" && a.cmd != "bound") {
         usage_exit("unknown sub-command");
     }
     for (; i < argc; ++i) {
@@ -185,6 +197,20 @@ Args parse(int argc, char **argv)
                 at = comma + 1;
             }
         }
+        else if (s == "--lower-bound" || s == "--lower_bound") a.lower_bound = true;
+        else if (s == "--upper") a.upper = std::stod(val());
+        else if (s == "--tour") a.tour_file = val();
+        else if (s == "--root") a.bound_opt.root = parse_usize(s, val());
+        else if (s == "--iterations") a.bound_opt.iterations = parse_usize(s, val());
+        else if (s == "--patience") {
+            const std::string v = val();
+            a.bound_patiences.clear();
+            for (size_t at = 0; at <= v.size();) {
+                const size_t comma = std::min(v.find(',', at), v.size());
+                a.bound_patiences.push_back((double)parse_usize(s, v.substr(at, comma - at)));
+                at = comma + 1;
+            }
+        }
         else if (s == "--progress-digest") a.progress_digest = true;
         else if (s == "--timing") a.timing = true;
         else if (s == "--full-exit") a.full_exit = true;
@@ -194,6 +220,11 @@ Args parse(int argc, char **argv)
     if (a.output_format != "text" && a.output_format != "json") usage_exit("--output-format: text or json");
     if (!a.fourier_lambdas.empty()) a.opt.fourier.lambda = a.fourier_lambdas[0];
     if (!a.fourier_lrs.empty()) a.opt.fourier.lr = a.fourier_lrs[0];
+    if (a.cmd == "bound") {
+        if (a.file.empty()) usage_exit("bound: -i FILE is required");
+        if (a.upper != 0.0 && !a.tour_file.empty()) usage_exit("bound: --upper or --tour, not both");
+        return a;  // (--lambda is lambda0's list here, not the Fourier curve's)
+    }
     if (a.fourier_lambdas.size() > 1 || a.fourier_lrs.size() > 1) {  // the grid, lambda the outer index: one job each, the best kept
         const std::vector<double> las = a.fourier_lambdas.empty() ? std::vector<double>{a.opt.fourier.lambda} : a.fourier_lambdas;
         const std::vector<double> lrs = a.fourier_lrs.empty() ? std::vector<double>{a.opt.fourier.lr} : a.fourier_lrs;
@@ -313,7 +344,9 @@ int run(int argc, char **argv)
         }
         std::vector<Solvers> stages;
         const bool json_mode = a.cmd == "solve" && a.output_format == "json";  // `pipeline` always prints text (main.rs:425,430)
-        if (a.cmd == "solve") {
+        if (a.cmd == "bound") {
+            stages = {Solvers::NearestNeighbor, Solvers::TwoOpt};  // where neither --upper nor --tour gives the upper bound
+        } else if (a.cmd == "solve") {
             std::string name = a.solver;
             for (auto &ch : name) ch = (char)std::tolower((unsigned char)ch);
             if (name == "fast") stages = {Solvers::NearestNeighbor, Solvers::TwoOpt};  // resolve_preset (main.rs:354-369)
@@ -407,6 +440,42 @@ int run(int argc, char **argv)
             std::memcpy(&bits, &v, 4);
             dg.word(k == 0 ? bits : 0u, 4);
         };
+        if (a.cmd == "bound") {
+            double upper = a.upper;
+            std::string upper_from = "--upper";
+            if (!a.tour_file.empty()) {  // the tour's length by tl_tour_length, as --optimal-tour prices one
+                cli::OptimalComparison cmp;
+                if (!cli::compute_optimal_comparison(ctx, 0.0f, problem, opt_tour::read_from_file(a.tour_file), cmp) || !(cmp.optimal_cost > 0.0f)) {
+                    std::fprintf(stderr, "error: bound: --tour: no tour of this instance in `%s`\n", a.tour_file.c_str());
+                    return 1;
+                }
+                upper = (double)cmp.optimal_cost;
+                upper_from = "--tour";
+            } else if (upper == 0.0) {
+                upper = (double)pipeline::run_pipeline_stages(ctx, problem, stages, a.opt).back().solution.total;
+                upper_from = "nn,2opt";
+            }
+            const std::vector<double> las = a.fourier_lambdas.empty() ? std::vector<double>{a.bound_opt.lambda0} : a.fourier_lambdas;
+            const std::vector<double> pats = a.bound_patiences.empty() ? std::vector<double>{(double)a.bound_opt.patience} : a.bound_patiences;
+            std::vector<one_tree_bound::BoundOptions> jobs;
+            for (double la : las)
+                for (double pa : pats) {
+                    one_tree_bound::BoundOptions o = a.bound_opt;
+                    o.lambda0 = la;
+                    o.patience = (size_t)pa;
+                    jobs.push_back(o);
+                }
+            const one_tree_bound::Bound b = one_tree_bound::bound_batch(ctx, problem, upper, jobs);
+            const one_tree_bound::BoundOptions &bo = jobs[b.job];
+            if (a.output_format == "json")
+                std::printf("{\"bound\":%s,\"gap_pct\":%s,\"iterations_run\":%u,\"job\":%u,\"jobs\":%zu,\"lambda\":%s,\"patience\":%zu,\"proved\":%s,\"upper\":%s,\"upper_from\":\"%s\"}\n",
+                            cli::json_f64(b.bound).c_str(), cli::json_f64(b.gap_pct(upper)).c_str(), b.result.iterations_run, b.job, jobs.size(),
+                            cli::json_f64(bo.lambda0).c_str(), bo.patience, b.is_tour ? "true" : "false", cli::json_f64(upper).c_str(), upper_from.c_str());
+            else
+                std::printf("bound=%.17g job=%u of %zu (lambda=%g patience=%zu) upper=%.17g (%s) gap_pct=%.4f%s\n", b.bound, b.job, jobs.size(), bo.lambda0, bo.patience,
+                            upper, upper_from.c_str(), b.gap_pct(upper), b.is_tour ? " proved=1" : "");
+            return 0;
+        }
         if (a.progress_digest) a.opt.progress = &on_progress;
         std::string runs_json;
         std::vector<pipeline::StageOutcome> outcomes;
@@ -434,8 +503,11 @@ int run(int argc, char **argv)
         if (!json_mode) std::fputs(cli::format_solution(tour, false).c_str(), stdout);
         cli::OptimalComparison cmp;
         const bool have_cmp = have_opt && cli::compute_optimal_comparison(ctx, tour.total, problem, ot, cmp);
-        if (json_mode) std::fputs(cli::format_solution_json(tour, false, have_cmp ? &cmp : nullptr).c_str(), stdout);
+        one_tree_bound::Bound lb;
+        if (a.lower_bound) lb = one_tree_bound::bound(ctx, problem, (double)tour.total);  // the solved tour is the upper bound
+        if (json_mode) std::fputs(cli::format_solution_json(tour, false, have_cmp ? &cmp : nullptr, a.lower_bound ? &lb : nullptr).c_str(), stdout);
         else if (have_cmp) std::fputs(cli::format_optimal_comparison(tour.total, cmp).c_str(), stderr);
+        if (a.lower_bound && !json_mode) std::fputs(cli::format_lower_bound(tour.total, lb).c_str(), stderr);
         if (a.timing) {
             std::fflush(stdout);
             std::fprintf(stderr, "{\"timing_ms\": {\"before_main\": %.1f, \"read_input\": %.4f, \"tl_create\": %.4f, \"problem\": %.4f, \"runs\": [%s], \"output\": %.4f, \"main_total\": %.4f}, \"n\": %zu}\n",
