@@ -182,18 +182,199 @@ inline bool validate_tour(const std::vector<size_t> &tour, const std::vector<KDP
     return a == b;
 }
 
-namespace detail {
+namespace detail {  // what the solves share; the seeded solvers' frame reads side by side with host/_chains.py
+inline bool live(const ProgressFn *tx) { return tx && *tx; }
+
 inline Solution finish(const TspProblem &p, const std::vector<uint32_t> &pos, float cost, const tl_stats &st, const ProgressFn *tx)
 {
     Solution s;
     s.total = cost;
     s.stats = st;
     for (uint32_t q : pos) s.route_.push_back(p.cities[q].id);
-    if (tx && *tx) {
+    if (live(tx)) {
         (*tx)(ProgressKind::PathUpdate, s.route_, cost);
         (*tx)(ProgressKind::Done, s.route_, cost);
     }
     return s;
+}
+
+// The prologue of a solve: the instance as the C ABI takes it, the start tour as positions (ip == nullptr: city order) and where
+// the result lands
+struct Call {
+    std::vector<float> xy;
+    uint32_t n;
+    const float *packed;
+    std::vector<uint32_t> init, out;
+    const uint32_t *ip = nullptr;
+    float cost = 0.f;
+    tl_stats st{};
+
+    Call(const TspProblem &problem, const std::vector<size_t> *init_tour)
+        : xy(problem.xy()), n((uint32_t)problem.cities.size()), packed(problem.explicit_packed()), out(n)
+    {
+        if (!init_tour) return;
+        init = problem.positions_of(*init_tour);
+        ip = init.data();
+    }
+    Call(const Call &) = delete;
+    Call &operator=(const Call &) = delete;
+    std::vector<uint32_t> start_tour() const  // the tour a descent or a chain starts from: the given positions, or city order
+    {
+        std::vector<uint32_t> pos(n);
+        for (uint32_t q = 0; q < n; ++q) pos[q] = ip ? init[q] : q;
+        return pos;
+    }
+};
+
+// the result of a call that has sent its own PathUpdates, and Done
+inline Solution finish_done(const TspProblem &p, const Call &c, const ProgressFn *tx, bool done = true)
+{
+    Solution s = finish(p, c.out, c.cost, c.st, nullptr);
+    if (done) (*tx)(ProgressKind::Done, s.route_, c.cost);
+    return s;
+}
+
+// call(cap, &len) runs a trace entry with room for cap records; where it had more (len > cap) it runs again with room for all:
+// every solver is deterministic, so the second run has the same records.  Returns len.
+template <class F> uint32_t grow_trace(uint32_t cap, F &&call)
+{
+    uint32_t len = 0;
+    for (;;) {
+        call(cap, &len);
+        if (len <= cap) break;
+        cap = len;
+    }
+    return len;
+}
+
+inline float bits_to_f32(uint32_t bits)  // the f32 a trace record carries as a u32
+{
+    float v;
+    std::memcpy(&v, &bits, 4);
+    return v;
+}
+
+// send(pos, d): n positions -> city ids -> PathUpdate(route, d)
+inline auto route_sender(const TspProblem &problem, const ProgressFn *tx)
+{
+    return [&problem, tx, route = std::vector<size_t>(problem.cities.size())](const uint32_t *pos, float d) mutable {
+        for (size_t q = 0; q < route.size(); ++q) route[q] = problem.cities[pos[q]].id;
+        (*tx)(ProgressKind::PathUpdate, route, d);
+    };
+}
+
+// KDPoint::distance (kdtree.rs:291-295) of the cities at positions p and q: separate roundings, correctly rounded sqrt.  The
+// volatile intermediates are the rounding specification: no product may be fused into the sum.
+inline float dist_f32(const std::vector<float> &xy, uint32_t p, uint32_t q)
+{
+    if (p == q) return 0.0f;
+    const volatile float dx = xy[2 * p] - xy[2 * q], dy = xy[2 * p + 1] - xy[2 * q + 1];
+    const volatile float sx = dx * dx, sy = dy * dy;
+    const volatile float ss = sx + sy;
+    return std::sqrt((float)ss);
+}
+
+// A population of tours, each refined by its own descent: population(c, init, count, out, costs, moves, &st) is the entry of
+// 2-opt, 3-opt or Or-opt; element k equals that solver's solve(ctx, problem, {}, nullptr, &init_tours[k]).
+template <class P>
+std::vector<Solution> solve_population(const TspProblem &problem, const std::vector<std::vector<size_t>> &init_tours, std::vector<uint32_t> *moves, P &&population)
+{
+    Call c(problem, nullptr);
+    const uint32_t n = c.n, count = (uint32_t)init_tours.size();
+    std::vector<uint32_t> init((size_t)count * n), out((size_t)count * n), mv(count);
+    for (uint32_t k = 0; k < count; ++k) {
+        const auto pos = problem.positions_of(init_tours[k]);
+        std::copy(pos.begin(), pos.end(), init.begin() + (size_t)k * n);
+    }
+    std::vector<float> costs(count);
+    population(c, init.data(), count, out.data(), costs.data(), mv.data(), &c.st);
+    std::vector<Solution> res;
+    for (uint32_t k = 0; k < count; ++k) {
+        std::vector<uint32_t> one(out.begin() + (size_t)k * n, out.begin() + (size_t)(k + 1) * n);
+        res.push_back(finish(problem, one, costs[k], c.st, nullptr));
+    }
+    if (moves) *moves = mv;
+    return res;
+}
+
+// What greedy edge, savings and Christofides send: fewer than min_n cities, Done alone; otherwise the identity (cities in file
+// order) with 0.0 before the selection, then the route with its length, then Done
+inline void construction_messages(const TspProblem &problem, const Solution &s, const ProgressFn *tx, uint32_t min_n)
+{
+    if (!live(tx)) return;
+    if (problem.cities.size() >= min_n) {
+        std::vector<size_t> identity;
+        for (auto &c : problem.cities) identity.push_back(c.id);
+        (*tx)(ProgressKind::PathUpdate, identity, 0.0f);
+        (*tx)(ProgressKind::PathUpdate, s.route_, s.total);
+    }
+    (*tx)(ProgressKind::Done, s.route_, s.total);
+}
+
+// _chains.solve_chains.  count > 1: population(count, outs, costs, moves, &best) runs the chains (or runs) at once into c.st and the
+// best one (lowest cost, then lowest index) is kept, st.moves its own where the entry has a moves array (has_moves; else moves is
+// nullptr); with a channel that one runs once more, alone, for its trace.  Else single(), or with a channel the trace of chain 0.
+// trace_and_replay(chain) runs the trace entry into c.out / c.cost / c.st and sends the reference's messages short of Done, which
+// follows here unless done is false.
+template <class P, class S, class T>
+Solution solve_chains(const TspProblem &problem, Call &c, const ProgressFn *tx, uint32_t count, bool has_moves, P &&population, S &&single, T &&trace_and_replay,
+                      bool done = true)
+{
+    uint32_t best = 0;
+    if (count > 1) {
+        std::vector<uint32_t> outs((size_t)count * c.n), moves(count);
+        std::vector<float> costs(count);
+        population(count, outs.data(), costs.data(), has_moves ? moves.data() : nullptr, &best);
+        std::copy(outs.begin() + (size_t)best * c.n, outs.begin() + (size_t)(best + 1) * c.n, c.out.begin());
+        c.cost = costs[best];
+        if (has_moves) c.st.moves = moves[best];
+        if (!live(tx)) return finish(problem, c.out, c.cost, c.st, nullptr);
+    } else if (!live(tx)) {
+        single();
+        return finish(problem, c.out, c.cost, c.st, nullptr);
+    }
+    trace_and_replay(best);
+    return finish_done(problem, c, tx, done);
+}
+
+// _chains.solve_swarm: solve_chains over the three entries of one population solver (particle_swarm, cuckoo_search,
+// flower_pollination, gravitational_search), `o` its opts struct.  The trace's log (epoch, who, cost bits, route index) and routes
+// grow until they hold every improvement; the replay is the reference's: PathUpdate(start best), per epoch its improvements in order
+// and EpochUpdate(epoch), then Done.
+template <class Opts>
+Solution solve_swarm(Context &ctx, const TspProblem &problem, const ProgressFn *tx, const std::vector<size_t> *init_tour, uint64_t seed, uint32_t runs, const Opts &o,
+                     int (*single_fn)(tl_ctx *, const float *, uint32_t, const float *, const uint32_t *, const Opts *, uint64_t, uint32_t *, float *, tl_stats *),
+                     int (*trace_fn)(tl_ctx *, const float *, uint32_t, const float *, const uint32_t *, const Opts *, uint64_t, uint32_t, uint32_t *, float *, tl_stats *,
+                                     uint32_t *, uint32_t, uint32_t *, uint32_t *, uint32_t, uint32_t *, uint32_t),
+                     int (*population_fn)(tl_ctx *, const float *, uint32_t, const float *, const uint32_t *, uint32_t, uint32_t, uint32_t, const Opts *, uint64_t,
+                                          uint32_t *, float *, uint32_t *, uint32_t *, tl_stats *))
+{
+    Call c(problem, init_tour);
+    const uint32_t n = c.n;
+    return solve_chains(
+        problem, c, tx, runs, false,
+        [&](uint32_t count, uint32_t *outs, float *costs, uint32_t *moves, uint32_t *best) {
+            ctx.check(population_fn(ctx.get(), c.xy.data(), n, c.packed, c.ip, c.ip ? 1u : 0u, 0u, count, &o, seed, outs, costs, moves, best, &c.st));
+        },
+        [&] { ctx.check(single_fn(ctx.get(), c.xy.data(), n, c.packed, c.ip, &o, seed, c.out.data(), &c.cost, &c.st)); },
+        [&](uint32_t run) {
+            std::vector<uint32_t> log, routes;
+            const uint32_t rows = grow_trace(64u, [&](uint32_t cap, uint32_t *got) {  // the improvements are few but not known in advance
+                log.assign((size_t)cap * 4, 0u);
+                routes.assign((size_t)cap * std::max(n, 1u), 0u);
+                ctx.check(trace_fn(ctx.get(), c.xy.data(), n, c.packed, c.ip, &o, seed, run, c.out.data(), &c.cost, &c.st, log.data(), cap, got, routes.data(), cap,
+                                   nullptr, 0u));
+            });
+            auto send = route_sender(problem, tx);
+            const auto path_update = [&](uint32_t k) { send(routes.data() + (size_t)k * n, bits_to_f32(log[(size_t)k * 4 + 2])); };
+            if (rows == 0) return;
+            path_update(0);
+            uint32_t k = 1;
+            for (uint32_t e = 0; e < o.epochs; ++e) {
+                for (; k < rows && log[(size_t)k * 4] == e; ++k) path_update(k);
+                (*tx)(ProgressKind::EpochUpdate, std::vector<size_t>{e}, 0.0f);
+            }
+        });
 }
 }  // namespace detail
 
@@ -201,42 +382,24 @@ namespace two_opt {  // two_opt.rs:7-67
 inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions & /*_opts*/, const ProgressFn *progress_tx,
                       const std::vector<size_t> *init_tour, int mode = TL_MODE_REF_ORDER)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
-    std::vector<uint32_t> init, out(n);
-    if (init_tour) init = problem.positions_of(*init_tour);
-    float cost = 0.f;
-    tl_stats st{};
+    detail::Call c(problem, init_tour);
+    const uint32_t n = c.n;
     // With a progress callback the descent also lists its moves (tl_two_opt_trace) and the reference's exact message sequence —
     // CityChange(path[i]) per outer i of every sweep, PathUpdate(path, new_distance) per move (two_opt.rs:30-32,53-56) — is
     // replayed from them once the kernel is back (coordinates within the LDS-resident descent, or problem.distances of a GEO /
     // EXPLICIT problem); otherwise the final PathUpdate (detail::finish).
-    const float *packed = problem.explicit_packed();
-    if (progress_tx && *progress_tx && mode == TL_MODE_REF_ORDER && n >= 3 && n <= 65535u &&
-        (packed || n <= tl_two_opt_lds_max_n(ctx.get()))) {
-        std::vector<size_t> route;
-        std::vector<uint32_t> pos(n);
-        for (uint32_t q = 0; q < n; ++q) pos[q] = init_tour ? init[q] : q;
-        for (uint32_t q : pos) route.push_back(problem.cities[q].id);
-        (*progress_tx)(ProgressKind::PathUpdate, route, 0.0f);  // :22-24
-        uint32_t cap = std::max<uint32_t>(64u, 16u * n), len = 0;
-        std::vector<uint32_t> log;
-        for (;;) {
+    if (detail::live(progress_tx) && mode == TL_MODE_REF_ORDER && n >= 3 && n <= 65535u && (c.packed || n <= tl_two_opt_lds_max_n(ctx.get()))) {
+        auto send = detail::route_sender(problem, progress_tx);
+        std::vector<uint32_t> pos = c.start_tour(), log;
+        send(pos.data(), 0.0f);  // :22-24
+        const uint32_t len = detail::grow_trace(std::max<uint32_t>(64u, 16u * n), [&](uint32_t cap, uint32_t *got) {
             log.assign(cap, 0u);
-            ctx.check(tl_two_opt_trace(ctx.get(), xy.data(), n, packed, init_tour ? init.data() : nullptr, out.data(), &cost, &st, log.data(), cap, &len));
-            if (len <= cap) break;
-            cap = len;  // the descent is deterministic: once more with room for every move
-        }
-        auto d = [&](uint32_t p, uint32_t q) -> float {  // problem.distances, or KDPoint::distance (kdtree.rs:291-295): separate roundings, correctly rounded sqrt
-            if (packed) return problem.distances.distance_by_pos(p, q);
-            const volatile float dx = xy[2 * p] - xy[2 * q], dy = xy[2 * p + 1] - xy[2 * q + 1];
-            const volatile float sx = dx * dx, sy = dy * dy;
-            const volatile float ss = sx + sy;
-            return std::sqrt((float)ss);
-        };
+            ctx.check(tl_two_opt_trace(ctx.get(), c.xy.data(), n, c.packed, c.ip, c.out.data(), &c.cost, &c.st, log.data(), cap, got));
+        });
+        auto d = [&](uint32_t p, uint32_t q) { return c.packed ? problem.distances.distance_by_pos(p, q) : detail::dist_f32(c.xy, p, q); };
         size_t k = 0;
         std::vector<size_t> one(1);
-        for (uint64_t sw = 0; sw < st.sweeps; ++sw, k += (k < len && log[k] == TL_TRACE_SWEEP) ? 1 : 0)
+        for (uint64_t sw = 0; sw < c.st.sweeps; ++sw, k += (k < len && log[k] == TL_TRACE_SWEEP) ? 1 : 0)
             for (uint32_t i = 0; i + 3 < n; ++i) {
                 one[0] = problem.cities[pos[i]].id;
                 (*progress_tx)(ProgressKind::CityChange, one, 0.0f);
@@ -244,42 +407,24 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOp
                     const uint32_t j = log[k] & 0xFFFFu;
                     const float new_distance = d(pos[i], pos[j]) + d(pos[i + 1], pos[j + 1]);
                     std::reverse(pos.begin() + i + 1, pos.begin() + j + 1);
-                    for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[pos[q]].id;
-                    (*progress_tx)(ProgressKind::PathUpdate, route, new_distance);
+                    send(pos.data(), new_distance);
                     ++k;
                 }
             }
-        Solution s;
-        s.total = cost;
-        s.stats = st;
-        for (uint32_t q : out) s.route_.push_back(problem.cities[q].id);
-        (*progress_tx)(ProgressKind::Done, s.route_, cost);
-        return s;
+        return detail::finish_done(problem, c, progress_tx);
     }
-    ctx.check(tl_two_opt(ctx.get(), xy.data(), n, problem.explicit_packed(), init_tour ? init.data() : nullptr, mode, out.data(), &cost, &st));
-    return detail::finish(problem, out, cost, st, progress_tx);
+    ctx.check(tl_two_opt(ctx.get(), c.xy.data(), n, c.packed, c.ip, mode, c.out.data(), &c.cost, &c.st));
+    return detail::finish(problem, c.out, c.cost, c.st, progress_tx);
 }
 
 // A population of tours, each refined by its own descent, all concurrently (tl_two_opt_population);
 // element k equals solve(ctx, problem, {}, nullptr, &init_tours[k]).
 inline std::vector<Solution> solve_population(Context &ctx, const TspProblem &problem, const std::vector<std::vector<size_t>> &init_tours)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size(), count = (uint32_t)init_tours.size();
-    std::vector<uint32_t> init((size_t)count * n), out((size_t)count * n);
-    for (uint32_t k = 0; k < count; ++k) {
-        const auto pos = problem.positions_of(init_tours[k]);
-        std::copy(pos.begin(), pos.end(), init.begin() + (size_t)k * n);
-    }
-    std::vector<float> costs(count);
-    tl_stats st{};
-    ctx.check(tl_two_opt_population(ctx.get(), xy.data(), n, problem.explicit_packed(), init.data(), count, out.data(), costs.data(), &st));
-    std::vector<Solution> res;
-    for (uint32_t k = 0; k < count; ++k) {
-        std::vector<uint32_t> one(out.begin() + (size_t)k * n, out.begin() + (size_t)(k + 1) * n);
-        res.push_back(detail::finish(problem, one, costs[k], st, nullptr));
-    }
-    return res;
+    return detail::solve_population(problem, init_tours, nullptr,
+                                    [&](const detail::Call &c, const uint32_t *init, uint32_t count, uint32_t *out, float *costs, uint32_t *, tl_stats *st) {
+                                        ctx.check(tl_two_opt_population(ctx.get(), c.xy.data(), c.n, c.packed, init, count, out, costs, st));
+                                    });
 }
 }  // namespace two_opt
 
@@ -307,43 +452,27 @@ inline void apply_3opt(std::vector<uint32_t> &path, uint32_t i, uint32_t j, uint
 inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions &, const ProgressFn *progress_tx,
                       const std::vector<size_t> *init_tour)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
-    std::vector<uint32_t> init, out(n);
-    if (init_tour) init = problem.positions_of(*init_tour);
-    float cost = 0.f;
-    tl_stats st{};
-    if (!(progress_tx && *progress_tx) || n < 4) {  // (n < 4: the reference returns before its first message, three_opt.rs:25-28)
-        ctx.check(tl_three_opt(ctx.get(), xy.data(), n, problem.explicit_packed(), init_tour ? init.data() : nullptr, out.data(), &cost, &st));
-        return detail::finish(problem, out, cost, st, nullptr);
+    detail::Call c(problem, init_tour);
+    const uint32_t n = c.n;
+    if (!detail::live(progress_tx) || n < 4) {  // (n < 4: the reference returns before its first message, three_opt.rs:25-28)
+        ctx.check(tl_three_opt(ctx.get(), c.xy.data(), n, c.packed, c.ip, c.out.data(), &c.cost, &c.st));
+        return detail::finish(problem, c.out, c.cost, c.st, nullptr);
     }
     // With a progress callback the solve also lists its moves (tl_three_opt_trace) and the reference's message sequence — the
     // start path, the path after every apply_3opt (each with 0.0), Done (three_opt.rs:34,42,47-49) — is replayed from them.
-    uint32_t cap = std::max<uint32_t>(64u, 4u * n), len = 0;
     std::vector<uint32_t> log;
-    for (;;) {
+    const uint32_t len = detail::grow_trace(std::max<uint32_t>(64u, 4u * n), [&](uint32_t cap, uint32_t *got) {
         log.assign((size_t)cap * 4, 0u);
-        ctx.check(tl_three_opt_trace(ctx.get(), xy.data(), n, problem.explicit_packed(), init_tour ? init.data() : nullptr, out.data(), &cost, &st,
-                                     log.data(), cap, &len));
-        if (len <= cap) break;
-        cap = len;  // deterministic: once more with room for every move
-    }
-    std::vector<uint32_t> pos(n);
-    for (uint32_t q = 0; q < n; ++q) pos[q] = init_tour ? init[q] : q;
-    std::vector<size_t> route(n);
-    auto send = [&]() {
-        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[pos[q]].id;
-        (*progress_tx)(ProgressKind::PathUpdate, route, 0.0f);
-    };
-    send();
+        ctx.check(tl_three_opt_trace(ctx.get(), c.xy.data(), n, c.packed, c.ip, c.out.data(), &c.cost, &c.st, log.data(), cap, got));
+    });
+    auto send = detail::route_sender(problem, progress_tx);
+    std::vector<uint32_t> pos = c.start_tour();
+    send(pos.data(), 0.0f);
     for (uint32_t m = 0; m < len; ++m) {
-        const uint32_t i = log[4 * m], j = log[4 * m + 1], k = log[4 * m + 2], kase = log[4 * m + 3];
-        apply_3opt(pos, i, j, k, kase);
-        send();
+        apply_3opt(pos, log[4 * m], log[4 * m + 1], log[4 * m + 2], log[4 * m + 3]);
+        send(pos.data(), 0.0f);
     }
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    return s;
+    return detail::finish_done(problem, c, progress_tx);
 }
 
 // A population of tours, each refined by its own descent (tl_three_opt_population: one workgroup per tour or tour after tour, the
@@ -351,23 +480,10 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOp
 inline std::vector<Solution> solve_population(Context &ctx, const TspProblem &problem, const std::vector<std::vector<size_t>> &init_tours,
                                               std::vector<uint32_t> *moves = nullptr)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size(), count = (uint32_t)init_tours.size();
-    std::vector<uint32_t> init((size_t)count * n), out((size_t)count * n), mv(count);
-    for (uint32_t k = 0; k < count; ++k) {
-        const auto pos = problem.positions_of(init_tours[k]);
-        std::copy(pos.begin(), pos.end(), init.begin() + (size_t)k * n);
-    }
-    std::vector<float> costs(count);
-    tl_stats st{};
-    ctx.check(tl_three_opt_population(ctx.get(), xy.data(), n, problem.explicit_packed(), init.data(), count, out.data(), costs.data(), mv.data(), &st));
-    std::vector<Solution> res;
-    for (uint32_t k = 0; k < count; ++k) {
-        std::vector<uint32_t> one(out.begin() + (size_t)k * n, out.begin() + (size_t)(k + 1) * n);
-        res.push_back(detail::finish(problem, one, costs[k], st, nullptr));
-    }
-    if (moves) *moves = mv;
-    return res;
+    return detail::solve_population(problem, init_tours, moves,
+                                    [&](const detail::Call &c, const uint32_t *init, uint32_t count, uint32_t *out, float *costs, uint32_t *mv, tl_stats *st) {
+                                        ctx.check(tl_three_opt_population(ctx.get(), c.xy.data(), c.n, c.packed, init, count, out, costs, mv, st));
+                                    });
 }
 }  // namespace three_opt
 
@@ -388,14 +504,7 @@ inline float tour_length_f32(const TspProblem &problem, const std::vector<float>
 {
     if (pos.size() < 2) return 0.0f;
     const bool have_dm = problem.distances.num_cities() == pos.size();
-    auto d = [&](uint32_t p, uint32_t q) -> float {
-        if (have_dm) return problem.distances.distance_by_pos(p, q);
-        if (p == q) return 0.0f;
-        const volatile float dx = xy[2 * p] - xy[2 * q], dy = xy[2 * p + 1] - xy[2 * q + 1];
-        const volatile float sx = dx * dx, sy = dy * dy;
-        const volatile float ss = sx + sy;
-        return std::sqrt((float)ss);
-    };
+    auto d = [&](uint32_t p, uint32_t q) { return have_dm ? problem.distances.distance_by_pos(p, q) : detail::dist_f32(xy, p, q); };
     volatile float total = d(pos.back(), pos.front());
     for (size_t k = 0; k + 1 < pos.size(); ++k) total = total + d(pos[k], pos[k + 1]);
     return total;
@@ -404,42 +513,27 @@ inline float tour_length_f32(const TspProblem &problem, const std::vector<float>
 inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions &, const ProgressFn *progress_tx,
                       const std::vector<size_t> *init_tour)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
-    std::vector<uint32_t> init, out(n);
-    if (init_tour) init = problem.positions_of(*init_tour);
-    float cost = 0.f;
-    tl_stats st{};
-    if (!(progress_tx && *progress_tx) || n < 4) {  // (n < 4: the reference returns before its first message, or_opt.rs:31-34)
-        ctx.check(tl_or_opt(ctx.get(), xy.data(), n, problem.explicit_packed(), init_tour ? init.data() : nullptr, out.data(), &cost, &st));
-        return detail::finish(problem, out, cost, st, nullptr);
+    detail::Call c(problem, init_tour);
+    const uint32_t n = c.n;
+    if (!detail::live(progress_tx) || n < 4) {  // (n < 4: the reference returns before its first message, or_opt.rs:31-34)
+        ctx.check(tl_or_opt(ctx.get(), c.xy.data(), n, c.packed, c.ip, c.out.data(), &c.cost, &c.st));
+        return detail::finish(problem, c.out, c.cost, c.st, nullptr);
     }
     // With a progress callback the solve also lists its moves (tl_or_opt_trace) and the reference's message sequence — the start
     // path (0.0), the path and its tour_length after every apply_relocation, Done (or_opt.rs:40-42,62-67,70-72) — is replayed.
-    uint32_t cap = std::max<uint32_t>(64u, 4u * n), len = 0;
     std::vector<uint32_t> log;
-    for (;;) {
+    const uint32_t len = detail::grow_trace(std::max<uint32_t>(64u, 4u * n), [&](uint32_t cap, uint32_t *got) {
         log.assign((size_t)cap * 4, 0u);
-        ctx.check(tl_or_opt_trace(ctx.get(), xy.data(), n, problem.explicit_packed(), init_tour ? init.data() : nullptr, out.data(), &cost, &st,
-                                  log.data(), cap, &len));
-        if (len <= cap) break;
-        cap = len;  // deterministic: once more with room for every move
-    }
-    std::vector<uint32_t> pos(n);
-    for (uint32_t q = 0; q < n; ++q) pos[q] = init_tour ? init[q] : q;
-    std::vector<size_t> route(n);
-    auto send = [&](float d) {
-        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[pos[q]].id;
-        (*progress_tx)(ProgressKind::PathUpdate, route, d);
-    };
-    send(0.0f);
+        ctx.check(tl_or_opt_trace(ctx.get(), c.xy.data(), n, c.packed, c.ip, c.out.data(), &c.cost, &c.st, log.data(), cap, got));
+    });
+    auto send = detail::route_sender(problem, progress_tx);
+    std::vector<uint32_t> pos = c.start_tour();
+    send(pos.data(), 0.0f);
     for (uint32_t m = 0; m < len; ++m) {
         apply_relocation(pos, log[4 * m], log[4 * m + 2], log[4 * m + 1], log[4 * m + 3] != 0u);
-        send(tour_length_f32(problem, xy, pos));
+        send(pos.data(), tour_length_f32(problem, c.xy, pos));
     }
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    return s;
+    return detail::finish_done(problem, c, progress_tx);
 }
 
 // A population of tours, each refined by its own descent, all concurrently (tl_or_opt_population);
@@ -447,23 +541,10 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOp
 inline std::vector<Solution> solve_population(Context &ctx, const TspProblem &problem, const std::vector<std::vector<size_t>> &init_tours,
                                               std::vector<uint32_t> *moves = nullptr)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size(), count = (uint32_t)init_tours.size();
-    std::vector<uint32_t> init((size_t)count * n), out((size_t)count * n), mv(count);
-    for (uint32_t k = 0; k < count; ++k) {
-        const auto pos = problem.positions_of(init_tours[k]);
-        std::copy(pos.begin(), pos.end(), init.begin() + (size_t)k * n);
-    }
-    std::vector<float> costs(count);
-    tl_stats st{};
-    ctx.check(tl_or_opt_population(ctx.get(), xy.data(), n, problem.explicit_packed(), init.data(), count, out.data(), costs.data(), mv.data(), &st));
-    std::vector<Solution> res;
-    for (uint32_t k = 0; k < count; ++k) {
-        std::vector<uint32_t> one(out.begin() + (size_t)k * n, out.begin() + (size_t)(k + 1) * n);
-        res.push_back(detail::finish(problem, one, costs[k], st, nullptr));
-    }
-    if (moves) *moves = mv;
-    return res;
+    return detail::solve_population(problem, init_tours, moves,
+                                    [&](const detail::Call &c, const uint32_t *init, uint32_t count, uint32_t *out, float *costs, uint32_t *mv, tl_stats *st) {
+                                        ctx.check(tl_or_opt_population(ctx.get(), c.xy.data(), c.n, c.packed, init, count, out, costs, mv, st));
+                                    });
 }
 }  // namespace or_opt
 
@@ -500,25 +581,11 @@ namespace greedy_edge {  // greedy_edge.rs:21-65 over graph.rs:54-196
 inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions & /*_opts*/, const ProgressFn *progress_tx,
                       const std::vector<size_t> * /*_init_tour*/)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
-    std::vector<uint32_t> out(n);
-    float cost = 0.f;
-    tl_stats st{};
+    detail::Call c(problem, nullptr);
     // GEO / EXPLICIT: the edges are the packed matrix's (distance_by_pos, graph.rs:62-68)
-    ctx.check(tl_greedy_edge(ctx.get(), xy.data(), problem.explicit_packed(), n, out.data(), &cost, &st));
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    if (progress_tx && *progress_tx) {
-        // greedy_edge.rs:33-62: n <= 2 sends Done alone; otherwise the identity (cities in file order) with 0.0 before the
-        // selection, then the path with its length, then Done
-        if (n > 2) {
-            std::vector<size_t> identity(n);
-            for (uint32_t k = 0; k < n; ++k) identity[k] = problem.cities[k].id;
-            (*progress_tx)(ProgressKind::PathUpdate, identity, 0.0f);
-            (*progress_tx)(ProgressKind::PathUpdate, s.route_, cost);
-        }
-        (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    }
+    ctx.check(tl_greedy_edge(ctx.get(), c.xy.data(), c.packed, c.n, c.out.data(), &c.cost, &c.st));
+    Solution s = detail::finish(problem, c.out, c.cost, c.st, nullptr);
+    detail::construction_messages(problem, s, progress_tx, 3);  // greedy_edge.rs:33-62: n <= 2 sends Done alone
     return s;
 }
 }  // namespace greedy_edge
@@ -528,25 +595,11 @@ namespace savings {  // savings.rs:34-82 over graph.rs:98-196
 inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions & /*_opts*/, const ProgressFn *progress_tx,
                       const std::vector<size_t> * /*_init_tour*/, uint32_t *hub = nullptr)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
-    std::vector<uint32_t> out(n);
-    float cost = 0.f;
-    tl_stats st{};
+    detail::Call c(problem, nullptr);
     // GEO / EXPLICIT: the edges are the packed matrix's (distance_by_pos, savings.rs:144-152); the hub is the coordinates' all the same
-    ctx.check(tl_savings(ctx.get(), xy.data(), problem.explicit_packed(), n, TL_SAVINGS_HUB_AUTO, out.data(), &cost, hub, &st));
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    if (progress_tx && *progress_tx) {
-        // savings.rs:46-79: n <= 2 sends Done alone; otherwise the identity (cities in file order) with 0.0 before the
-        // selection, then the path with its length, then Done
-        if (n > 2) {
-            std::vector<size_t> identity(n);
-            for (uint32_t k = 0; k < n; ++k) identity[k] = problem.cities[k].id;
-            (*progress_tx)(ProgressKind::PathUpdate, identity, 0.0f);
-            (*progress_tx)(ProgressKind::PathUpdate, s.route_, cost);
-        }
-        (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    }
+    ctx.check(tl_savings(ctx.get(), c.xy.data(), c.packed, c.n, TL_SAVINGS_HUB_AUTO, c.out.data(), &c.cost, hub, &c.st));
+    Solution s = detail::finish(problem, c.out, c.cost, c.st, nullptr);
+    detail::construction_messages(problem, s, progress_tx, 3);  // savings.rs:46-79: n <= 2 sends Done alone
     return s;
 }
 }  // namespace savings
@@ -555,25 +608,11 @@ namespace christofides {  // christofides.rs:12-68
 inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions & /*_opts*/, const ProgressFn *progress_tx,
                       const std::vector<size_t> * /*_init_tour*/)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
-    std::vector<uint32_t> out(n);
-    float cost = 0.f;
-    tl_stats st{};
+    detail::Call c(problem, nullptr);
     // GEO / EXPLICIT: every distance is the packed matrix's (distance_by_pos, christofides.rs:102-104, :147-149)
-    ctx.check(tl_christofides(ctx.get(), xy.data(), problem.explicit_packed(), n, out.data(), &cost, &st));
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    if (progress_tx && *progress_tx) {
-        // christofides.rs:24-65: n < 4 sends Done alone; otherwise the identity (cities in file order) with 0.0 once the tree is
-        // built, then the route with its length, then Done
-        if (n >= 4) {
-            std::vector<size_t> identity(n);
-            for (uint32_t k = 0; k < n; ++k) identity[k] = problem.cities[k].id;
-            (*progress_tx)(ProgressKind::PathUpdate, identity, 0.0f);
-            (*progress_tx)(ProgressKind::PathUpdate, s.route_, cost);
-        }
-        (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    }
+    ctx.check(tl_christofides(ctx.get(), c.xy.data(), c.packed, c.n, c.out.data(), &c.cost, &c.st));
+    Solution s = detail::finish(problem, c.out, c.cost, c.st, nullptr);
+    detail::construction_messages(problem, s, progress_tx, 4);  // christofides.rs:24-65: n < 4 sends Done alone; the identity goes out once the tree is built
     return s;
 }
 }  // namespace christofides
@@ -912,53 +951,29 @@ struct SAOptions {  // mod.rs:689-706
 inline Solution solve(Context &ctx, const TspProblem &problem, const SAOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
                       uint64_t seed = 1, uint32_t chains = 1)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
-    std::vector<uint32_t> init, out(n);
-    if (init_tour) init = problem.positions_of(*init_tour);
-    const uint32_t *ip = init_tour ? init.data() : nullptr;
+    detail::Call c(problem, init_tour);
+    const uint32_t n = c.n;
     const tl_sa_opts o{(uint32_t)opts.heuristic.epochs, opts.cooling_rate, opts.min_temperature, opts.max_temperature};
-    float cost = 0.f;
-    tl_stats st{};
-    uint32_t chain = 0;
-    if (chains > 1) {
-        std::vector<uint32_t> outs((size_t)chains * n), moves(chains);
-        std::vector<float> costs(chains);
-        ctx.check(tl_sim_anneal_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, chains, &o, seed, outs.data(), costs.data(),
-                                           moves.data(), &chain, &st));
-        std::copy(outs.begin() + (size_t)chain * n, outs.begin() + (size_t)(chain + 1) * n, out.begin());
-        cost = costs[chain];
-        st.moves = moves[chain];
-        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
-    } else if (!(progress_tx && *progress_tx)) {
-        ctx.check(tl_sim_anneal(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, out.data(), &cost, &st));
-        return detail::finish(problem, out, cost, st, nullptr);
-    }
-    uint32_t cap = 1u << 14, len = 0;
-    std::vector<uint32_t> log;
-    for (;;) {
-        log.assign((size_t)cap * 4, 0u);
-        ctx.check(tl_sim_anneal_trace_chain(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, chain, out.data(), &cost, &st, log.data(), cap, &len));
-        if (len <= cap) break;
-        cap = len;  // deterministic: once more with room for every accepted epoch
-    }
-    std::vector<uint32_t> pos(n);
-    for (uint32_t q = 0; q < n; ++q) pos[q] = init_tour ? init[q] : q;
-    std::vector<size_t> route(n);
-    auto send = [&](float d) {
-        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[pos[q]].id;
-        (*progress_tx)(ProgressKind::PathUpdate, route, d);
-    };
-    send(or_opt::tour_length_f32(problem, xy, pos));
-    for (uint32_t m = 0; m < len; ++m) {
-        std::reverse(pos.begin() + log[4 * m + 1], pos.begin() + log[4 * m + 2] + 1);  // swap_cities (route.rs:102-113)
-        float d;
-        std::memcpy(&d, &log[4 * m + 3], 4);
-        send(d);
-    }
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    return s;
+    return detail::solve_chains(
+        problem, c, progress_tx, chains, true,
+        [&](uint32_t count, uint32_t *outs, float *costs, uint32_t *moves, uint32_t *best) {
+            ctx.check(tl_sim_anneal_population(ctx.get(), c.xy.data(), n, c.packed, c.ip, c.ip ? 1u : 0u, 0u, count, &o, seed, outs, costs, moves, best, &c.st));
+        },
+        [&] { ctx.check(tl_sim_anneal(ctx.get(), c.xy.data(), n, c.packed, c.ip, &o, seed, c.out.data(), &c.cost, &c.st)); },
+        [&](uint32_t chain) {
+            std::vector<uint32_t> log;
+            const uint32_t len = detail::grow_trace(1u << 14, [&](uint32_t cap, uint32_t *got) {  // room for every accepted epoch
+                log.assign((size_t)cap * 4, 0u);
+                ctx.check(tl_sim_anneal_trace_chain(ctx.get(), c.xy.data(), n, c.packed, c.ip, &o, seed, chain, c.out.data(), &c.cost, &c.st, log.data(), cap, got));
+            });
+            auto send = detail::route_sender(problem, progress_tx);
+            std::vector<uint32_t> pos = c.start_tour();
+            send(pos.data(), or_opt::tour_length_f32(problem, c.xy, pos));
+            for (uint32_t m = 0; m < len; ++m) {
+                std::reverse(pos.begin() + log[4 * m + 1], pos.begin() + log[4 * m + 2] + 1);  // swap_cities (route.rs:102-113)
+                send(pos.data(), detail::bits_to_f32(log[4 * m + 3]));
+            }
+        });
 }
 }  // namespace simulated_annealing
 
@@ -970,53 +985,34 @@ namespace tabu_search {  // tabu_search.rs:9-110
 inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
                       uint64_t seed = 1, uint32_t chains = 1)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
-    const uint32_t epochs = (uint32_t)opts.epochs;
-    std::vector<uint32_t> init, out(n);
-    if (init_tour) init = problem.positions_of(*init_tour);
-    const uint32_t *ip = init_tour ? init.data() : nullptr;
-    float cost = 0.f;
-    tl_stats st{};
-    uint32_t chain = 0;
-    if (chains > 1) {
-        std::vector<uint32_t> outs((size_t)chains * n), moves(chains);
-        std::vector<float> costs(chains);
-        ctx.check(tl_tabu_search_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, chains, epochs, seed, outs.data(),
-                                            costs.data(), moves.data(), &chain, &st));
-        std::copy(outs.begin() + (size_t)chain * n, outs.begin() + (size_t)(chain + 1) * n, out.begin());
-        cost = costs[chain];
-        st.moves = moves[chain];
-        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
-    } else if (!(progress_tx && *progress_tx)) {
-        ctx.check(tl_tabu_search(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, epochs, seed, out.data(), &cost, &st));
-        return detail::finish(problem, out, cost, st, nullptr);
-    }
-    const uint32_t cap = epochs + 1u;
-    uint32_t len = 0;
-    std::vector<uint32_t> log((size_t)cap * 4, 0u);
-    ctx.check(tl_tabu_search_trace_chain(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, epochs, seed, chain, out.data(), &cost, &st, log.data(), cap, &len));
-    std::vector<uint32_t> pos(n);
-    for (uint32_t q = 0; q < n; ++q) pos[q] = init_tour ? init[q] : q;
-    std::vector<size_t> route(n);
-    auto send = [&](float d) {
-        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[pos[q]].id;
-        (*progress_tx)(ProgressKind::PathUpdate, route, d);
-    };
-    float best = or_opt::tour_length_f32(problem, xy, pos);
-    send(0.0f);
-    for (uint32_t m = 0; m < len && m < cap; ++m) {
-        std::reverse(pos.begin() + log[4 * m + 1], pos.begin() + log[4 * m + 2] + 1);  // swap_cities (route.rs:102-113)
-        float d;
-        std::memcpy(&d, &log[4 * m + 3], 4);
-        if (d < best) {
-            best = d;
-            send(d);
-        }
-    }
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    return s;
+    detail::Call c(problem, init_tour);
+    const uint32_t n = c.n, epochs = (uint32_t)opts.epochs;
+    return detail::solve_chains(
+        problem, c, progress_tx, chains, true,
+        [&](uint32_t count, uint32_t *outs, float *costs, uint32_t *moves, uint32_t *best) {
+            ctx.check(tl_tabu_search_population(ctx.get(), c.xy.data(), n, c.packed, c.ip, c.ip ? 1u : 0u, 0u, count, epochs, seed, outs, costs, moves, best, &c.st));
+        },
+        [&] { ctx.check(tl_tabu_search(ctx.get(), c.xy.data(), n, c.packed, c.ip, epochs, seed, c.out.data(), &c.cost, &c.st)); },
+        [&](uint32_t chain) {
+            // One record per epoch and epochs + 1 epochs run, so the log's length is known and nothing grows: the entry reports
+            // len = epochs + 1 = cap on every call that succeeds, and refuses the epochs (0, 2^32 - 1) at which cap would not be that.
+            const uint32_t cap = epochs + 1u;
+            uint32_t len = 0;
+            std::vector<uint32_t> log((size_t)cap * 4, 0u);
+            ctx.check(tl_tabu_search_trace_chain(ctx.get(), c.xy.data(), n, c.packed, c.ip, epochs, seed, chain, c.out.data(), &c.cost, &c.st, log.data(), cap, &len));
+            auto send = detail::route_sender(problem, progress_tx);
+            std::vector<uint32_t> pos = c.start_tour();
+            float best = or_opt::tour_length_f32(problem, c.xy, pos);
+            send(pos.data(), 0.0f);
+            for (uint32_t m = 0; m < len; ++m) {
+                std::reverse(pos.begin() + log[4 * m + 1], pos.begin() + log[4 * m + 2] + 1);  // swap_cities (route.rs:102-113)
+                const float d = detail::bits_to_f32(log[4 * m + 3]);
+                if (d < best) {
+                    best = d;
+                    send(pos.data(), d);
+                }
+            }
+        });
 }
 }  // namespace tabu_search
 
@@ -1039,43 +1035,24 @@ struct GAOptions {  // mod.rs:815-846
 inline Solution solve(Context &ctx, const TspProblem &problem, const GAOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
                       uint64_t seed = 1, uint32_t runs = 1)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
-    const uint32_t epochs = (uint32_t)opts.heuristic.epochs, e = (uint32_t)std::min<size_t>(opts.n_elite, 0xFFFFFFFFu);
+    detail::Call c(problem, init_tour);
+    const uint32_t n = c.n, epochs = (uint32_t)opts.heuristic.epochs, e = (uint32_t)std::min<size_t>(opts.n_elite, 0xFFFFFFFFu);
     const float p = opts.mutation_probability;
-    std::vector<uint32_t> init, out(n);
-    if (init_tour) init = problem.positions_of(*init_tour);
-    const uint32_t *ip = init_tour ? init.data() : nullptr;
-    float cost = 0.f;
-    tl_stats st{};
-    uint32_t run = 0;
-    if (runs > 1) {
-        std::vector<uint32_t> outs((size_t)runs * n);
-        std::vector<float> costs(runs);
-        ctx.check(tl_genetic_algorithm_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, 0u, runs, epochs, p, e, seed, outs.data(), costs.data(),
-                                                  &run, &st));
-        std::copy(outs.begin() + (size_t)run * n, outs.begin() + (size_t)(run + 1) * n, out.begin());
-        cost = costs[run];
-        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
-    } else if (!(progress_tx && *progress_tx)) {
-        ctx.check(tl_genetic_algorithm(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, epochs, p, e, seed, out.data(), &cost, &st));
-        return detail::finish(problem, out, cost, st, nullptr);
-    }
-    uint32_t len = 0;
-    std::vector<uint32_t> log((size_t)std::max(epochs, 1u) * 4, 0u), routes((size_t)std::max(epochs, 1u) * n, 0u);
-    ctx.check(tl_genetic_algorithm_trace_run(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, epochs, p, e, seed, run, out.data(), &cost, &st, log.data(),
-                                             epochs, &len, routes.data(), epochs));
-    std::vector<size_t> route(n);
-    for (uint32_t g = 0; g < len && g < epochs; ++g) {
-        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[routes[(size_t)g * n + q]].id;
-        float d;
-        std::memcpy(&d, &log[4 * (size_t)g + 2], 4);
-        (*progress_tx)(ProgressKind::PathUpdate, route, d);
-    }
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    (*progress_tx)(ProgressKind::PathUpdate, s.route_, cost);
-    (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    return s;
+    return detail::solve_chains(
+        problem, c, progress_tx, runs, false,
+        [&](uint32_t count, uint32_t *outs, float *costs, uint32_t *, uint32_t *best) {
+            ctx.check(tl_genetic_algorithm_population(ctx.get(), c.xy.data(), n, c.packed, c.ip, 0u, count, epochs, p, e, seed, outs, costs, best, &c.st));
+        },
+        [&] { ctx.check(tl_genetic_algorithm(ctx.get(), c.xy.data(), n, c.packed, c.ip, epochs, p, e, seed, c.out.data(), &c.cost, &c.st)); },
+        [&](uint32_t run) {
+            uint32_t len = 0;
+            std::vector<uint32_t> log((size_t)std::max(epochs, 1u) * 4, 0u), routes((size_t)std::max(epochs, 1u) * n, 0u);
+            ctx.check(tl_genetic_algorithm_trace_run(ctx.get(), c.xy.data(), n, c.packed, c.ip, epochs, p, e, seed, run, c.out.data(), &c.cost, &c.st, log.data(), epochs,
+                                                     &len, routes.data(), epochs));
+            auto send = detail::route_sender(problem, progress_tx);
+            for (uint32_t g = 0; g < len && g < epochs; ++g) send(routes.data() + (size_t)g * n, detail::bits_to_f32(log[4 * (size_t)g + 2]));
+            send(c.out.data(), c.cost);  // the one more: the result itself
+        });
 }
 }  // namespace genetic_algorithm
 
@@ -1102,56 +1079,38 @@ struct AcoOptions {  // mod.rs:1082-1153
 inline Solution solve(Context &ctx, const TspProblem &problem, const AcoOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
                       uint64_t seed = 1, uint32_t runs = 1)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
-    const uint32_t epochs = (uint32_t)opts.heuristic.epochs, ants = (uint32_t)std::min<size_t>(opts.num_ants, 0xFFFFFFFFu);
+    detail::Call c(problem, init_tour);
+    const uint32_t n = c.n, epochs = (uint32_t)opts.heuristic.epochs, ants = (uint32_t)std::min<size_t>(opts.num_ants, 0xFFFFFFFFu);
     const float a = opts.alpha, b = opts.beta, r = opts.evaporation_rate;
-    std::vector<uint32_t> init, out(n);
-    if (init_tour) init = problem.positions_of(*init_tour);
-    const uint32_t *ip = init_tour ? init.data() : nullptr;
-    float cost = 0.f;
-    tl_stats st{};
-    uint32_t run = 0;
-    if (runs > 1) {
-        std::vector<uint32_t> outs((size_t)runs * n);
-        std::vector<float> costs(runs);
-        ctx.check(tl_ant_colony_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, runs, epochs, a, b, r, ants, seed, outs.data(),
-                                           costs.data(), &run, &st));
-        std::copy(outs.begin() + (size_t)run * n, outs.begin() + (size_t)(run + 1) * n, out.begin());
-        cost = costs[run];
-        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
-    } else if (!(progress_tx && *progress_tx)) {
-        ctx.check(tl_ant_colony(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, epochs, a, b, r, ants, seed, out.data(), &cost, &st));
-        return detail::finish(problem, out, cost, st, nullptr);
-    }
-    uint32_t len = 0, rows = 0, cap = 64;
-    std::vector<uint32_t> log((size_t)3 * std::max(ants, 1u), 0u), routes;
-    for (;;) {  // the route log holds every improving ant: ask again with the count where 64 rows were too few
-        routes.assign((size_t)cap * (n + 3), 0u);
-        ctx.check(tl_ant_colony_trace_run(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, epochs, a, b, r, ants, seed, run, out.data(), &cost, &st,
-                                          log.data(), 1u, &len, routes.data(), cap, &rows));
-        if (rows <= cap) break;
-        cap = rows;
-    }
-    std::vector<size_t> route(n);
-    const auto path_update = [&](uint32_t k) {
-        const uint32_t *rec = routes.data() + (size_t)k * (n + 3);
-        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[rec[3 + q]].id;
-        float d;
-        std::memcpy(&d, &rec[2], 4);
-        (*progress_tx)(ProgressKind::PathUpdate, route, d);
-    };
-    if (rows > 0) {  // (n <= 2: no row, the reference sends Done alone)
-        path_update(0);
-        uint32_t k = 1;
-        for (uint32_t g = 0; g < epochs; ++g) {
-            for (; k < rows && routes[(size_t)k * (n + 3)] == g; ++k) path_update(k);
-            (*progress_tx)(ProgressKind::EpochUpdate, std::vector<size_t>{g}, 0.0f);
-        }
-    }
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    return s;
+    return detail::solve_chains(
+        problem, c, progress_tx, runs, false,
+        [&](uint32_t count, uint32_t *outs, float *costs, uint32_t *, uint32_t *best) {
+            ctx.check(tl_ant_colony_population(ctx.get(), c.xy.data(), n, c.packed, c.ip, c.ip ? 1u : 0u, 0u, count, epochs, a, b, r, ants, seed, outs, costs, best, &c.st));
+        },
+        [&] { ctx.check(tl_ant_colony(ctx.get(), c.xy.data(), n, c.packed, c.ip, epochs, a, b, r, ants, seed, c.out.data(), &c.cost, &c.st)); },
+        [&](uint32_t run) {
+            // the trace is the colony's own: one epoch-log row, and a route log of rows (epoch, ant, cost bits, the n positions) that
+            // holds every improving ant
+            uint32_t len = 0;
+            std::vector<uint32_t> log((size_t)3 * std::max(ants, 1u), 0u), routes;
+            const uint32_t rows = detail::grow_trace(64u, [&](uint32_t cap, uint32_t *got) {
+                routes.assign((size_t)cap * (n + 3), 0u);
+                ctx.check(tl_ant_colony_trace_run(ctx.get(), c.xy.data(), n, c.packed, c.ip, epochs, a, b, r, ants, seed, run, c.out.data(), &c.cost, &c.st, log.data(), 1u,
+                                                  &len, routes.data(), cap, got));
+            });
+            auto send = detail::route_sender(problem, progress_tx);
+            const auto path_update = [&](uint32_t k) {
+                const uint32_t *rec = routes.data() + (size_t)k * (n + 3);
+                send(rec + 3, detail::bits_to_f32(rec[2]));
+            };
+            if (rows == 0) return;  // (n <= 2: no row, the reference sends Done alone)
+            path_update(0);
+            uint32_t k = 1;
+            for (uint32_t g = 0; g < epochs; ++g) {
+                for (; k < rows && routes[(size_t)k * (n + 3)] == g; ++k) path_update(k);
+                (*progress_tx)(ProgressKind::EpochUpdate, std::vector<size_t>{g}, 0.0f);
+            }
+        });
 }
 }  // namespace ant_colony
 
@@ -1164,55 +1123,8 @@ namespace particle_swarm {  // particle_swarm.rs:22-129
 inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
                       uint64_t seed = 1, uint32_t runs = 1)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
     const tl_pso_opts o{(uint32_t)opts.epochs, (uint32_t)std::min<size_t>(opts.n_nearest, 0xFFFFFFFFu)};
-    std::vector<uint32_t> init, out(n);
-    if (init_tour) init = problem.positions_of(*init_tour);
-    const uint32_t *ip = init_tour ? init.data() : nullptr;
-    float cost = 0.f;
-    tl_stats st{};
-    uint32_t run = 0;
-    if (runs > 1) {
-        std::vector<uint32_t> outs((size_t)runs * n);
-        std::vector<float> costs(runs);
-        ctx.check(tl_particle_swarm_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, runs, &o, seed, outs.data(), costs.data(),
-                                               nullptr, &run, &st));
-        std::copy(outs.begin() + (size_t)run * n, outs.begin() + (size_t)(run + 1) * n, out.begin());
-        cost = costs[run];
-        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
-    } else if (!(progress_tx && *progress_tx)) {
-        ctx.check(tl_particle_swarm(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, out.data(), &cost, &st));
-        return detail::finish(problem, out, cost, st, nullptr);
-    }
-    uint32_t rows = 0, cap = 64;
-    std::vector<uint32_t> log, routes;
-    for (;;) {  // the log holds every improvement: ask again with the count where 64 records were too few
-        log.assign((size_t)cap * 4, 0u);
-        routes.assign((size_t)cap * std::max(n, 1u), 0u);
-        ctx.check(tl_particle_swarm_trace(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, run, out.data(), &cost, &st, log.data(), cap, &rows,
-                                          routes.data(), cap, nullptr, 0u));
-        if (rows <= cap) break;
-        cap = rows;
-    }
-    std::vector<size_t> route(n);
-    const auto path_update = [&](uint32_t k) {
-        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[routes[(size_t)k * n + q]].id;
-        float d;
-        std::memcpy(&d, &log[(size_t)k * 4 + 2], 4);
-        (*progress_tx)(ProgressKind::PathUpdate, route, d);
-    };
-    if (rows > 0) {
-        path_update(0);
-        uint32_t k = 1;
-        for (uint32_t e = 0; e < o.epochs; ++e) {
-            for (; k < rows && log[(size_t)k * 4] == e; ++k) path_update(k);
-            (*progress_tx)(ProgressKind::EpochUpdate, std::vector<size_t>{e}, 0.0f);
-        }
-    }
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    return s;
+    return detail::solve_swarm(ctx, problem, progress_tx, init_tour, seed, runs, o, tl_particle_swarm, tl_particle_swarm_trace, tl_particle_swarm_population);
 }
 }  // namespace particle_swarm
 
@@ -1235,55 +1147,8 @@ struct CSOptions {  // mod.rs:913-940
 inline Solution solve(Context &ctx, const TspProblem &problem, const CSOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
                       uint64_t seed = 1, uint32_t runs = 1)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
     const tl_cs_opts o{(uint32_t)opts.heuristic.epochs, (uint32_t)std::min<size_t>(opts.heuristic.n_nearest, 0xFFFFFFFFu), opts.mutation_probability};
-    std::vector<uint32_t> init, out(n);
-    if (init_tour) init = problem.positions_of(*init_tour);
-    const uint32_t *ip = init_tour ? init.data() : nullptr;
-    float cost = 0.f;
-    tl_stats st{};
-    uint32_t run = 0;
-    if (runs > 1) {
-        std::vector<uint32_t> outs((size_t)runs * n);
-        std::vector<float> costs(runs);
-        ctx.check(tl_cuckoo_search_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, runs, &o, seed, outs.data(), costs.data(),
-                                               nullptr, &run, &st));
-        std::copy(outs.begin() + (size_t)run * n, outs.begin() + (size_t)(run + 1) * n, out.begin());
-        cost = costs[run];
-        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
-    } else if (!(progress_tx && *progress_tx)) {
-        ctx.check(tl_cuckoo_search(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, out.data(), &cost, &st));
-        return detail::finish(problem, out, cost, st, nullptr);
-    }
-    uint32_t rows = 0, cap = 64;
-    std::vector<uint32_t> log, routes;
-    for (;;) {  // the log holds every improvement: ask again with the count where 64 records were too few
-        log.assign((size_t)cap * 4, 0u);
-        routes.assign((size_t)cap * std::max(n, 1u), 0u);
-        ctx.check(tl_cuckoo_search_trace(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, run, out.data(), &cost, &st, log.data(), cap, &rows,
-                                          routes.data(), cap, nullptr, 0u));
-        if (rows <= cap) break;
-        cap = rows;
-    }
-    std::vector<size_t> route(n);
-    const auto path_update = [&](uint32_t k) {
-        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[routes[(size_t)k * n + q]].id;
-        float d;
-        std::memcpy(&d, &log[(size_t)k * 4 + 2], 4);
-        (*progress_tx)(ProgressKind::PathUpdate, route, d);
-    };
-    if (rows > 0) {
-        path_update(0);
-        uint32_t k = 1;
-        for (uint32_t e = 0; e < o.epochs; ++e) {
-            for (; k < rows && log[(size_t)k * 4] == e; ++k) path_update(k);
-            (*progress_tx)(ProgressKind::EpochUpdate, std::vector<size_t>{e}, 0.0f);
-        }
-    }
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    return s;
+    return detail::solve_swarm(ctx, problem, progress_tx, init_tour, seed, runs, o, tl_cuckoo_search, tl_cuckoo_search_trace, tl_cuckoo_search_population);
 }
 }  // namespace cuckoo_search
 
@@ -1306,55 +1171,8 @@ struct FPAOptions {  // mod.rs:998-1026
 inline Solution solve(Context &ctx, const TspProblem &problem, const FPAOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
                       uint64_t seed = 1, uint32_t runs = 1)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
     const tl_fpa_opts o{(uint32_t)opts.heuristic.epochs, (uint32_t)std::min<size_t>(opts.heuristic.n_nearest, 0xFFFFFFFFu), opts.mutation_probability};
-    std::vector<uint32_t> init, out(n);
-    if (init_tour) init = problem.positions_of(*init_tour);
-    const uint32_t *ip = init_tour ? init.data() : nullptr;
-    float cost = 0.f;
-    tl_stats st{};
-    uint32_t run = 0;
-    if (runs > 1) {
-        std::vector<uint32_t> outs((size_t)runs * n);
-        std::vector<float> costs(runs);
-        ctx.check(tl_flower_pollination_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, runs, &o, seed, outs.data(), costs.data(),
-                                               nullptr, &run, &st));
-        std::copy(outs.begin() + (size_t)run * n, outs.begin() + (size_t)(run + 1) * n, out.begin());
-        cost = costs[run];
-        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
-    } else if (!(progress_tx && *progress_tx)) {
-        ctx.check(tl_flower_pollination(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, out.data(), &cost, &st));
-        return detail::finish(problem, out, cost, st, nullptr);
-    }
-    uint32_t rows = 0, cap = 64;
-    std::vector<uint32_t> log, routes;
-    for (;;) {  // the log holds every improvement: ask again with the count where 64 records were too few
-        log.assign((size_t)cap * 4, 0u);
-        routes.assign((size_t)cap * std::max(n, 1u), 0u);
-        ctx.check(tl_flower_pollination_trace(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, run, out.data(), &cost, &st, log.data(), cap, &rows,
-                                          routes.data(), cap, nullptr, 0u));
-        if (rows <= cap) break;
-        cap = rows;
-    }
-    std::vector<size_t> route(n);
-    const auto path_update = [&](uint32_t k) {
-        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[routes[(size_t)k * n + q]].id;
-        float d;
-        std::memcpy(&d, &log[(size_t)k * 4 + 2], 4);
-        (*progress_tx)(ProgressKind::PathUpdate, route, d);
-    };
-    if (rows > 0) {
-        path_update(0);
-        uint32_t k = 1;
-        for (uint32_t e = 0; e < o.epochs; ++e) {
-            for (; k < rows && log[(size_t)k * 4] == e; ++k) path_update(k);
-            (*progress_tx)(ProgressKind::EpochUpdate, std::vector<size_t>{e}, 0.0f);
-        }
-    }
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    return s;
+    return detail::solve_swarm(ctx, problem, progress_tx, init_tour, seed, runs, o, tl_flower_pollination, tl_flower_pollination_trace, tl_flower_pollination_population);
 }
 }  // namespace flower_pollination
 
@@ -1367,55 +1185,9 @@ namespace gravitational_search {  // gravitational_search.rs:23-145
 inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
                       uint64_t seed = 1, uint32_t runs = 1)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
     const tl_gsa_opts o{(uint32_t)opts.epochs, (uint32_t)std::min<size_t>(opts.n_nearest, 0xFFFFFFFFu), 0u};
-    std::vector<uint32_t> init, out(n);
-    if (init_tour) init = problem.positions_of(*init_tour);
-    const uint32_t *ip = init_tour ? init.data() : nullptr;
-    float cost = 0.f;
-    tl_stats st{};
-    uint32_t run = 0;
-    if (runs > 1) {
-        std::vector<uint32_t> outs((size_t)runs * n);
-        std::vector<float> costs(runs);
-        ctx.check(tl_gravitational_search_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, runs, &o, seed, outs.data(), costs.data(),
-                                               nullptr, &run, &st));
-        std::copy(outs.begin() + (size_t)run * n, outs.begin() + (size_t)(run + 1) * n, out.begin());
-        cost = costs[run];
-        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
-    } else if (!(progress_tx && *progress_tx)) {
-        ctx.check(tl_gravitational_search(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, out.data(), &cost, &st));
-        return detail::finish(problem, out, cost, st, nullptr);
-    }
-    uint32_t rows = 0, cap = 64;
-    std::vector<uint32_t> log, routes;
-    for (;;) {  // the log holds every improvement: ask again with the count where 64 records were too few
-        log.assign((size_t)cap * 4, 0u);
-        routes.assign((size_t)cap * std::max(n, 1u), 0u);
-        ctx.check(tl_gravitational_search_trace(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, run, out.data(), &cost, &st, log.data(), cap, &rows,
-                                          routes.data(), cap, nullptr, 0u));
-        if (rows <= cap) break;
-        cap = rows;
-    }
-    std::vector<size_t> route(n);
-    const auto path_update = [&](uint32_t k) {
-        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[routes[(size_t)k * n + q]].id;
-        float d;
-        std::memcpy(&d, &log[(size_t)k * 4 + 2], 4);
-        (*progress_tx)(ProgressKind::PathUpdate, route, d);
-    };
-    if (rows > 0) {
-        path_update(0);
-        uint32_t k = 1;
-        for (uint32_t e = 0; e < o.epochs; ++e) {
-            for (; k < rows && log[(size_t)k * 4] == e; ++k) path_update(k);
-            (*progress_tx)(ProgressKind::EpochUpdate, std::vector<size_t>{e}, 0.0f);
-        }
-    }
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    return s;
+    return detail::solve_swarm(ctx, problem, progress_tx, init_tour, seed, runs, o, tl_gravitational_search, tl_gravitational_search_trace,
+                               tl_gravitational_search_population);
 }
 }  // namespace gravitational_search
 
@@ -1431,45 +1203,32 @@ struct SOMOptions {  // mod.rs:1465-1482
 // 0 .. runs-1 of the seed at once, the best one returned (lowest cost, then lowest run).  With a progress callback the reference's
 // messages — EpochUpdate(t) then PathUpdate(snapshot) at every t % max(epochs / 10, 1) == 0, a final PathUpdate only where
 // epochs % checkpoint != 0, then Done (som.rs:117-145; nothing for n < 2) — are replayed from that run's checkpoint records.
-inline Solution solve(Context &ctx, const TspProblem &problem, const SOMOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
+inline Solution solve(Context &ctx, const TspProblem &problem, const SOMOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> * /*init_tour*/,
                       uint64_t seed = 1, uint32_t runs = 1)
 {
-    (void)init_tour;
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
+    detail::Call c(problem, nullptr);
+    const uint32_t n = c.n;
     const tl_som_opts o{(uint32_t)std::min<size_t>(opts.epochs, 0xFFFFFFFFu), (uint32_t)std::min<size_t>(opts.neuron_multiplier, 0xFFFFFFFFu), opts.learning_rate,
                         opts.radius_fraction, 0u, 0u, 0ull};
-    std::vector<uint32_t> out(n);
-    float cost = 0.f;
-    tl_stats st{};
-    uint32_t run = 0;
-    if (runs > 1) {
-        std::vector<uint32_t> outs((size_t)runs * n);
-        std::vector<float> costs(runs);
-        ctx.check(tl_kohonen_som_population(ctx.get(), xy.data(), n, problem.explicit_packed(), 0u, runs, &o, seed, outs.data(), costs.data(), &run, &st));
-        std::copy(outs.begin() + (size_t)run * n, outs.begin() + (size_t)(run + 1) * n, out.begin());
-        cost = costs[run];
-        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
-    } else if (!(progress_tx && *progress_tx)) {
-        ctx.check(tl_kohonen_som(ctx.get(), xy.data(), n, problem.explicit_packed(), &o, seed, out.data(), &cost, &st));
-        return detail::finish(problem, out, cost, st, nullptr);
-    }
-    const uint32_t cap = 20;
-    uint32_t rows = 0;
-    std::vector<uint32_t> ep(cap), tours((size_t)cap * std::max(n, 1u)), cb(cap);
-    ctx.check(tl_kohonen_som_trace(ctx.get(), xy.data(), n, problem.explicit_packed(), &o, seed, run, out.data(), &cost, &st, nullptr, 0u, nullptr, ep.data(),
-                                   tours.data(), cb.data(), cap, &rows));
-    std::vector<size_t> route(n);
-    for (uint32_t k = 0; k < rows && k < cap; ++k) {
-        if (ep[k] != 0xFFFFFFFFu) (*progress_tx)(ProgressKind::EpochUpdate, std::vector<size_t>{ep[k]}, 0.0f);
-        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[tours[(size_t)k * n + q]].id;
-        float d;
-        std::memcpy(&d, &cb[k], 4);
-        (*progress_tx)(ProgressKind::PathUpdate, route, d);
-    }
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    if (n >= 2) (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    return s;
+    return detail::solve_chains(
+        problem, c, progress_tx, runs, false,
+        [&](uint32_t count, uint32_t *outs, float *costs, uint32_t *, uint32_t *best) {
+            ctx.check(tl_kohonen_som_population(ctx.get(), c.xy.data(), n, c.packed, 0u, count, &o, seed, outs, costs, best, &c.st));
+        },
+        [&] { ctx.check(tl_kohonen_som(ctx.get(), c.xy.data(), n, c.packed, &o, seed, c.out.data(), &c.cost, &c.st)); },
+        [&](uint32_t run) {
+            const uint32_t cap = 20;
+            uint32_t rows = 0;
+            std::vector<uint32_t> ep(cap), tours((size_t)cap * std::max(n, 1u)), cb(cap);
+            ctx.check(tl_kohonen_som_trace(ctx.get(), c.xy.data(), n, c.packed, &o, seed, run, c.out.data(), &c.cost, &c.st, nullptr, 0u, nullptr, ep.data(), tours.data(),
+                                           cb.data(), cap, &rows));
+            auto send = detail::route_sender(problem, progress_tx);
+            for (uint32_t k = 0; k < rows && k < cap; ++k) {
+                if (ep[k] != 0xFFFFFFFFu) (*progress_tx)(ProgressKind::EpochUpdate, std::vector<size_t>{ep[k]}, 0.0f);
+                send(tours.data() + (size_t)k * n, detail::bits_to_f32(cb[k]));
+            }
+        },
+        n >= 2);  // (n < 2: the reference sends nothing, Done included)
 }
 }  // namespace kohonen_som
 
@@ -1485,61 +1244,37 @@ namespace hill_climb {  // stochastic_hill.rs:7-97
 inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOptions &opts, const ProgressFn *progress_tx, const std::vector<size_t> *init_tour,
                       uint64_t seed = 1, uint32_t chains = 1, uint32_t window = 0)
 {
-    const auto xy = problem.xy();
-    const uint32_t n = (uint32_t)problem.cities.size();
-    std::vector<uint32_t> init, out(n);
-    if (init_tour) init = problem.positions_of(*init_tour);
-    const uint32_t *ip = init_tour ? init.data() : nullptr;
+    detail::Call c(problem, init_tour);
+    const uint32_t n = c.n;
     const tl_hill_opts o{(uint32_t)opts.epochs, (uint32_t)opts.platoo_epochs, window, 0u};
-    float cost = 0.f;
-    tl_stats st{};
-    uint32_t chain = 0;
-    if (chains > 1) {
-        std::vector<uint32_t> outs((size_t)chains * n), moves(chains);
-        std::vector<float> costs(chains);
-        ctx.check(tl_hill_climb_population(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, ip ? 1u : 0u, 0u, chains, &o, seed, outs.data(), costs.data(),
-                                           moves.data(), &chain, &st));
-        std::copy(outs.begin() + (size_t)chain * n, outs.begin() + (size_t)(chain + 1) * n, out.begin());
-        cost = costs[chain];
-        st.moves = moves[chain];
-        if (!(progress_tx && *progress_tx)) return detail::finish(problem, out, cost, st, nullptr);
-    } else if (!(progress_tx && *progress_tx)) {
-        ctx.check(tl_hill_climb(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, out.data(), &cost, &st));
-        return detail::finish(problem, out, cost, st, nullptr);
-    }
-    uint32_t cap = 1u << 14, len = 0;
-    std::vector<uint32_t> log;
-    for (;;) {
-        log.assign((size_t)cap * 4, 0u);
-        ctx.check(tl_hill_climb_trace_chain(ctx.get(), xy.data(), n, problem.explicit_packed(), ip, &o, seed, chain, out.data(), &cost, &st, log.data(), cap, &len));
-        if (len <= cap) break;
-        cap = len;  // deterministic: once more with room for every event
-    }
-    std::vector<uint32_t> pos(n);
-    for (uint32_t q = 0; q < n; ++q) pos[q] = init_tour ? init[q] : q;
-    std::vector<size_t> route(n);
-    auto send = [&](float d) {
-        for (uint32_t q = 0; q < n; ++q) route[q] = problem.cities[pos[q]].id;
-        (*progress_tx)(ProgressKind::PathUpdate, route, d);
-    };
-    send(0.0f);
-    for (uint32_t m = 0; m < len; ++m) {
-        if (log[4 * m + 1] == 0xFFFFFFFFu) {  // a restart: the Fisher-Yates pass of csrc/hill_spec.h on the current contents
-            for (uint32_t j = n - 1u; j >= 1u; --j) {
-                const uint64_t u = tl_hill_draw(seed, chain, (1ull << 58) + (uint64_t)log[4 * m] * n + j, 26u);
-                std::swap(pos[j], pos[(uint32_t)(((u >> 32) * (j + 1u)) >> 32)]);
+    return detail::solve_chains(
+        problem, c, progress_tx, chains, true,
+        [&](uint32_t count, uint32_t *outs, float *costs, uint32_t *moves, uint32_t *best) {
+            ctx.check(tl_hill_climb_population(ctx.get(), c.xy.data(), n, c.packed, c.ip, c.ip ? 1u : 0u, 0u, count, &o, seed, outs, costs, moves, best, &c.st));
+        },
+        [&] { ctx.check(tl_hill_climb(ctx.get(), c.xy.data(), n, c.packed, c.ip, &o, seed, c.out.data(), &c.cost, &c.st)); },
+        [&](uint32_t chain) {
+            std::vector<uint32_t> log;
+            const uint32_t len = detail::grow_trace(1u << 14, [&](uint32_t cap, uint32_t *got) {  // room for every event
+                log.assign((size_t)cap * 4, 0u);
+                ctx.check(tl_hill_climb_trace_chain(ctx.get(), c.xy.data(), n, c.packed, c.ip, &o, seed, chain, c.out.data(), &c.cost, &c.st, log.data(), cap, got));
+            });
+            auto send = detail::route_sender(problem, progress_tx);
+            std::vector<uint32_t> pos = c.start_tour();
+            send(pos.data(), 0.0f);
+            for (uint32_t m = 0; m < len; ++m) {
+                if (log[4 * m + 1] == 0xFFFFFFFFu) {  // a restart: the Fisher-Yates pass of csrc/hill_spec.h on the current contents
+                    for (uint32_t j = n - 1u; j >= 1u; --j) {
+                        const uint64_t u = tl_hill_draw(seed, chain, (1ull << 58) + (uint64_t)log[4 * m] * n + j, 26u);
+                        std::swap(pos[j], pos[(uint32_t)(((u >> 32) * (j + 1u)) >> 32)]);
+                    }
+                    send(pos.data(), 0.0f);
+                } else {
+                    std::reverse(pos.begin() + log[4 * m + 1], pos.begin() + log[4 * m + 2] + 1);  // swap_cities (route.rs:102-113)
+                    send(pos.data(), detail::bits_to_f32(log[4 * m + 3]));
+                }
             }
-            send(0.0f);
-        } else {
-            std::reverse(pos.begin() + log[4 * m + 1], pos.begin() + log[4 * m + 2] + 1);  // swap_cities (route.rs:102-113)
-            float d;
-            std::memcpy(&d, &log[4 * m + 3], 4);
-            send(d);
-        }
-    }
-    Solution s = detail::finish(problem, out, cost, st, nullptr);
-    (*progress_tx)(ProgressKind::Done, s.route_, cost);
-    return s;
+        });
 }
 }  // namespace hill_climb
 

@@ -119,6 +119,13 @@ size_t parse_usize(const std::string &flag, const std::string &v)
     return (size_t)x;
 }
 
+void exit_if_invalid(const std::string &why)  // an options struct's validate(): the message, or empty
+{
+    if (why.empty()) return;
+    std::fprintf(stderr, "error: %s\n", why.c_str());
+    std::exit(1);
+}
+
 Args parse(int argc, char **argv)
 {
     Args a;
@@ -244,27 +251,9 @@ Args parse(int argc, char **argv)
         std::fprintf(stderr, "error: max_depth must be >= 1\n");
         std::exit(1);
     }
-    {   // SAOptions::from_cli validates (mod.rs:708-742)
-        const std::string why = a.opt.sa.validate();
-        if (!why.empty()) {
-            std::fprintf(stderr, "error: %s\n", why.c_str());
-            std::exit(1);
-        }
-    }
-    {   // GAOptions::validate (mod.rs:833-846)
-        const std::string why = a.opt.ga.validate();
-        if (!why.empty()) {
-            std::fprintf(stderr, "error: %s\n", why.c_str());
-            std::exit(1);
-        }
-    }
-    {   // AcoOptions::validate (mod.rs:1115-1153)
-        const std::string why = a.opt.aco.validate();
-        if (!why.empty()) {
-            std::fprintf(stderr, "error: %s\n", why.c_str());
-            std::exit(1);
-        }
-    }
+    exit_if_invalid(a.opt.sa.validate());   // SAOptions::from_cli validates (mod.rs:708-742)
+    exit_if_invalid(a.opt.ga.validate());   // GAOptions::validate (mod.rs:833-846)
+    exit_if_invalid(a.opt.aco.validate());  // AcoOptions::validate (mod.rs:1115-1153)
     a.opt.two_opt_mode = a.best ? TL_MODE_BEST_SWEEP : TL_MODE_REF_ORDER;
     return a;
 }

@@ -170,10 +170,12 @@ def test_python_pipeline_facade(tsplib_dir, goldens):
         TA.pipeline.run_pipeline_stages(prob, ["sa"])
 
 
-def _digest(messages):
-    # the CLI's --progress-digest: FNV-1a 64 over (kind, id count u32, ids u64, f32 bits) per message; Done: the kind only
+def _digest(messages, epoch_updates=False):
+    # the CLI's --progress-digest: FNV-1a 64 over (kind, id count u32, ids u64, f32 bits) per message; Done: the kind only;
+    # EpochUpdate(epoch): kind 3, one id (the epoch), four zero bytes.  The counts are [PathUpdate, CityChange, Done], and with
+    # epoch_updates a fourth, EpochUpdate.
     import struct
-    h, n = 1469598103934665603, [0, 0, 0]
+    h, n = 1469598103934665603, [0, 0, 0, 0]
 
     def feed(b):
         nonlocal h
@@ -181,7 +183,7 @@ def _digest(messages):
             h = ((h ^ x) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
 
     for kind, payload in messages:
-        k = {"PathUpdate": 0, "CityChange": 1, "Done": 2}[kind]
+        k = {"PathUpdate": 0, "CityChange": 1, "Done": 2, "EpochUpdate": 3}[kind]
         n[k] += 1
         feed(bytes([k]))
         if k == 2:
@@ -189,7 +191,7 @@ def _digest(messages):
         ids, v = (payload[0], payload[1]) if k == 0 else ([payload], 0.0)
         feed(struct.pack("<I", len(ids)) + b"".join(struct.pack("<Q", int(i)) for i in ids))
         feed(struct.pack("<f", v) if k == 0 else struct.pack("<I", 0))
-    return n, h
+    return (n if epoch_updates else n[:3]), h
 
 
 def test_cpp_mirror_replays_the_same_progress_messages_as_the_python_mirror(cli, ctx, tsplib_dir):
@@ -218,3 +220,63 @@ def test_cpp_mirror_replays_the_same_progress_messages_as_the_python_mirror(cli,
         n, h = _digest(got)
         assert [int(m.group(1)), int(m.group(2)), int(m.group(3))] == n, name
         assert m.group(4) == f"{h:016x}", name
+
+
+_SWARM = ["--epochs", "6", "--seed", "3", "--n-nearest", "31", "--mutation-probability", "0.25"]
+
+
+def _swarm_heuristic(TA):
+    return TA.HeuristicOptions(epochs=6, n_nearest=31)
+
+
+# (case id, solver, instance, CLI flags, Python call -> solve(prob, tx)).  Every CLI run is `solve <solver> --no-seed`, i.e. the one
+# stage from city order, so the Python side is that solver's solve with init_tour None, the same seed and the same options.
+_REPLAY_CASES = [
+    ("simulated_annealing", "simulated_annealing", "berlin52", ["--epochs", "0", "--cooling-rate", "0.01", "--seed", "1"],
+     lambda TA, p, tx, c: TA.simulated_annealing.solve(p, TA.SAOptions(TA.HeuristicOptions(epochs=0), cooling_rate=1e-2), tx, None, ctx=c, seed=1)),
+    ("tabu_search", "tabu_search", "berlin52", ["--epochs", "150", "--seed", "1"],
+     lambda TA, p, tx, c: TA.tabu_search.solve(p, TA.HeuristicOptions(epochs=150), tx, None, ctx=c, seed=1)),
+    ("genetic_algorithm", "genetic_algorithm", "berlin52", ["--epochs", "5", "--seed", "3", "--mutation-probability", "0.5", "--n-elite", "3"],
+     lambda TA, p, tx, c: TA.genetic_algorithm.solve(p, TA.genetic_algorithm.GAOptions(TA.HeuristicOptions(epochs=5), 0.5, 3), tx, None, ctx=c, seed=3)),
+    ("ant_colony", "ant_colony", "berlin52", ["--epochs", "3", "--seed", "3", "--alpha", "1.5", "--beta", "2.5", "--evaporation-rate", "0.25", "--num-ants", "10"],
+     lambda TA, p, tx, c: TA.ant_colony.solve(p, TA.ant_colony.AcoOptions(TA.HeuristicOptions(epochs=3), 1.5, 2.5, 0.25, 10), tx, None, ctx=c, seed=3)),
+    ("particle_swarm", "particle_swarm", "berlin52", _SWARM,
+     lambda TA, p, tx, c: TA.particle_swarm.solve(p, _swarm_heuristic(TA), tx, None, ctx=c, seed=3)),
+    ("cuckoo_search", "cuckoo_search", "berlin52", _SWARM,
+     lambda TA, p, tx, c: TA.cuckoo_search.solve(p, TA.cuckoo_search.CSOptions(_swarm_heuristic(TA), 0.25), tx, None, ctx=c, seed=3)),
+    ("flower_pollination", "flower_pollination", "berlin52", _SWARM,
+     lambda TA, p, tx, c: TA.flower_pollination.solve(p, TA.flower_pollination.FPAOptions(_swarm_heuristic(TA), 0.25), tx, None, ctx=c, seed=3)),
+    ("gravitational_search", "gravitational_search", "berlin52", _SWARM,
+     lambda TA, p, tx, c: TA.gravitational_search.solve(p, _swarm_heuristic(TA), tx, None, ctx=c, seed=3)),
+    ("kohonen_som", "kohonen_som", "berlin52", ["--epochs", "25", "--seed", "3", "--learning_rate", "0.7", "--radius_fraction", "0.2", "--neuron_multiplier", "4"],
+     lambda TA, p, tx, c: TA.kohonen_som.solve(p, TA.kohonen_som.SOMOptions(25, 0.7, 0.2, 4), tx, None, ctx=c, seed=3)),
+    ("bhk", "bhk", "burma14", [], lambda TA, p, tx, c: TA.bellman_karp.solve(p, TA.HeuristicOptions(), tx, None, ctx=c)),
+    ("branch_and_bound", "branch_and_bound", "burma14", [], lambda TA, p, tx, c: TA.branch_and_bound.solve(p, None, tx, None, ctx=c)),
+    # the best of three: population -> the best chain or run -> that one once more for its trace (an annealing stage counts its
+    # chains with --chains, the swarm solvers with --runs)
+    ("simulated_annealing-best-of-3", "simulated_annealing", "berlin52", ["--epochs", "0", "--cooling-rate", "0.01", "--seed", "1", "--chains", "3"],
+     lambda TA, p, tx, c: TA.simulated_annealing.solve(p, TA.SAOptions(TA.HeuristicOptions(epochs=0), cooling_rate=1e-2), tx, None, ctx=c, seed=1, chains=3)),
+    ("particle_swarm-best-of-3", "particle_swarm", "berlin52", _SWARM + ["--runs", "3"],
+     lambda TA, p, tx, c: TA.particle_swarm.solve(p, _swarm_heuristic(TA), tx, None, ctx=c, seed=3, runs=3)),
+]
+
+
+@pytest.mark.parametrize("case", _REPLAY_CASES, ids=[c[0] for c in _REPLAY_CASES])
+def test_cpp_mirror_replays_seeded_and_exact_solvers_as_the_python_mirror(case, cli, ctx, tsplib_dir):
+    # The C++ mirror's replays of the seeded solvers (from their trace entries) and of the two exact solvers against the Python
+    # mirror's, by content: the same counts per kind (EpochUpdate the fourth) and the same digest over every id and f32 bit.
+    import re
+    import teeline_amd as TA
+    name, solver, instance, flags, solve = case
+    f = os.path.join(tsplib_dir, instance + ".tsp")
+    r = subprocess.run([cli, "solve", solver, "--no-seed", "-i", f, "--progress-digest", *flags], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    m = re.search(r"progress: path_updates=(\d+) city_changes=(\d+) done=(\d+) digest=([0-9a-f]{16})(?: epoch_updates=(\d+))?", r.stderr)
+    assert m, r.stderr
+    print(name, m.group(0))
+    got = []
+    sol = solve(TA, TA.tsplib.read_from_file(f).problem(), lambda kind, payload: got.append((kind, payload)), ctx)
+    n, h = _digest(got, epoch_updates=True)
+    assert [int(m.group(1)), int(m.group(2)), int(m.group(3)), int(m.group(5) or 0)] == n, name
+    assert m.group(4) == f"{h:016x}", name
+    assert r.stdout.splitlines()[-2:] == TA.pipeline.format_solution(sol).splitlines(), name
