@@ -13,6 +13,7 @@ import numpy as np
 
 from _ga_oracle import INIT_EVENT, SLOT_SHUFFLE, draw, draw_key, position, uniform
 from _sa_oracle import chain_key, dist_fn, tour_length
+from _swarm_oracle import cached
 
 DEFAULTS = dict(epochs=150, alpha=1.0, beta=2.0, evaporation_rate=0.5, num_ants=25)  # mod.rs:1091-1112
 TAU_MIN_RATIO = np.float32(1e-4)
@@ -279,14 +280,5 @@ def messages(res, ids=None):
     return out + [("Done", None)]
 
 
-_cache = {}
-
-
-def solve_cached(key, *args, **kw):
-    """solve() once per process and key; the results are shared between tests and must not be written to"""
-    if key not in _cache:
-        out = solve(*args, **kw)
-        out["tour"].setflags(write=False)
-        _cache[key] = out
-    return _cache[key]
+solve_cached = cached(solve)
 

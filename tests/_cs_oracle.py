@@ -15,6 +15,7 @@ import numpy as np
 
 from _ga_oracle import SLOT_SHUFFLE, draw, draw_key, init_event, position  # noqa: F401  (draw: re-exported)
 from _sa_oracle import chain_key, dist_fn, tour_length
+from _swarm_oracle import NONE, bits, cached, log_words, messages, route_words, uniform  # noqa: F401
 
 SLOT_LEVY, SLOT_TARGET, SLOT_ABANDON = 0, 12, 13
 SLOT_REV_I, SLOT_REV_J, SLOT_REPLACE = 0, 1, 2
@@ -24,7 +25,6 @@ DEFAULT_NESTS = 25
 MAX_NESTS = 4096
 EVENT_LIMIT = 1 << 58
 DEFAULTS = dict(epochs=10_000, n_nearest=3, mutation_probability=0.001)  # mod.rs:604-611, 918-925
-NONE = 0xFFFFFFFF
 MIN_POSITIVE = 2.2250738585072014e-308
 SIGMA_U = 0.6966
 LN2_HI, LN2_LO, LOG2E, HALF_PI = 6.93147180369123816490e-01, 1.90821492927058770002e-10, 1.4426950408889634, 1.5707963267948966
@@ -49,10 +49,6 @@ def base(epoch, N, c, n):
 
 def events_fit(epochs, N, n):
     return epochs * N * (n + 1) <= EVENT_LIMIT
-
-
-def uniform(u):
-    return (int(u) >> 11) * 2.0 ** -53
 
 
 # ---------------------------------------------------------------- the Lévy step, on arrays (one statement for one draw and for 10^6)
@@ -309,22 +305,8 @@ def solve(xy, packed, n, init=None, *, epochs, n_nearest=3, mutation_probability
                 counters=dict(flights=epochs * N, improved=len(improvements) - 1), nests=N)
 
 
-def bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
-
-
 def f64_bits(x):
     return int(np.array([x], dtype=np.float64).view(np.uint64)[0])
-
-
-def log_words(res, route_cap=None):
-    """the improvement log of tl_cuckoo_search_trace: [epoch, source, cost bits, route index]"""
-    rows = [[e, i, bits(c), k if route_cap is None or k < route_cap else NONE] for k, (e, i, c, _r) in enumerate(res["improvements"])]
-    return np.asarray(rows, dtype=np.uint32).reshape(-1, 4)
-
-
-def route_words(res, n):
-    return np.asarray([r for _e, _i, _c, r in res["improvements"]], dtype=np.uint32).reshape(-1, n)
 
 
 def epoch_words(res):
@@ -335,28 +317,4 @@ def epoch_words(res):
     return np.asarray(rows, dtype=np.uint32).reshape(-1, 4 * N)
 
 
-def messages(res, ids=None):
-    """what the reference sends (cuckoo_search.rs:73-75,98-100,120-122,127-129,132-134)"""
-    name = (lambda r: [int(v) for v in r]) if ids is None else (lambda r: [int(v) for v in np.asarray(ids)[np.asarray(r, dtype=np.int64)]])
-    imp = res["improvements"]
-    out = [("PathUpdate", (name(imp[0][3]), float(imp[0][2])))]
-    k = 1
-    for e in range(len(res["epochs"])):
-        while k < len(imp) and imp[k][0] == e:
-            out.append(("PathUpdate", (name(imp[k][3]), float(imp[k][2]))))
-            k += 1
-        out.append(("EpochUpdate", e))
-    out.append(("Done", None))
-    return out
-
-
-_cache = {}
-
-
-def solve_cached(key, *args, **kw):
-    """solve() once per process and key; the results are shared between tests and must not be written to"""
-    if key not in _cache:
-        res = solve(*args, **kw)
-        res["tour"].setflags(write=False)
-        _cache[key] = res
-    return _cache[key]
+solve_cached = cached(solve)

@@ -9,6 +9,7 @@ import numpy as np
 
 from _sa_oracle import dist_fn, tour_length
 from _som_oracle import cossin2pi
+from _swarm_oracle import cached
 
 DEFAULTS = dict(k_max=4, m=200, lam=0.05, lambda_decay=0.5, lr=0.05, epochs=400)  # mod.rs:1341-1352
 TWO_PI = 6.283185307179586
@@ -229,11 +230,4 @@ def f64_words(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).view(np.uint64).ravel()
 
 
-_CACHE = {}
-
-
-def solve_cached(key, xy, packed, n, **kw):
-    """one oracle run per key for all the tests that need it; the record is shared and left unchanged"""
-    if key not in _CACHE:
-        _CACHE[key] = solve(xy, packed, n, **kw)
-    return _CACHE[key]
+solve_cached = cached(solve, lambda res: res)  # (the record is shared and left unchanged; nothing of it is made read-only)

@@ -16,14 +16,14 @@ import numpy as np
 
 from _cs_oracle import WORDS, levy_from_words
 from _ga_oracle import SLOT_SHUFFLE, draw, draw_key, init_event, position  # noqa: F401  (draw: re-exported)
-from _pso_oracle import swap_sequence_inverse  # noqa: F401  (the O(n) walk, tested equal to the literal search: for the large sizes)
 from _sa_oracle import chain_key, dist_fn, tour_length
+from _swarm_oracle import (NONE, apply_swaps, bits, cached, log_words, messages, route_words, shuffled, swap_sequence_inverse,  # noqa: F401
+                           swap_sequence_literal, uniform)
 
 SLOT_SWITCH, SLOT_LEVY, SLOT_J, SLOT_K, SLOT_EPSILON = 0, 1, 13, 14, 15
 DEFAULT_FLOWERS = 25
 MAX_FLOWERS = 4096
 DEFAULTS = dict(epochs=10_000, n_nearest=3, mutation_probability=0.001)  # mod.rs:604-611, 1003-1010
-NONE = 0xFFFFFFFF
 GLOBAL_BIT = 1 << 31
 
 
@@ -39,10 +39,6 @@ def switch_prob(mutation_probability):
 
 def event(epoch, N, i):
     return epoch * N + i
-
-
-def uniform(u):
-    return (int(u) >> 11) * 2.0 ** -53
 
 
 def clamped_ceil(x, length):
@@ -94,39 +90,10 @@ def roles(n, N, epochs, seeded):
     return out
 
 
-def swap_sequence_literal(src, dst):
-    """swap_sequence (route.rs:118-134) as written: a linear search from i + 1 on (list.index is one); saturating_sub for n = 0"""
-    tmp = [int(v) for v in src]
-    dst = [int(v) for v in dst]
-    seq = []
-    for i in range(max(len(tmp) - 1, 0)):
-        if tmp[i] != dst[i]:
-            j = tmp.index(dst[i], i + 1)
-            seq.append((i, j))
-            tmp[i], tmp[j] = tmp[j], tmp[i]
-    return seq
-
-
-def apply_swaps(pos, swaps):
-    """apply_swaps (route.rs:137-143)"""
-    out = list(pos)
-    for i, j in swaps:
-        out[i], out[j] = out[j], out[i]
-    return out
-
-
 def pollinate(flower, source, target, prefix, seq=swap_sequence_literal):
     """the move on given tours: (the sequence's length, flower after the first min(prefix, length) swaps of it)"""
     s = seq(source, target)
     return len(s), apply_swaps(flower, s[:min(prefix, len(s))])
-
-
-def shuffled(key, n, i):
-    r = list(range(n))
-    for j in range(n - 1, 0, -1):
-        k = position(draw_key(key, init_event(n, i, j), SLOT_SHUFFLE), j + 1)
-        r[j], r[k] = r[k], r[j]
-    return r
 
 
 def move(key, ev, i, N, sp, flower_i, gbest, flower_of, seq, half=0.5):
@@ -204,20 +171,6 @@ def solve(xy, packed, n, init=None, *, epochs, n_nearest=3, mutation_probability
                 counters=dict(moves=epochs * N, improved=len(improvements) - 1), flowers=N)
 
 
-def bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
-
-
-def log_words(res, route_cap=None):
-    """the improvement log of tl_flower_pollination_trace: [epoch, flower, cost bits, route index]"""
-    rows = [[e, i, bits(c), k if route_cap is None or k < route_cap else NONE] for k, (e, i, c, _r) in enumerate(res["improvements"])]
-    return np.asarray(rows, dtype=np.uint32).reshape(-1, 4)
-
-
-def route_words(res, n):
-    return np.asarray([r for _e, _i, _c, r in res["improvements"]], dtype=np.uint32).reshape(-1, n)
-
-
 def epoch_words(res):
     """the per-epoch record: flower cost bits | bit 31 global, else j | k << 12 | sequence length | prefix << 16 | bit 0 accepted, bit 1 built again"""
     N = res["flowers"]
@@ -226,28 +179,4 @@ def epoch_words(res):
     return np.asarray(rows, dtype=np.uint32).reshape(-1, 4 * N)
 
 
-def messages(res, ids=None):
-    """what the reference sends (flower_pollination.rs:113-115,133-136,142-144,147-149)"""
-    name = (lambda r: [int(v) for v in r]) if ids is None else (lambda r: [int(v) for v in np.asarray(ids)[np.asarray(r, dtype=np.int64)]])
-    imp = res["improvements"]
-    out = [("PathUpdate", (name(imp[0][3]), float(imp[0][2])))]
-    k = 1
-    for e in range(len(res["epochs"])):
-        while k < len(imp) and imp[k][0] == e:
-            out.append(("PathUpdate", (name(imp[k][3]), float(imp[k][2]))))
-            k += 1
-        out.append(("EpochUpdate", e))
-    out.append(("Done", None))
-    return out
-
-
-_cache = {}
-
-
-def solve_cached(key, *args, **kw):
-    """solve() once per process and key; the results are shared between tests and must not be written to"""
-    if key not in _cache:
-        res = solve(*args, **kw)
-        res["tour"].setflags(write=False)
-        _cache[key] = res
-    return _cache[key]
+solve_cached = cached(solve)

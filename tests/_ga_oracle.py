@@ -10,6 +10,7 @@ from..=to and does NOT recompute the fitness; best() is the last of equal maxima
 import numpy as np
 
 from _sa_oracle import G, chain_key, dist_fn, mix, pair_from_key, tour_length
+from _swarm_oracle import cached, read_only
 
 INIT_EVENT = 1 << 58
 SLOT_SELECT, SLOT_MUTATE, SLOT_SHUFFLE, SLOT_COUNT = 22, 24, 26, 27
@@ -211,13 +212,4 @@ def solve(xy, packed, n, init=None, *, epochs, mutation_probability=0.001, n_eli
     return out + (pops,) if keep else out
 
 
-_cache = {}
-
-
-def solve_cached(key, *args, **kw):
-    """solve() once per process and key; the results are shared between tests and must not be written to"""
-    if key not in _cache:
-        out = solve(*args, **kw)
-        out[0].setflags(write=False)
-        _cache[key] = (out[0], out[1], tuple(out[2]), dict(out[3])) + tuple(out[4:])
-    return _cache[key]
+solve_cached = cached(solve, lambda out: (read_only(out[0]), out[1], tuple(out[2]), dict(out[3])) + tuple(out[4:]))

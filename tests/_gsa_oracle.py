@@ -14,8 +14,10 @@ import numpy as np
 
 from _cs_oracle import exp_spec
 from _ga_oracle import SLOT_SHUFFLE, draw, draw_key, init_event, position  # noqa: F401  (draw: re-exported)
-from _pso_oracle import apply_swaps, keep, swap_sequence_inverse, swap_sequence_literal, vmax  # noqa: F401
+from _pso_oracle import keep, vmax
 from _sa_oracle import chain_key, dist_fn, tour_length
+from _swarm_oracle import (NONE, apply_swaps, bits, cached, log_words, messages, route_words, shuffled, swap_sequence_inverse,  # noqa: F401
+                           swap_sequence_literal, uniform)
 
 SLOT_R = 0
 DEFAULT_AGENTS = 25
@@ -24,7 +26,6 @@ MAX_PULL = 20
 G0, ALPHA, INERTIA_W = 20.0, 1.0, 0.0
 EPSILON = 2.220446049250313e-16
 DEFAULTS = dict(epochs=10_000, n_nearest=3)  # mod.rs:604-611
-NONE = 0xFFFFFFFF
 
 
 class RefPanics(Exception):
@@ -41,10 +42,6 @@ def kbest_count(N):
 
 def event(epoch, N, i, j):
     return (epoch * N + i) * N + j
-
-
-def uniform(u):
-    return (int(u) >> 11) * 2.0 ** -53
 
 
 def g_of(epoch, epochs):
@@ -90,14 +87,6 @@ def roles(n, N, epochs, seeded):
         for i in range(N):
             out += [(event(e, N, i, j), SLOT_R, ("r", e, i, j)) for j in range(N)]
     return out
-
-
-def shuffled(key, n, i):
-    r = list(range(n))
-    for j in range(n - 1, 0, -1):
-        k = position(draw_key(key, init_event(n, i, j), SLOT_SHUFFLE), j + 1)
-        r[j], r[k] = r[k], r[j]
-    return r
 
 
 def pull(src, dst, m, seq=swap_sequence_literal):
@@ -171,22 +160,8 @@ def solve(xy, packed, n, init=None, *, epochs, n_nearest=3, seed=1, run=0, seq=s
                 counters=dict(moves=epochs * N, improved=len(improvements) - 1), agents=N)
 
 
-def bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
-
-
 def f64_bits(x):
     return int(np.array([x], dtype=np.float64).view(np.uint64)[0])
-
-
-def log_words(res, route_cap=None):
-    """the improvement log of tl_gravitational_search_trace: [epoch, agent, cost bits, route index]"""
-    rows = [[e, i, bits(c), k if route_cap is None or k < route_cap else NONE] for k, (e, i, c, _r) in enumerate(res["improvements"])]
-    return np.asarray(rows, dtype=np.uint32).reshape(-1, 4)
-
-
-def route_words(res, n):
-    return np.asarray([r for _e, _i, _c, r in res["improvements"]], dtype=np.uint32).reshape(-1, n)
 
 
 def epoch_words(res):
@@ -201,21 +176,6 @@ def pairs_words(pairs):
     return [i | (j << 16) for i, j in pairs]
 
 
-def messages(res, ids=None):
-    """what the reference sends (gravitational_search.rs:72-74,130-132,136-138,141-143)"""
-    name = (lambda r: [int(v) for v in r]) if ids is None else (lambda r: [int(v) for v in np.asarray(ids)[np.asarray(r, dtype=np.int64)]])
-    imp = res["improvements"]
-    out = [("PathUpdate", (name(imp[0][3]), float(imp[0][2])))]
-    k = 1
-    for e in range(len(res["epochs"])):
-        while k < len(imp) and imp[k][0] == e:
-            out.append(("PathUpdate", (name(imp[k][3]), float(imp[k][2]))))
-            k += 1
-        out.append(("EpochUpdate", e))
-    out.append(("Done", None))
-    return out
-
-
 def evidence(res):
     """the share of live pulls whose j had already moved in the epoch, and the mean number of live pulls per move"""
     pulls = [p for ep in res["epochs"] for m in ep["moves"] for p in m["pulls"]]
@@ -223,13 +183,4 @@ def evidence(res):
     return dict(moved_share=(sum(p["moved"] for p in pulls) / len(pulls)) if pulls else 0.0, live_per_move=len(pulls) / max(moves, 1))
 
 
-_cache = {}
-
-
-def solve_cached(key, *args, **kw):
-    """solve() once per process and key; the results are shared between tests and must not be written to"""
-    if key not in _cache:
-        res = solve(*args, **kw)
-        res["tour"].setflags(write=False)
-        _cache[key] = res
-    return _cache[key]
+solve_cached = cached(solve)

@@ -9,6 +9,7 @@ the best route is returned; every cost is tour_length (closing edge first, seque
 import numpy as np
 
 from _sa_oracle import G, M64, chain_key, dist_fn, mix, pair_from_key, tour_length
+from _swarm_oracle import bits, cached  # noqa: F401  (bits: re-exported)
 
 NONE = 0xFFFFFFFF
 INIT_EVENT = 1 << 58
@@ -39,10 +40,6 @@ def roles(n, epochs):
         out += [((e, s), ("pair", e, s)) for s in range(22)]
         out += [((shuffle_event(e, n, j), SLOT_SHUFFLE), ("shuffle", e, j)) for j in range(1, n)]
     return out
-
-
-def bits(x):
-    return int(np.array([x], dtype=np.float32).view(np.uint32)[0])
 
 
 def solve(xy, packed, n, init=None, *, seed=1, chain=0, epochs=10_000, platoo_epochs=500):
@@ -167,13 +164,4 @@ def replay(ids, start, res):
     return out
 
 
-_cache = {}
-
-
-def solve_cached(key, *args, **kw):
-    """solve() once per process and key; the results are shared between tests and must not be written to"""
-    if key not in _cache:
-        res = solve(*args, **kw)
-        res["tour"].setflags(write=False)
-        _cache[key] = res
-    return _cache[key]
+solve_cached = cached(solve)

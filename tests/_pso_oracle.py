@@ -14,12 +14,13 @@ import numpy as np
 
 from _ga_oracle import SLOT_SHUFFLE, draw, draw_key, init_event, position  # noqa: F401  (draw: re-exported)
 from _sa_oracle import chain_key, dist_fn, tour_length
+from _swarm_oracle import (NONE, apply_swaps, bits, cached, log_words, orbits, route_words, shuffled, swap_sequence_inverse,  # noqa: F401
+                           swap_sequence_literal, swap_sequence_orbit, uniform)
 
 SLOT_R1, SLOT_R2 = 0, 1
 DEFAULT_PARTICLES = 30
 MAX_PARTICLES = 4096
 DEFAULTS = dict(epochs=10_000, n_nearest=3)  # mod.rs:604-611
-NONE = 0xFFFFFFFF
 
 
 def particles(n_nearest):
@@ -32,10 +33,6 @@ def vmax(n):
 
 def step_event(epoch, P, particle):
     return epoch * P + particle
-
-
-def uniform(u):
-    return (u >> 11) * 2.0 ** -53
 
 
 def weight(epoch, epochs):
@@ -62,85 +59,6 @@ def roles(n, P, epochs, seeded):
             out.append((step_event(e, P, i), SLOT_R1, ("r1", e, i)))
             out.append((step_event(e, P, i), SLOT_R2, ("r2", e, i)))
     return out
-
-
-def swap_sequence_literal(src, dst):
-    """swap_sequence (route.rs:118-134) as written: a linear search from i + 1 on (list.index is one)"""
-    tmp = [int(v) for v in src]
-    dst = [int(v) for v in dst]
-    seq = []
-    for i in range(max(len(tmp) - 1, 0)):
-        if tmp[i] != dst[i]:
-            j = tmp.index(dst[i], i + 1)
-            seq.append((i, j))
-            tmp[i], tmp[j] = tmp[j], tmp[i]
-    return seq
-
-
-def swap_sequence_inverse(src, dst):
-    """the same walk with a table of where every city is instead of the search: O(n)"""
-    tmp = [int(v) for v in src]
-    where = [0] * len(tmp)
-    for k, c in enumerate(tmp):
-        where[c] = k
-    seq = []
-    for i in range(max(len(tmp) - 1, 0)):
-        want = int(dst[i])
-        if tmp[i] != want:
-            j = where[want]
-            seq.append((i, j))
-            where[tmp[i]], where[want] = j, i
-            tmp[i], tmp[j] = tmp[j], tmp[i]
-    return seq
-
-
-def orbits(src, dst):
-    """pi(p) = src^-1[dst[p]] and the lengths of its cycles"""
-    n = len(src)
-    inv = [0] * n
-    for k, c in enumerate(src):
-        inv[int(c)] = k
-    pi = [inv[int(dst[p])] for p in range(n)]
-    seen, lens = [False] * n, []
-    for s in range(n):
-        if not seen[s]:
-            k, p = 0, s
-            while not seen[p]:
-                seen[p] = True
-                p = pi[p]
-                k += 1
-            lens.append(k)
-    return pi, lens
-
-
-def swap_sequence_orbit(src, dst):
-    """the form the device computes (csrc/particle_swarm.hip): in ascending i, (i, q) for every i that is not the largest position
-    of its pi-cycle, q the first of pi(i), pi^2(i), .. above i"""
-    pi, _ = orbits(src, dst)
-    seq = []
-    for i in range(len(pi)):
-        p = pi[i]
-        while p < i:
-            p = pi[p]
-        if p > i:
-            seq.append((i, p))
-    return seq
-
-
-def apply_swaps(pos, swaps):
-    """apply_swaps (route.rs:137-143)"""
-    out = list(pos)
-    for i, j in swaps:
-        out[i], out[j] = out[j], out[i]
-    return out
-
-
-def shuffled(key, n, particle):
-    r = list(range(n))
-    for j in range(n - 1, 0, -1):
-        k = position(draw_key(key, init_event(n, particle, j), SLOT_SHUFFLE), j + 1)
-        r[j], r[k] = r[k], r[j]
-    return r
 
 
 def solve(xy, packed, n, init=None, *, epochs, n_nearest=3, seed=1, run=0, seq=swap_sequence_literal, mutate=None):
@@ -203,27 +121,13 @@ def solve(xy, packed, n, init=None, *, epochs, n_nearest=3, seed=1, run=0, seq=s
                 counters=dict(steps=epochs * P, improved=len(improvements) - 1), particles=P, vmax=vm)
 
 
-def bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
-
-
-def log_words(res, route_cap=None):
-    """the improvement log of tl_particle_swarm_trace: [epoch, particle, cost bits, route index]"""
-    rows = [[e, i, bits(c), k if route_cap is None or k < route_cap else NONE] for k, (e, i, c, _r) in enumerate(res["improvements"])]
-    return np.asarray(rows, dtype=np.uint32).reshape(-1, 4)
-
-
-def route_words(res, n):
-    return np.asarray([r for _e, _i, _c, r in res["improvements"]], dtype=np.uint32).reshape(-1, n)
-
-
 def epoch_words(res):
     """the per-epoch record: every particle's cost bits, then every particle's velocity length"""
     P = res["particles"]
     return np.asarray([[bits(c) for c in ep["costs"]] + list(ep["vlens"]) for ep in res["epochs"]], dtype=np.uint32).reshape(-1, 2 * P)
 
 
-def messages(res, ids=None):
+def messages(res, ids=None):  # (not _swarm_oracle's: this one tolerates an empty improvement list, as the reference's `if let Some` does)
     """what the reference sends (particle_swarm.rs:72-74,114-116,120-122,125-127)"""
     name = (lambda r: [int(v) for v in r]) if ids is None else (lambda r: [int(v) for v in np.asarray(ids)[np.asarray(r, dtype=np.int64)]])
     imp = res["improvements"]
@@ -240,13 +144,4 @@ def messages(res, ids=None):
     return out
 
 
-_cache = {}
-
-
-def solve_cached(key, *args, **kw):
-    """solve() once per process and key; the results are shared between tests and must not be written to"""
-    if key not in _cache:
-        res = solve(*args, **kw)
-        res["tour"].setflags(write=False)
-        _cache[key] = res
-    return _cache[key]
+solve_cached = cached(solve)

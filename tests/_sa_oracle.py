@@ -12,6 +12,8 @@ import math
 
 import numpy as np
 
+from _swarm_oracle import cached, read_only
+
 M64 = (1 << 64) - 1
 G = 0x9E3779B97F4A7C15
 F32_EPS = np.float32(1.1920929e-07)
@@ -185,13 +187,4 @@ def solve(xy, packed, n, init=None, *, seed=1, chain=0, temps=None, **opts):
     return tour.astype(np.uint32), np.float32(cost), trace
 
 
-_cache = {}
-
-
-def solve_cached(key, *args, **kw):
-    """solve() once per process and key; the results are shared between tests and must not be written to"""
-    if key not in _cache:
-        tour, cost, trace = solve(*args, **kw)
-        tour.setflags(write=False)
-        _cache[key] = (tour, cost, tuple(trace))
-    return _cache[key]
+solve_cached = cached(solve, lambda out: (read_only(out[0]), out[1], tuple(out[2])))

@@ -17,6 +17,7 @@ import numpy as np
 from _cs_oracle import COS_C, HALF_PI, SIN_C, _horner, exp_spec
 from _ga_oracle import draw, draw_key, position  # noqa: F401  (draw: re-exported)
 from _sa_oracle import chain_key, dist_fn, tour_length
+from _swarm_oracle import bits, cached, read_only  # noqa: F401  (bits: re-exported)
 
 SLOT_CITY = 0
 MAX_NEURONS = 65536
@@ -192,10 +193,6 @@ def solve(xy, packed, n, *, epochs, learning_rate=0.8, radius_fraction=0.1, neur
                 trivial=False, neurons=M)
 
 
-def bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
-
-
 def f64_bits(x):
     return int(np.array([x], dtype=np.float64).view(np.uint64)[0])
 
@@ -223,14 +220,4 @@ def messages(res, ids=None):
     return out
 
 
-_cache = {}
-
-
-def solve_cached(key, *args, **kw):
-    """solve() once per process and key; the results are shared between tests and must not be written to"""
-    if key not in _cache:
-        res = solve(*args, **kw)
-        res["tour"].setflags(write=False)
-        res["ring"].setflags(write=False)
-        _cache[key] = res
-    return _cache[key]
+solve_cached = cached(solve, lambda res: (read_only(res["tour"]), read_only(res["ring"]), res)[2])

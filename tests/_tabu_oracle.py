@@ -13,6 +13,7 @@ from collections import deque
 import numpy as np
 
 from _sa_oracle import G, chain_key, dist_fn, mix, pair_from_key, tour_length
+from _swarm_oracle import cached, read_only
 
 CHUNK = 64  # candidates costed at once (any value gives the same chain: the first qualifying candidate in order is taken)
 
@@ -123,21 +124,17 @@ def solve(xy, packed, n, init=None, *, epochs, seed=1, chain=0, record=None):
     return best.astype(np.uint32), np.float32(best_distance), log, cnt
 
 
-_cache = {}
-_records = {}
+def _solve_recorded(*args, **kw):
+    """solve()'s result and, last, its `record`"""
+    rec = {}
+    tour, cost, log, cnt = solve(*args, record=rec, **kw)
+    return read_only(tour), cost, tuple(log), dict(cnt), rec
 
 
-def solve_cached(key, *args, **kw):
-    """solve() once per process and key; the results are shared between tests and must not be written to"""
-    if key not in _cache:
-        rec = {}
-        tour, cost, log, cnt = solve(*args, record=rec, **kw)
-        tour.setflags(write=False)
-        _cache[key] = (tour, cost, tuple(log), dict(cnt))
-        _records[key] = rec
-    return _cache[key]
+_recorded = cached(_solve_recorded, tuple)
+solve_cached = lambda key, *args, **kw: _recorded(key, *args, **kw)[:4]  # noqa: E731
 
 
 def record_of(key):
     """the list's record (solve's `record`) of a chain that solve_cached has computed under `key`"""
-    return _records[key]
+    return _recorded.cache[key][4]

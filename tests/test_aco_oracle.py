@@ -15,14 +15,11 @@ import _aco_cases as AC
 import _aco_oracle as ACO
 import _sa_cases as K
 import _sa_oracle as SA
+from _swarm_oracle import bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = json.load(open(os.path.join(ROOT, "tests", "golden", "goldens_aco.json")))
 CASES = AC.golden_cases()
-
-
-def bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
 
 
 def f32(b):

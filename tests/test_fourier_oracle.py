@@ -13,6 +13,7 @@ import pytest
 
 import _fourier_cases as FC
 import _fourier_oracle as FO
+from _raw_context import _vp
 import _sa_cases as K
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,10 +26,6 @@ bits = FO.bits
 def lib():
     from teeline_amd import _capi
     return _capi.load()
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _compile(tmp, name, extra):

@@ -15,14 +15,11 @@ import _ga_cases as GC
 import _ga_oracle as GA
 import _sa_cases as K
 import _sa_oracle as SA
+from _swarm_oracle import bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = json.load(open(os.path.join(ROOT, "tests", "golden", "goldens_ga.json")))
 CASES = GC.golden_cases()
-
-
-def bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
 
 
 def trace_words(trace):

@@ -12,21 +12,15 @@ import pytest
 
 import _aco_cases as AC
 import _aco_oracle as ACO
+from _raw_context import _vp, jitter_context
 import _sa_cases as K
+from _swarm_harness import okey
+from _swarm_oracle import bits
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORK = 8 << 30  # the workspace the entries plan with (include/teeline_gpu.h)
 CH = AC.CHUNK
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
 
 
 def par(o):
@@ -56,10 +50,6 @@ def gpu_population(ctx, xy, packed, n, init, init_count, first, count, o):
     rc = ctx.lib.tl_ant_colony_population(ctx.handle, _vp(xy), n, _vp(packed), _vp(ini), init_count, first, count, *par(o), _vp(out), _vp(costs), C.byref(best),
                                           C.byref(st))
     return rc, out, costs, best.value, st.as_dict()
-
-
-def okey(key, n, init, o):
-    return (key, n, None if init is None else tuple(int(v) for v in init), tuple(sorted(o.items())))
 
 
 def check_run(ctx, key, xy, packed, n, init, o, keep=False):
@@ -404,34 +394,13 @@ def test_cli_equals_the_oracle(ctx):
 
 
 # ---------------------------------------------------------------- jitter build
-class _RawContext:
-    """A context of another build of the library (ctypes only: the package binds the product library)."""
-
-    def __init__(self, path):
-        from teeline_amd import _capi
-        self.lib = C.CDLL(path)
-        vp, u32, u64, f32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float
-        self.lib.tl_create.argtypes = [C.c_int, u32, C.POINTER(vp)]
-        self.lib.tl_destroy.argtypes = [vp]
-        self.lib.tl_destroy.restype = None
-        self.lib.tl_last_error.argtypes = [vp]
-        self.lib.tl_last_error.restype = C.c_char_p
-        self.lib.tl_ant_colony_trace_run.argtypes = [vp, vp, u32, vp, vp, u32, f32, f32, f32, u32, u64, u32, vp, C.POINTER(f32), C.POINTER(_capi.TlStats), vp, u32,
-                                                     C.POINTER(u32), vp, u32, C.POINTER(u32)]
-        self.handle = vp()
-        rc = self.lib.tl_create(0, 0, C.byref(self.handle))
-        assert rc == 0, self.lib.tl_last_error(None)
-
-    def close(self):
-        self.lib.tl_destroy(self.handle)
-
-
 def test_jitter_build():
     """n = 130 with 65 ants on the race-stress build (-DTL_JITTER: waves leave every barrier far apart): the double-buffered tiles,
     the per-ant chunk of the second walk, two groups of ants"""
-    lib = os.path.join(ROOT, "teeline_amd", "libteeline_gpu_jitter.so")
-    assert os.path.exists(lib), "built by __graft_entry__.build()"
-    jctx = _RawContext(lib)
+    from teeline_amd import _capi
+    vp, u32, u64, f32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float
+    jctx = jitter_context({"tl_ant_colony_trace_run": [vp, vp, u32, vp, vp, u32, f32, f32, f32, u32, u64, u32, vp, C.POINTER(f32), C.POINTER(_capi.TlStats), vp, u32, C.POINTER(u32),
+                                                       vp, u32, C.POINTER(u32)]})
     try:
         check_run(jctx, "jitter", AC.instance(130), None, 130, None, dict(AC.OPT, epochs=2, num_ants=65, seed=130, run=0))
     finally:

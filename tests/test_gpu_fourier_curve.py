@@ -11,6 +11,7 @@ import pytest
 
 import _fourier_cases as FC
 import _fourier_oracle as FO
+from _raw_context import _vp
 import _sa_cases as K
 
 pytestmark = pytest.mark.gpu
@@ -18,10 +19,6 @@ pytestmark = pytest.mark.gpu
 CASES = FC.cases()
 bits = FO.bits
 GOLD = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "goldens_fourier.json")))
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def c_opts(o, chunk=0, span=0, threads=0):

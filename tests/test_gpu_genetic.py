@@ -11,21 +11,14 @@ import pytest
 
 import _ga_cases as GC
 import _ga_oracle as GA
+from _raw_context import _vp, jitter_context
 import _sa_cases as K
+from _swarm_oracle import bits
 from test_ga_oracle import PINS
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORK = 8 << 30  # the workspace the entries plan with (include/teeline_gpu.h)
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
 
 
 def gpu_trace(ctx, xy, packed, n, init, epochs, p, e, seed, run=0, cap=None, route_cap=None):
@@ -407,33 +400,12 @@ def test_cli_equals_the_oracle(ctx):
 
 
 # ---------------------------------------------------------------- jitter build
-class _RawContext:
-    """A context of another build of the library (ctypes only: the package binds the product library)."""
-
-    def __init__(self, path):
-        from teeline_amd import _capi
-        self.lib = C.CDLL(path)
-        vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
-        self.lib.tl_create.argtypes = [C.c_int, u32, C.POINTER(vp)]
-        self.lib.tl_destroy.argtypes = [vp]
-        self.lib.tl_destroy.restype = None
-        self.lib.tl_last_error.argtypes = [vp]
-        self.lib.tl_last_error.restype = C.c_char_p
-        self.lib.tl_genetic_algorithm_trace_run.argtypes = [vp, vp, u32, vp, vp, u32, C.c_float, u32, u64, u32, vp, C.POINTER(C.c_float),
-                                                            C.POINTER(_capi.TlStats), vp, u32, C.POINTER(u32), vp, u32]
-        self.handle = vp()
-        rc = self.lib.tl_create(0, 0, C.byref(self.handle))
-        assert rc == 0, self.lib.tl_last_error(None)
-
-    def close(self):
-        self.lib.tl_destroy(self.handle)
-
-
 def test_jitter_build():
     """Runs on the race-stress build (-DTL_JITTER: waves leave every barrier far apart): the compaction's double-buffered wave counts"""
-    lib = os.path.join(ROOT, "teeline_amd", "libteeline_gpu_jitter.so")
-    assert os.path.exists(lib), "built by __graft_entry__.build()"
-    jctx = _RawContext(lib)
+    from teeline_amd import _capi
+    vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+    jctx = jitter_context({"tl_genetic_algorithm_trace_run": [vp, vp, u32, vp, vp, u32, C.c_float, u32, u64, u32, vp, C.POINTER(C.c_float), C.POINTER(_capi.TlStats), vp, u32,
+                                                              C.POINTER(u32), vp, u32]})
     try:
         check_run(jctx, "wide", instance(257), None, 257, None, 3, 0.5, 3, 257)
         check_run(jctx, "epochs", K.small(8), None, 8, None, 50, 0.5, 3, 5)

@@ -5,7 +5,7 @@ live pulls, and g's bits — which pin the draws, the masses and the stable rank
 cut to v_max and the sequential sums) and the stats against the oracle's counters — in both input forms, for the runs of a batch and
 for every span of epochs a launch; and the device's pull alone (tl_gsa_selftest_pull) on planted pairs."""
 import ctypes as C
-import os
+import functools
 
 import numpy as np
 import pytest
@@ -13,81 +13,21 @@ import pytest
 import _gsa_cases as GC
 import _gsa_oracle as GO
 import _sa_cases as K
+import _swarm_harness as H
+from _raw_context import _vp
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WORK = 8 << 30  # the workspace the entries plan with (include/teeline_gpu.h)
+WORK = H.WORK
 bits = GO.bits
 FAST = GO.swap_sequence_inverse  # (tests/test_gsa_oracle.py: equal to the literal search)
 GOLDEN = GC.golden_cases()
 
 
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _opts(o, span=0):
-    from teeline_amd import _capi
-    return _capi.TlGsaOpts(o["epochs"], o["n_nearest"], span)
-
-
-def gpu_trace(ctx, xy, packed, n, init, o, cap=4096, route_cap=None, epoch_cap=None, span=0):
-    from teeline_amd import _capi
-    N = GO.agents(o["n_nearest"])
-    route_cap = min(4096, 1 + min(o["epochs"], 4096) * N) if route_cap is None else route_cap
-    epoch_cap = o["epochs"] if epoch_cap is None else epoch_cap
-    out = np.full(max(n, 1), 0xFFFFFFFF, dtype=np.uint32)
-    log = np.full((max(cap, 1), 4), 0xFFFFFFFF, dtype=np.uint32)
-    routes = np.full((max(route_cap, 1), max(n, 1)), 0xFFFFFFFF, dtype=np.uint32)
-    elog = np.full((max(epoch_cap, 1), 3 * N + 2), 0xFFFFFFFF, dtype=np.uint32)
-    cost, ln, st = C.c_float(-1.0), C.c_uint32(), _capi.TlStats()
-    ini = None if init is None else np.ascontiguousarray(init, dtype=np.uint32)
-    po = _opts(o, span)
-    rc = ctx.lib.tl_gravitational_search_trace(ctx.handle, _vp(xy), n, _vp(packed), _vp(ini), C.byref(po), o["seed"], o.get("run", 0), _vp(out), C.byref(cost),
-                                               C.byref(st), _vp(log), cap, C.byref(ln), _vp(routes), route_cap, _vp(elog), epoch_cap)
-    return rc, out[:n], np.float32(cost.value), log[:min(ln.value, cap)], ln.value, st.as_dict(), routes[:min(ln.value, route_cap), :n], elog[:min(epoch_cap, o["epochs"])]
-
-
-def gpu_population(ctx, xy, packed, n, init, init_count, first, count, o, span=0):
-    from teeline_amd import _capi
-    out = np.full((count, n), 0xFFFFFFFF, dtype=np.uint32)
-    costs = np.full(count, -1.0, dtype=np.float32)
-    moves = np.full(count, 0xFFFFFFFF, dtype=np.uint32)
-    best, st = C.c_uint32(0xFFFFFFFF), _capi.TlStats()
-    ini = None if init is None else np.ascontiguousarray(init, dtype=np.uint32)
-    po = _opts(o, span)
-    rc = ctx.lib.tl_gravitational_search_population(ctx.handle, _vp(xy), n, _vp(packed), _vp(ini), init_count, first, count, C.byref(po), o["seed"], _vp(out),
-                                                    _vp(costs), _vp(moves), C.byref(best), C.byref(st))
-    return rc, out, costs, moves, best.value, st.as_dict()
-
-
-def okey(key, n, init, o):
-    return (key, n, None if init is None else tuple(int(v) for v in init), tuple(sorted(o.items())))
-
-
-def check_run(ctx, key, xy, packed, n, init, o, seq=GO.swap_sequence_literal, span=0):
-    """one run against the oracle: tour, cost, every log record and route, every epoch row, stats"""
-    res = GO.solve_cached(okey(key, n, init, o), xy, packed, n, init, seq=seq, **o)
-    rc, out, gcost, glog, ln, st, routes, elog = gpu_trace(ctx, xy, packed, n, init, o, span=span)
-    assert rc == 0, ctx.lib.tl_last_error(ctx.handle).decode()
-    want = GO.epoch_words(res)
-    for e in range(o["epochs"]):
-        assert elog[e].tolist() == want[e].tolist(), (key, "epoch", e)
-    assert ln == len(res["improvements"]) and glog.tolist() == GO.log_words(res).tolist(), key
-    assert routes.tolist() == GO.route_words(res, n).tolist(), key
-    assert out.tolist() == res["tour"].tolist(), key
-    assert bits(gcost) == bits(res["cost"]), (key, gcost, res["cost"])
-    c = res["counters"]
-    assert (st["sweeps"], st["candidates"], st["moves"]) == (o["epochs"], c["moves"], c["improved"]), (key, st, c)
-    return res
-
-
-def plan(ctx, n, n_nearest=3, count=1, work=WORK, flags=0):
-    info = ctx.device_info()
-    N, t, per = C.c_uint32(), C.c_int(), C.c_uint32()
-    rc = ctx.lib.tl_gravitational_search_plan(n, n_nearest, count, info["cus"], info["lds_bytes"], work, flags, C.byref(N), C.byref(t), C.byref(per))
-    return rc, N.value, t.value, per.value
+GSA = H.GSA
+_opts = GSA.opts
+gpu_trace, gpu_population, plan, check_run = (functools.partial(f, GSA) for f in (H.gpu_trace, H.gpu_population, H.plan, H.check_run))
+okey = H.okey
 
 
 # ---------------------------------------------------------------- the device's pull alone
@@ -289,36 +229,12 @@ def test_new_symbols_resolve(ctx):
 
 
 # ---------------------------------------------------------------- jitter build
-class _RawContext:
-    """A context of another build of the library (ctypes only: the package binds the product library)."""
-
-    def __init__(self, path):
-        from teeline_amd import _capi
-        self.lib = C.CDLL(path)
-        vp, u32, u64, f32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float
-        self.lib.tl_create.argtypes = [C.c_int, u32, C.POINTER(vp)]
-        self.lib.tl_destroy.argtypes = [vp]
-        self.lib.tl_destroy.restype = None
-        self.lib.tl_last_error.argtypes = [vp]
-        self.lib.tl_last_error.restype = C.c_char_p
-        self.lib.tl_gravitational_search_trace.argtypes = [vp, vp, u32, vp, vp, C.POINTER(_capi.TlGsaOpts), u64, u32, vp, C.POINTER(f32), C.POINTER(_capi.TlStats), vp,
-                                                           u32, C.POINTER(u32), vp, u32, vp, u32]
-        self.lib.tl_gsa_selftest_pull.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
-        self.handle = vp()
-        rc = self.lib.tl_create(0, 0, C.byref(self.handle))
-        assert rc == 0, self.lib.tl_last_error(None)
-
-    def close(self):
-        self.lib.tl_destroy(self.handle)
-
-
 def test_jitter_build():
     """a handful of the cases above on the race-stress build (-DTL_JITTER: waves leave every barrier far apart): the live list and its
     wave counts, the slots handed from the pulling waves to the applying lane, the header words, the position written back before the
     next agent reads it"""
-    lib = os.path.join(ROOT, "teeline_amd", "libteeline_gpu_jitter.so")
-    assert os.path.exists(lib), "built by __graft_entry__.build()"
-    jctx = _RawContext(lib)
+    vp, u32 = C.c_void_p, C.c_uint32
+    jctx = H.jitter(GSA, {"tl_gsa_selftest_pull": [vp, vp, vp, vp, u32, u32, vp, vp]})
     try:
         for name in ("small8", "small5_truncated", "synth130_26_agents", "berlin52_default"):
             xy, packed, n, init, o, _want = GC.seeded_case(name)

@@ -3,7 +3,6 @@
 event log and the stats against the oracle's counters — at the plan's window, at window = 1 and window = 64, in both input forms and
 for the chains of a population."""
 import ctypes as C
-import os
 import threading
 
 import numpy as np
@@ -11,17 +10,13 @@ import pytest
 
 import _hill_cases as HC
 import _hill_oracle as HO
+from _raw_context import _vp, jitter_context
 import _sa_cases as K
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = HC.cases()
 bits = HO.bits
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def hopts(epochs, platoo, window=0, reserved=0):
@@ -303,40 +298,15 @@ def test_busy(ctx):
 
 
 # ---------------------------------------------------------------- jitter build
-class _RawContext:
-    """A context of another build of the library (ctypes only: the package binds the product library)."""
-
-    def __init__(self, path):
-        from teeline_amd import _capi
-        self.lib = C.CDLL(path)
-        vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
-        self.lib.tl_create.argtypes = [C.c_int, u32, C.POINTER(vp)]
-        self.lib.tl_destroy.argtypes = [vp]
-        self.lib.tl_destroy.restype = None
-        self.lib.tl_last_error.argtypes = [vp]
-        self.lib.tl_last_error.restype = C.c_char_p
-        self.lib.tl_hill_climb_trace_chain.argtypes = [vp, vp, u32, vp, vp, C.POINTER(_capi.TlHillOpts), u64, u32, vp, C.POINTER(C.c_float),
-                                                       C.POINTER(_capi.TlStats), vp, u32, C.POINTER(u32)]
-        self.lib.tl_hill_climb_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, C.POINTER(_capi.TlHillOpts), u64, vp, vp, vp, C.POINTER(u32),
-                                                      C.POINTER(_capi.TlStats)]
-        self.lib.tl_device_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
-        self.handle = vp()
-        rc = self.lib.tl_create(0, 0, C.byref(self.handle))
-        assert rc == 0, self.lib.tl_last_error(None)
-        cus = C.c_int()
-        assert self.lib.tl_device_info(self.handle, C.byref(cus), None, None, 0) == 0
-        self.cus = cus.value
-
-    def close(self):
-        self.lib.tl_destroy(self.handle)
-
-
 def test_jitter_build():
     """Windows with and without an event on the race-stress build (-DTL_JITTER: waves leave every barrier far apart): the rotating
     verdict slots, the restart and the commit, four waves a chain and one."""
-    lib = os.path.join(ROOT, "teeline_amd", "libteeline_gpu_jitter.so")
-    assert os.path.exists(lib), "built by __graft_entry__.build()"
-    jctx = _RawContext(lib)
+    from teeline_amd import _capi
+    vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+    jctx = jitter_context({"tl_hill_climb_trace_chain": [vp, vp, u32, vp, vp, C.POINTER(_capi.TlHillOpts), u64, u32, vp, C.POINTER(C.c_float), C.POINTER(_capi.TlStats), vp, u32,
+                                                         C.POINTER(u32)],
+                           "tl_hill_climb_population": [vp, vp, u32, vp, vp, u32, u32, u32, C.POINTER(_capi.TlHillOpts), u64, vp, vp, vp, C.POINTER(u32),
+                                                        C.POINTER(_capi.TlStats)]})
     try:
         for name in ("berlin52_p7", "small8_p1", "berlin52_e63"):
             xy, packed, n, init, o, _w = CASES[name]

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from _raw_context import _vp
 import _som_cases as SC
 import _som_oracle as SO
 
@@ -14,10 +15,6 @@ pytestmark = pytest.mark.gpu
 
 CASES = SC.cases()
 bits = SO.bits
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _opts(o, form=0, work=0):

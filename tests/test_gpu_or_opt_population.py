@@ -10,14 +10,10 @@ import pytest
 
 import _oracle as O
 import _plants as P
+from _raw_context import _vp, jitter_context
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def population(ctx, xy, packed, n, tours, sentinel=None):
@@ -309,31 +305,10 @@ def test_run_population_equals_the_pipeline_per_tour(ctx):
 
 
 # ---------------------------------------------------------------- 11. jitter build
-class _RawContext:
-    """A context of another build of the library (ctypes only: the package binds the product library)."""
-
-    def __init__(self, path):
-        self.lib = C.CDLL(path)
-        self.lib.tl_create.argtypes = [C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
-        self.lib.tl_destroy.argtypes = [C.c_void_p]
-        self.lib.tl_destroy.restype = None
-        self.lib.tl_last_error.argtypes = [C.c_void_p]
-        self.lib.tl_last_error.restype = C.c_char_p
-        self.lib.tl_or_opt_population.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p]
-        self.handle = C.c_void_p()
-        rc = self.lib.tl_create(0, 0, C.byref(self.handle))
-        assert rc == 0, self.lib.tl_last_error(None)
-
-    def close(self):
-        self.lib.tl_destroy(self.handle)
-
-
 def test_jitter_build():
     """Cases 1 and 2 on the race-stress build (-DTL_JITTER: waves leave every barrier far apart)."""
-    lib = os.path.join(ROOT, "teeline_amd", "libteeline_gpu_jitter.so")
-    assert os.path.exists(lib), "built by __graft_entry__.build()"
-    jctx = _RawContext(lib)
+    vp, u32 = C.c_void_p, C.c_uint32
+    jctx = jitter_context({"tl_or_opt_population": [vp, vp, u32, vp, vp, u32, vp, vp, vp, vp]})
     try:
         for n in EDGE_SIZES:
             xy, tours = edge_case(n)

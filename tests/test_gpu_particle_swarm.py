@@ -5,6 +5,7 @@ keeps, the truncation, the swap sequences and the sequential sums of every step,
 epoch the second pass of the commit) and the stats against the oracle's counters — in both input forms and for the runs of a
 batch; and the device's swap sequence alone on given permutation pairs (tl_pso_selftest_swap_sequence)."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -14,80 +15,19 @@ import pytest
 import _pso_cases as PC
 import _pso_oracle as PO
 import _sa_cases as K
+import _swarm_harness as H
+from _raw_context import _vp
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WORK = 8 << 30  # the workspace the entries plan with (include/teeline_gpu.h)
 NT = PC.THREADS
 bits = PO.bits
 
 
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _opts(o):
-    from teeline_amd import _capi
-    return _capi.TlPsoOpts(o["epochs"], o["n_nearest"])
-
-
-def gpu_trace(ctx, xy, packed, n, init, o, cap=4096, route_cap=None, epoch_cap=None):
-    from teeline_amd import _capi
-    P = PO.particles(o["n_nearest"])
-    route_cap = min(4096, 1 + min(o["epochs"], 4096) * P) if route_cap is None else route_cap
-    epoch_cap = o["epochs"] if epoch_cap is None else epoch_cap
-    out = np.full(max(n, 1), 0xFFFFFFFF, dtype=np.uint32)
-    log = np.full((max(cap, 1), 4), 0xFFFFFFFF, dtype=np.uint32)
-    routes = np.full((max(route_cap, 1), max(n, 1)), 0xFFFFFFFF, dtype=np.uint32)
-    elog = np.full((max(epoch_cap, 1), 2 * P), 0xFFFFFFFF, dtype=np.uint32)
-    cost, ln, st = C.c_float(-1.0), C.c_uint32(), _capi.TlStats()
-    ini = None if init is None else np.ascontiguousarray(init, dtype=np.uint32)
-    po = _opts(o)
-    rc = ctx.lib.tl_particle_swarm_trace(ctx.handle, _vp(xy), n, _vp(packed), _vp(ini), C.byref(po), o["seed"], o.get("run", 0), _vp(out), C.byref(cost), C.byref(st),
-                                         _vp(log), cap, C.byref(ln), _vp(routes), route_cap, _vp(elog), epoch_cap)
-    return rc, out[:n], np.float32(cost.value), log[:min(ln.value, cap)], ln.value, st.as_dict(), routes[:min(ln.value, route_cap), :n], elog[:min(epoch_cap, o["epochs"])]
-
-
-def gpu_population(ctx, xy, packed, n, init, init_count, first, count, o):
-    from teeline_amd import _capi
-    out = np.full((count, n), 0xFFFFFFFF, dtype=np.uint32)
-    costs = np.full(count, -1.0, dtype=np.float32)
-    moves = np.full(count, 0xFFFFFFFF, dtype=np.uint32)
-    best, st = C.c_uint32(0xFFFFFFFF), _capi.TlStats()
-    ini = None if init is None else np.ascontiguousarray(init, dtype=np.uint32)
-    po = _opts(o)
-    rc = ctx.lib.tl_particle_swarm_population(ctx.handle, _vp(xy), n, _vp(packed), _vp(ini), init_count, first, count, C.byref(po), o["seed"], _vp(out), _vp(costs),
-                                              _vp(moves), C.byref(best), C.byref(st))
-    return rc, out, costs, moves, best.value, st.as_dict()
-
-
-def okey(key, n, init, o):
-    return (key, n, None if init is None else tuple(int(v) for v in init), tuple(sorted(o.items())))
-
-
-def check_run(ctx, key, xy, packed, n, init, o, **kw):
-    """one run against the oracle: tour, cost, every log record and route, every epoch row, stats"""
-    res = PO.solve_cached(okey(key, n, init, o), xy, packed, n, init, **o, **kw)
-    rc, out, gcost, glog, ln, st, routes, elog = gpu_trace(ctx, xy, packed, n, init, o)
-    assert rc == 0, ctx.lib.tl_last_error(ctx.handle).decode()
-    want = PO.epoch_words(res)
-    for e in range(o["epochs"]):
-        assert elog[e].tolist() == want[e].tolist(), (key, "epoch", e)
-    assert ln == len(res["improvements"]) and glog.tolist() == PO.log_words(res).tolist(), key
-    assert routes.tolist() == PO.route_words(res, n).tolist(), key
-    assert out.tolist() == res["tour"].tolist(), key
-    assert bits(gcost) == bits(res["cost"]), (key, gcost, res["cost"])
-    c = res["counters"]
-    assert (st["sweeps"], st["candidates"], st["moves"]) == (o["epochs"], c["steps"], c["improved"]), (key, st, c)
-    return res
-
-
-def plan(ctx, n, n_nearest=3, count=1, work=WORK, flags=0):
-    info = ctx.device_info()
-    P, t, per = C.c_uint32(), C.c_int(), C.c_uint32()
-    rc = ctx.lib.tl_particle_swarm_plan(n, n_nearest, count, info["cus"], info["lds_bytes"], work, flags, C.byref(P), C.byref(t), C.byref(per))
-    return rc, P.value, t.value, per.value
+PSO = H.PSO
+_opts = PSO.opts
+gpu_trace, plan, check_run = (functools.partial(f, PSO) for f in (H.gpu_trace, H.plan, H.check_run))
+okey = H.okey
 
 
 # ---------------------------------------------------------------- the device's swap sequence
@@ -227,100 +167,31 @@ def test_small_n_needs_no_device(ctx):
 
 
 def test_plain_entry_defaults_and_truncated_trace(ctx):
-    from teeline_amd import _capi
-    xy, _packed_, n, init, o = GOLDEN["berlin52"]
-    res = PO.solve_cached(okey("berlin52", n, init, o), xy, None, n, init, **o)
-    out, gcost, st = np.zeros(52, dtype=np.uint32), C.c_float(), _capi.TlStats()
-    po = _opts(o)
-    assert ctx.lib.tl_particle_swarm(ctx.handle, _vp(xy), 52, None, None, C.byref(po), o["seed"], _vp(out), C.byref(gcost), C.byref(st)) == 0
-    assert out.tolist() == res["tour"].tolist() and bits(gcost.value) == bits(res["cost"])
-    assert (st.sweeps, st.candidates, st.moves) == (o["epochs"], res["counters"]["steps"], res["counters"]["improved"])
-    rc, out2, _c, glog, ln, _st, routes, elog = gpu_trace(ctx, xy, None, 52, None, o, cap=3, route_cap=2, epoch_cap=5)  # truncation is reported
-    assert rc == 0 and ln == len(res["improvements"]) > 3 and len(glog) == 3 and len(routes) == 2 and len(elog) == 5 and out2.tolist() == res["tour"].tolist()
-    assert glog.tolist() == PO.log_words(res, route_cap=2)[:3].tolist() and routes.tolist() == PO.route_words(res, 52)[:2].tolist()
-    assert elog.tolist() == PO.epoch_words(res)[:5].tolist()
+    H.plain_entry_defaults_and_truncated_trace(PSO, ctx, GOLDEN)
 
 
 # ---------------------------------------------------------------- batches
 POP = dict(epochs=4, n_nearest=3, seed=31)
 
 
-def check_population(ctx, xy, n, init, init_count, first, count, sample, o=POP):
-    rc, out, costs, moves, best, st = gpu_population(ctx, xy, None, n, init, init_count, first, count, o)
-    assert rc == 0, ctx.lib.tl_last_error(ctx.handle).decode()
-    assert (np.sort(out, axis=1) == np.arange(n)).all()
-    for r in sample:
-        ini = None if init is None else np.asarray(init).reshape(-1, n)[r if init_count > 1 else 0]
-        res = PO.solve_cached(okey("pop", n, ini, dict(o, run=first + r)), xy, None, n, ini, **dict(o, run=first + r))
-        assert out[r].tolist() == res["tour"].tolist() and bits(costs[r]) == bits(res["cost"]) and moves[r] == res["counters"]["improved"], (count, r)
-    keys = [(bits(c) << 32) | r for r, c in enumerate(costs)]
-    assert best == int(np.argmin(keys)) and st["sweeps"] == o["epochs"] * count and st["moves"] == int(moves.sum())
-    return out, costs
-
-
 def test_batches(ctx):
-    n = 60
-    xy = PC.instance(n)
-    cus = ctx.device_info()["cus"]
-    count = cus + 1
-    out, costs = check_population(ctx, xy, n, None, 0, 0, count, [0, 7, cus])
-    rc, o1, c1, _m, b1, _ = gpu_population(ctx, xy, None, n, None, 0, 7, 1, POP)  # first_run = 7, count = 1 equals run 7 of the batch
-    assert rc == 0 and b1 == 0 and o1[0].tolist() == out[7].tolist() and bits(c1[0]) == bits(costs[7])
-    one = PC.start_tour(n, 3)
-    check_population(ctx, xy, n, one, 1, 100, 3, [0, 1, 2])
-    each = np.stack([PC.start_tour(n, 50 + r) for r in range(3)])
-    check_population(ctx, xy, n, each, 3, 5, 3, [0, 1, 2])
-    assert gpu_population(ctx, xy, None, n, None, 0, 0, 0, POP)[0] == 0  # count == 0: TL_OK, nothing written
+    H.batches(PSO, ctx, PC, POP)
 
 
 def test_more_runs_than_one_launch_sequence(ctx):
     """the run is the grid's y: a sequence holds at most 65535 runs; at n = 3 a 65536th run goes in a second one"""
-    n = 3
-    xy = K.small(3)
-    o = dict(epochs=1, n_nearest=3, seed=3)
-    per = plan(ctx, n, 3, 10 ** 6)[3]
-    assert per == 65535 and plan(ctx, 60, 3, 10, 2 * (6 * 30 * 60 + 120 + 8 * 30 * 21 + 16 * 30) + 2560)[3] == 2  # a small workspace bounds it, too
-    out, costs = check_population(ctx, xy, n, None, 0, 0, per + 1, [0, per - 1, per], o)
-    rc, o1, c1, _m, _b, _ = gpu_population(ctx, xy, None, n, None, 0, per, 1, o)
-    assert rc == 0 and o1[0].tolist() == out[per].tolist() and bits(c1[0]) == bits(costs[per])
+    H.more_runs_than_one_launch_sequence(PSO, ctx, dict(epochs=1, n_nearest=3, seed=3), 2 * (6 * 30 * 60 + 120 + 8 * 30 * 21 + 16 * 30) + 2560)
 
 
 # ---------------------------------------------------------------- context reuse, errors
 def test_context_reuse_larger_then_smaller():
     """stale positions, velocities and logs must not leak: the larger instance leaves its tables where the smaller one's begin"""
-    import teeline_amd as TA
-    with TA.Context(0) as c:
-        check_run(c, "trips", PC.instance(300), None, 300, None, dict(epochs=3, n_nearest=3, seed=300, run=0))
-        check_run(c, "epochs", K.small(8), None, 8, None, dict(epochs=2, n_nearest=3, seed=5, run=0))
-        xy, packed, n, init, o = GOLDEN["gr17_matrix"]
-        check_run(c, "gr17_matrix", xy, packed, n, init, o)
+    H.context_reuse(PSO, [("trips", PC.instance(300), None, 300, None, dict(epochs=3, n_nearest=3, seed=300, run=0)),
+                          ("epochs", K.small(8), None, 8, None, dict(epochs=2, n_nearest=3, seed=5, run=0)), ("gr17_matrix",) + GOLDEN["gr17_matrix"]])
 
 
 def test_errors(ctx):
-    import teeline_amd as TA
-    from teeline_amd import _capi
-    b = K.tsplib("berlin52")
-    err = lambda: ctx.lib.tl_last_error(ctx.handle).decode()  # noqa: E731
-    good = dict(epochs=2, n_nearest=3, seed=1)
-    bad = np.arange(52, dtype=np.uint32)
-    bad[3] = 52
-    assert gpu_trace(ctx, b["xy"], None, 52, bad, good)[0] == _capi.TL_ERR_BADARG and "permutation" in err()
-    assert gpu_trace(ctx, b["xy"], None, 52, None, dict(good, epochs=2 ** 32 - 1), epoch_cap=0)[0] == _capi.TL_ERR_UNSUPPORTED and "epochs" in err()
-    assert gpu_trace(ctx, b["xy"], None, 52, None, dict(good, n_nearest=4097), epoch_cap=0)[0] == _capi.TL_ERR_UNSUPPORTED and "particles" in err()
-    assert plan(ctx, 52, 1024)[:3] == (0, 1024, 64) and plan(ctx, 52, 1024)[3] >= 1 and plan(ctx, 52, 4097) == (0, 0, 0, 0)
-    out, cost = np.zeros(52, dtype=np.uint32), C.c_float()
-    po = _opts(good)
-    assert ctx.lib.tl_particle_swarm(ctx.handle, None, 52, None, None, C.byref(po), 1, _vp(out), C.byref(cost), None) == _capi.TL_ERR_BADARG
-    assert err() == "tl_particle_swarm: NULL argument"
-    assert gpu_population(ctx, b["xy"], None, 52, None, 0, 2 ** 32 - 3, 6, good)[0] == _capi.TL_ERR_BADARG
-    assert err() == "tl_particle_swarm_population: run ids beyond 2^32 - 1"
-    assert gpu_population(ctx, b["xy"], None, 52, np.arange(104, dtype=np.uint32) % 52, 2, 0, 6, good)[0] == _capi.TL_ERR_BADARG and "init_count" in err()
-    ln = C.c_uint32()
-    assert ctx.lib.tl_particle_swarm_trace(ctx.handle, _vp(b["xy"]), 52, None, None, C.byref(po), 1, 0, _vp(out), C.byref(cost), None, None, 4, C.byref(ln), None, 0,
-                                           None, 0) == _capi.TL_ERR_BADARG
-    assert plan(ctx, 52, 3, 1, WORK, 1 << 31)[0] == _capi.TL_ERR_UNSUPPORTED
-    with TA.Context(0, 1 << 31) as odd:  # a bit no flag has
-        assert gpu_trace(odd, b["xy"], None, 52, None, good)[0] == _capi.TL_ERR_UNSUPPORTED
+    H.common_errors(PSO, ctx, "particles")
 
 
 # ---------------------------------------------------------------- mirrors
@@ -397,34 +268,10 @@ def test_cli_equals_the_oracle(ctx):
 
 
 # ---------------------------------------------------------------- jitter build
-class _RawContext:
-    """A context of another build of the library (ctypes only: the package binds the product library)."""
-
-    def __init__(self, path):
-        from teeline_amd import _capi
-        self.lib = C.CDLL(path)
-        vp, u32, u64, f32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float
-        self.lib.tl_create.argtypes = [C.c_int, u32, C.POINTER(vp)]
-        self.lib.tl_destroy.argtypes = [vp]
-        self.lib.tl_destroy.restype = None
-        self.lib.tl_last_error.argtypes = [vp]
-        self.lib.tl_last_error.restype = C.c_char_p
-        self.lib.tl_particle_swarm_trace.argtypes = [vp, vp, u32, vp, vp, C.POINTER(_capi.TlPsoOpts), u64, u32, vp, C.POINTER(f32), C.POINTER(_capi.TlStats), vp, u32,
-                                                     C.POINTER(u32), vp, u32, vp, u32]
-        self.handle = vp()
-        rc = self.lib.tl_create(0, 0, C.byref(self.handle))
-        assert rc == 0, self.lib.tl_last_error(None)
-
-    def close(self):
-        self.lib.tl_destroy(self.handle)
-
-
 def test_jitter_build():
     """a handful of the cases above on the race-stress build (-DTL_JITTER: waves leave every barrier far apart): the compaction's
     double-buffered wave counts, the LDS blocks reused within a step, the commit's second pass"""
-    lib = os.path.join(ROOT, "teeline_amd", "libteeline_gpu_jitter.so")
-    assert os.path.exists(lib), "built by __graft_entry__.build()"
-    jctx = _RawContext(lib)
+    jctx = H.jitter(PSO)
     try:
         for name in ("small8_every_condition", "synth130_every_condition"):
             xy, packed, n, init, o, _want = PC.seeded_case(name)

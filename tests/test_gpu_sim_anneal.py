@@ -9,25 +9,19 @@ import threading
 import numpy as np
 import pytest
 
+from _raw_context import _vp, jitter_context
 import _sa_cases as K
 import _sa_oracle as SA
+from _swarm_oracle import bits
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def c_opts(o):
     from teeline_amd import _capi
     return _capi.TlSaOpts(o["epochs"], o["cooling_rate"], o["min_temperature"], o["max_temperature"])
-
-
-def bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
 
 
 def gpu_trace(ctx, xy, packed, n, init, opts, seed, chain=0, cap=None):
@@ -413,39 +407,14 @@ def test_cli_equals_python_mirror(ctx):
 
 
 # ---------------------------------------------------------------- jitter build
-class _RawContext:
-    """A context of another build of the library (ctypes only: the package binds the product library)."""
-
-    def __init__(self, path):
-        from teeline_amd import _capi
-        self.lib = C.CDLL(path)
-        vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
-        self.lib.tl_create.argtypes = [C.c_int, u32, C.POINTER(vp)]
-        self.lib.tl_destroy.argtypes = [vp]
-        self.lib.tl_destroy.restype = None
-        self.lib.tl_last_error.argtypes = [vp]
-        self.lib.tl_last_error.restype = C.c_char_p
-        self.lib.tl_sim_anneal_trace_chain.argtypes = [vp, vp, u32, vp, vp, C.POINTER(_capi.TlSaOpts), u64, u32, vp, C.POINTER(C.c_float),
-                                                       C.POINTER(_capi.TlStats), vp, u32, C.POINTER(u32)]
-        self.lib.tl_sim_anneal_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, C.POINTER(_capi.TlSaOpts), u64, vp, vp, vp, C.POINTER(u32),
-                                                      C.POINTER(_capi.TlStats)]
-        self.handle = vp()
-        rc = self.lib.tl_create(0, 0, C.byref(self.handle))
-        assert rc == 0, self.lib.tl_last_error(None)
-        self.lib.tl_device_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
-        cus = C.c_int()
-        assert self.lib.tl_device_info(self.handle, C.byref(cus), None, None, 0) == 0
-        self.cus = cus.value
-
-    def close(self):
-        self.lib.tl_destroy(self.handle)
-
-
 def test_jitter_build():
     """The berlin52 traces on the race-stress build (-DTL_JITTER: waves leave every barrier far apart)."""
-    lib = os.path.join(ROOT, "teeline_amd", "libteeline_gpu_jitter.so")
-    assert os.path.exists(lib), "built by __graft_entry__.build()"
-    jctx = _RawContext(lib)
+    from teeline_amd import _capi
+    vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+    jctx = jitter_context({"tl_sim_anneal_trace_chain": [vp, vp, u32, vp, vp, C.POINTER(_capi.TlSaOpts), u64, u32, vp, C.POINTER(C.c_float), C.POINTER(_capi.TlStats), vp, u32,
+                                                         C.POINTER(u32)],
+                           "tl_sim_anneal_population": [vp, vp, u32, vp, vp, u32, u32, u32, C.POINTER(_capi.TlSaOpts), u64, vp, vp, vp, C.POINTER(u32),
+                                                        C.POINTER(_capi.TlStats)]})
     try:
         for name in ("berlin52_hot", "berlin52_cold", "small3_hot"):
             xy, packed, n, init, opts, seed = CASES[name]

@@ -12,13 +12,10 @@ import pytest
 
 import _sa_cases as K
 import _sa_oracle as SA
+from _swarm_oracle import bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = json.load(open(os.path.join(ROOT, "tests", "golden", "goldens_sa.json")))
-
-
-def bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
 
 
 @pytest.fixture(scope="module")

@@ -13,16 +13,13 @@ import pytest
 
 import _sa_cases as K
 import _sa_oracle as SA
+from _swarm_oracle import bits
 import _tabu_cases as TC
 import _tabu_oracle as TO
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = json.load(open(os.path.join(ROOT, "tests", "golden", "goldens_tabu.json")))
 CASES = TC.golden_cases()
-
-
-def bits(f):
-    return int(np.array([f], dtype=np.float32).view(np.uint32)[0])
 
 
 def log_words(log):
