@@ -46,7 +46,8 @@ extern "C" {
                             tl_two_opt_last_counters, new tl_create flags, k <= 64; later: tl_or_opt_population, tl_or_opt_lds_max_n,
                             TL_FLAG_OR_OPT_FORCE_SCAN, tl_three_opt_population and its three companions, TL_FLAG_3OPT_POP_*, tl_sim_anneal and its companions,
                             TL_FLAG_SA_NO_SPECULATION, tl_tabu_search and its companions,
-                            TL_FLAG_TABU_FULL_COMPARE) leave it — a caller built against 5 runs unchanged */
+                            TL_FLAG_TABU_FULL_COMPARE, TL_MODE_BEST_SWEEP in the 2-opt batch entries, tl_two_opt_best_population and its three
+                            companions) leave it — a caller built against 5 runs unchanged */
 
 typedef struct tl_ctx tl_ctx;
 
@@ -469,7 +470,13 @@ int tl_branch_and_bound_plan(uint32_t n, int cus, int lds_bytes, int *threads, i
  * optional) gets every restart's final cost.  Ranks shard [0,R) between themselves and min-reduce
  * tl_pack_cost_key(best_cost, best_restart) with RCCL.
  * Beyond tl_two_opt_lds_max_n (or with TL_FLAG_2OPT_FORCE_HBM) the restarts run ONE AFTER THE OTHER through the HBM form:
- * the same tours, costs and counters; stats->kernel_ms is then the sum of the descents' device times. */
+ * the same tours, costs and counters; stats->kernel_ms is then the sum of the descents' device times.
+ * mode == TL_MODE_BEST_SWEEP (coordinates, n <= 65535 as in tl_two_opt): every restart is a whole best-sweep descent in ONE workgroup
+ * with the tour, the tile metadata and the row-key cache in that CU's LDS (csrc/two_opt_best_lds.hip), no launch between sweeps;
+ * restart r's tour, cost and counters are what tl_two_opt(..., TL_MODE_BEST_SWEEP, ...) gives from the same start.  Beyond
+ * tl_two_opt_best_lds_max_n, or after tl_two_opt_best_force_scan(ctx, 1), the restarts run one after the other through that chip-wide form
+ * (kernel_ms: the sum of the descents' device times; over several devices the slowest shard's sum, as above).  stats->candidates is
+ * the sum over the descents of sweeps * (n-3)(n-2)/2.  tl_two_opt_last_counters has nothing to report after a call in this mode. */
 int tl_two_opt_multistart(tl_ctx *ctx, const float *xy, uint32_t n, uint64_t seed, uint32_t first,
                           uint32_t count, int mode, uint32_t *out_best_pos, float *out_best_cost,
                           uint32_t *out_best_restart, float *out_costs, tl_stats *stats);
@@ -499,6 +506,28 @@ uint64_t tl_pack_cost_key(float cost, uint32_t restart);
 int tl_two_opt_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed,
                           const uint32_t *init_pos, uint32_t count, uint32_t *out_pos, float *out_costs,
                           tl_stats *stats);
+/* The same for TL_MODE_BEST_SWEEP (EUC_2D coordinates, 3 <= n <= 65535): each of the `count` tours by its own best-sweep descent, one
+ * workgroup per tour with the whole state in that CU's LDS (csrc/two_opt_best_lds.hip), all concurrently.  Tour r of out_pos /
+ * out_costs / out_moves (optional, count entries: the moves that descent applied) is exactly what the single-tour entry in mode
+ * TL_MODE_BEST_SWEEP returns for init_pos + r * n alone: the route element for element, the cost bit for bit.
+ * count == 0: TL_OK, nothing written.  A row of init_pos that is not a permutation of 0..n-1: TL_ERR_BADARG, the message names the
+ * tour; nothing is launched or written.  A descent at the sweep cap: TL_ERR_NO_CONVERGE, the message names the tour.
+ * tl_two_opt_best_lds_max_n: the largest n of the LDS-resident form (0 for a NULL context) — 18 bytes per position of the padded
+ * tour (point, row key, 16-bit position) and 20 per tile of the padded tile table: 8 768 on 160 KB.  Beyond it, or
+ * after tl_two_opt_best_force_scan(ctx, 1), the tours run one after the other through the chip-wide descent: the same results;
+ * stats->kernel_ms is then the sum of the descents' device times.
+ * tl_two_opt_best_force_scan: a setting of the context (on != 0: every later best-sweep multi-start / population call of this context
+ * takes the loop at every n; for tl_two_opt_multistart_devices the setting of ctxs[0] decides; 0 restores the default) — the cross-check
+ * of the two forms.  It is a setting and not a tl_create flag because all 31 assigned flag bits are taken and bit 31 stays the one bit
+ * no flag has, which the seeded solvers refuse.  TL_ERR_BADARG for a NULL context.
+ * tl_two_opt_best_plan (host-only, no context): which form a batch of `count` descents of n cities takes on a device with `cus`
+ * compute units and lds_bytes of LDS per workgroup, with the context's force-scan setting as `force_scan` — *form 0: one workgroup per
+ * descent, *threads wide; *form 1: the loop over the chip-wide descent (*threads 0).  TL_ERR_BADARG on a NULL output. */
+uint32_t tl_two_opt_best_lds_max_n(const tl_ctx *ctx);
+int tl_two_opt_best_plan(uint32_t n, uint32_t count, int cus, int lds_bytes, int force_scan, int *form, int *threads);
+int tl_two_opt_best_force_scan(tl_ctx *ctx, int on);
+int tl_two_opt_best_population(tl_ctx *ctx, const float *xy, uint32_t n, const uint32_t *init_pos, uint32_t count, uint32_t *out_pos,
+                               float *out_costs, uint32_t *out_moves, tl_stats *stats);
 
 /* Or-opt over a population of `count` explicit tours (init_pos: count x n positions), each by its own or_opt::solve descent
  * (or_opt.rs:18-74), one workgroup per tour with the tour in that CU's LDS (csrc/or_opt_lds.hip), all concurrently.  Tour r of
@@ -1309,7 +1338,9 @@ uint64_t tl_one_tree_bound_work_bytes(uint32_t n, uint32_t jobs, uint32_t log_ca
  * on the device for the previous call's descents on stream A before it rebuilds them (no host synchronisation).
  * Asynchronous: returns after enqueueing — except that a batch with more descents than the device has CUs at 7 100 < n <= 10 240
  * first asks the device whether the coordinates lie on a decimal grid (then two descents share a CU): one 4-byte read-back,
- * i.e. a synchronisation of `stream`, before the descents are enqueued. */
+ * i.e. a synchronisation of `stream`, before the descents are enqueued.
+ * mode == TL_MODE_BEST_SWEEP: one LDS-resident best-sweep descent per workgroup (csrc/two_opt_best_lds.hip); stats words 0-3 as above,
+ * the rest 0; n beyond tl_two_opt_best_lds_max_n or 65535: TL_ERR_UNSUPPORTED (this entry has no loop form). */
 int tl_two_opt_batch_dev(tl_ctx *ctx, const float *d_xy, uint32_t n, const uint32_t *d_init,
                          uint64_t seed, uint32_t first, uint32_t count, int mode, uint32_t *d_out_pos,
                          float *d_out_cost, uint64_t *d_out_stats, void *stream);

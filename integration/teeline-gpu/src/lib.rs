@@ -225,6 +225,11 @@ unsafe extern "C" {
     fn tl_or_opt_lds_max_n(ctx: *const TlCtx) -> u32;
     fn tl_or_opt_population(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, count: u32,
                             out_pos: *mut u32, out_costs: *mut f32, out_moves: *mut u32, stats: *mut Stats) -> c_int;
+    fn tl_two_opt_best_lds_max_n(ctx: *const TlCtx) -> u32;
+    fn tl_two_opt_best_plan(n: u32, count: u32, cus: c_int, lds_bytes: c_int, force_scan: c_int, form: *mut c_int, threads: *mut c_int) -> c_int;
+    fn tl_two_opt_best_force_scan(ctx: *mut TlCtx, on: c_int) -> c_int;
+    fn tl_two_opt_best_population(ctx: *mut TlCtx, xy: *const f32, n: u32, init_pos: *const u32, count: u32, out_pos: *mut u32,
+                                  out_costs: *mut f32, out_moves: *mut u32, stats: *mut Stats) -> c_int;
     fn tl_three_opt_pop_max_n(ctx: *const TlCtx) -> u32;
     fn tl_three_opt_population_plan(n: u32, count: u32, cus: c_int, lds_bytes: c_int, work_bytes: u64, flags: u32, form: *mut c_int,
                                     threads: *mut c_int, batch: *mut u32) -> c_int;
@@ -1232,6 +1237,45 @@ impl Context {
             .collect())
     }
 
+    /// Largest n whose best-sweep descent fits one CU's LDS (`tl_two_opt_best_lds_max_n`): beyond it a batch runs descent after descent.
+    pub fn two_opt_best_lds_max_n(&self) -> u32 {
+        // SAFETY: a plain query of a live context.
+        unsafe { tl_two_opt_best_lds_max_n(self.raw) }
+    }
+
+    /// Best-sweep batches of this context loop over `two_opt`'s chip-wide descent at every n (`tl_two_opt_best_force_scan`): the
+    /// cross-check of the two forms.
+    pub fn two_opt_best_force_scan(&self, on: bool) -> Result<(), Error> {
+        // SAFETY: a setting of a live context.
+        self.check(unsafe { tl_two_opt_best_force_scan(self.raw, on as c_int) })
+    }
+
+    /// Best-sweep 2-opt over a population (coordinates only): `init_pos` holds `count` tours of n positions back to back, each refined
+    /// by its own `TL_MODE_BEST_SWEEP` descent, all concurrently (`tl_two_opt_best_population`).  Tour k of the result is what `two_opt`
+    /// in that mode returns for it alone; its `stats` are the call's (sums over the population) with `moves` replaced by that tour's own.
+    pub fn two_opt_best_population(&self, xy: &[f32], init_pos: &[u32]) -> Result<Vec<Tour>, Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, None, None);
+        if n == 0 {
+            return Ok(Vec::new());
+        }
+        assert!(init_pos.len() % n as usize == 0, "init_pos holds whole tours of n positions");
+        let count = init_pos.len() / n as usize;
+        let mut pos = vec![0u32; init_pos.len()];
+        let mut costs = vec![0f32; count];
+        let mut moves = vec![0u32; count];
+        let mut stats = Stats::default();
+        // SAFETY: as in two_opt; every output buffer holds count (x n) entries.
+        let rc = unsafe {
+            tl_two_opt_best_population(self.raw, xy.as_ptr(), n, init_pos.as_ptr(), count as u32, pos.as_mut_ptr(), costs.as_mut_ptr(),
+                                       moves.as_mut_ptr(), &mut stats)
+        };
+        self.check(rc)?;
+        Ok((0..count)
+            .map(|k| Tour { pos: pos[k * n as usize..(k + 1) * n as usize].to_vec(), cost: costs[k], stats: Stats { moves: moves[k] as u64, ..stats } })
+            .collect())
+    }
+
     /// Largest n of the per-workgroup form of `three_opt_population` (either input form).
     pub fn three_opt_pop_max_n(&self) -> u32 {
         // SAFETY: a plain query of a live context.
@@ -1363,6 +1407,15 @@ pub fn three_opt_population_plan(n: u32, count: u32, cus: i32, lds_bytes: i32, w
     // SAFETY: the three outputs are live locals.
     let rc = unsafe { tl_three_opt_population_plan(n, count, cus, lds_bytes, work_bytes, flags, &mut form, &mut threads, &mut batch) };
     if rc == 0 { Some((form, threads, batch)) } else { None }
+}
+
+/// The rule the best-sweep batch entries follow (`tl_two_opt_best_plan`; pure, no device): `(form, threads)` — form 0: one workgroup
+/// of `threads` per descent, form 1: the loop over the chip-wide descent; `None` for a device that is none.
+pub fn two_opt_best_plan(n: u32, count: u32, cus: i32, lds_bytes: i32, force_scan: bool) -> Option<(i32, i32)> {
+    let (mut form, mut threads) = (0 as c_int, 0 as c_int);
+    // SAFETY: the two outputs are live locals.
+    let rc = unsafe { tl_two_opt_best_plan(n, count, cus, lds_bytes, force_scan as c_int, &mut form, &mut threads) };
+    if rc == 0 { Some((form, threads)) } else { None }
 }
 
 /// `tl_create` flag: `three_opt_population` runs its tours one after the other through `three_opt`'s chip-wide descent.

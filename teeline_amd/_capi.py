@@ -57,6 +57,7 @@ SYMBOLS = [
     "tl_lk_live", "tl_two_opt_neighbour_lists", "tl_two_opt_plan", "tl_multistart_shard", "tl_two_opt_last_counters",
     "tl_greedy_edge", "tl_savings_hub", "tl_savings", "tl_christofides", "tl_bellman_karp",
     "tl_or_opt_population", "tl_or_opt_lds_max_n",
+    "tl_two_opt_best_population", "tl_two_opt_best_lds_max_n", "tl_two_opt_best_plan", "tl_two_opt_best_force_scan",
     "tl_three_opt_population", "tl_three_opt_pop_max_n", "tl_three_opt_population_plan", "tl_three_opt_population_work_limit",
     "tl_sim_anneal", "tl_sim_anneal_trace", "tl_sim_anneal_trace_chain", "tl_sim_anneal_population", "tl_sim_anneal_lds_max_n", "tl_sim_anneal_plan",
     "tl_sa_draw", "tl_sa_schedule_epochs", "tl_sa_selftest_accept",
@@ -255,6 +256,11 @@ def load():
     L.tl_or_opt_lds_max_n.argtypes = [vp]
     L.tl_or_opt_lds_max_n.restype = u32
     L.tl_or_opt_population.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, C.POINTER(TlStats)]
+    L.tl_two_opt_best_lds_max_n.argtypes = [vp]
+    L.tl_two_opt_best_lds_max_n.restype = u32
+    L.tl_two_opt_best_plan.argtypes = [u32, u32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+    L.tl_two_opt_best_force_scan.argtypes = [vp, i32]
+    L.tl_two_opt_best_population.argtypes = [vp, vp, u32, vp, u32, vp, vp, vp, C.POINTER(TlStats)]
     L.tl_three_opt_pop_max_n.argtypes = [vp]
     L.tl_three_opt_pop_max_n.restype = u32
     L.tl_three_opt_population.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, C.POINTER(TlStats)]

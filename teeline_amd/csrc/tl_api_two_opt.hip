@@ -29,14 +29,70 @@ static_assert((TL_DM_LONG_MAX) <= tl::kDmLongCap, "TL_DM_LONG_MAX exceeds TL_DM_
 // ------------------------------------------------------------------------------------------------
 // 2-opt
 // ------------------------------------------------------------------------------------------------
+// TL_MODE_BEST_SWEEP for a batch: one LDS-resident descent per workgroup (two_opt_best_lds.hip).  The refusals carry the single-tour
+// form's messages; beyond the LDS the host-buffer entries loop over the chip-wide form instead (best_runs_loop) and never get here.
+static const char *const kBestNeedsXy = "TL_MODE_BEST_SWEEP needs EUC_2D coordinates (dm_packed must be NULL)";
+static const char *const kBestKeyLimit = "TL_MODE_BEST_SWEEP: n=%u > 65535 (packed (i,j) key)";
+static int best_lds_enqueue(tl_ctx *c, const float2 *d_xy, const float *d_dm, uint32_t n, const uint32_t *d_init, uint32_t init_mode, uint64_t seed,
+                            uint32_t first, uint32_t count, uint32_t *d_out_pos, float *d_out_cost, uint64_t *d_out_stats, hipStream_t s)
+{
+    if (d_dm || !d_xy) return fail(c, TL_ERR_UNSUPPORTED, kBestNeedsXy);
+    if (n > 65535) return fail(c, TL_ERR_UNSUPPORTED, kBestKeyLimit, n);
+    if (n > two_opt_best_lds_max_n(c->lds_bytes))
+        return fail(c, TL_ERR_UNSUPPORTED, "two_opt (BEST_SWEEP batch): n=%u exceeds the LDS-resident limit %u", n, two_opt_best_lds_max_n(c->lds_bytes));
+    if (init_mode != TL_INIT_ARRAY && init_mode != TL_INIT_SEEDED) return fail(c, TL_ERR_BADARG, "two_opt (BEST_SWEEP batch): no start tours");
+    BestLdsArgs A{};
+    A.xy = d_xy;
+    A.init = d_init;
+    A.out_pos = d_out_pos;
+    A.out_cost = d_out_cost;
+    A.out_stats = d_out_stats;
+    A.seed = seed;
+    A.first = first;
+    A.n = n;
+    A.max_sweeps = TL_MAX_SWEEPS;
+    A.init_mode = init_mode;
+    c->ev_valid = false;
+    c->stats_valid = false;  // (status and counters only: nothing for tl_two_opt_last_counters, as in the single-tour form)
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, launch_two_opt_best_lds(A, count, two_opt_best_lds_threads(n, count, c->cus, c->lds_bytes), s));
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    c->ev_valid = true;
+    return TL_OK;
+}
+
+// does a host-buffer batch entry run its BEST_SWEEP descents one after the other through the chip-wide form (two_opt_best.hip)?
+static bool best_runs_loop(const tl_ctx *c, uint32_t n) { return n > two_opt_best_lds_max_n(c->lds_bytes) || c->two_opt_best_force_scan; }
+
+extern "C" int tl_two_opt_best_force_scan(tl_ctx *c, int on)
+{
+    TL_ENTER(c);
+    if (!c) return fail(c, TL_ERR_BADARG, "tl_two_opt_best_force_scan: NULL context");
+    c->two_opt_best_force_scan = on != 0;
+    return TL_OK;
+}
+
+extern "C" uint32_t tl_two_opt_best_lds_max_n(const tl_ctx *c) { return c ? two_opt_best_lds_max_n(c->lds_bytes) : 0u; }
+
+// Measured on one MI355X (256 CUs), scripts/timing_best_sweep_batch.py, profiles/best_sweep_batch_timing.jsonl; NOTEBOOK.md,
+// "Best-sweep 2-opt for batches": the per-workgroup form is the faster one at every size timed, so it runs wherever a descent fits.
+extern "C" int tl_two_opt_best_plan(uint32_t n, uint32_t count, int cus, int lds_bytes, int force_scan, int *form, int *threads)
+{
+    if (!form || !threads || cus <= 0 || lds_bytes <= 0) return TL_ERR_BADARG;
+    *form = (n < 3 || n > two_opt_best_lds_max_n(lds_bytes) || force_scan) ? 1 : 0;
+    *threads = *form ? 0 : two_opt_best_lds_threads(n, count ? count : 1u, cus, lds_bytes);
+    return TL_OK;
+}
+
 static int two_opt_enqueue(tl_ctx *c, const float2 *d_xy, const float *d_dm, uint32_t n, const uint32_t *d_init,
                            uint32_t init_mode, uint64_t seed, uint32_t first, uint32_t count, int mode,
                            uint32_t *d_out_pos, float *d_out_cost, uint64_t *d_out_stats, hipStream_t s,
                            uint32_t *d_move_log = nullptr, uint32_t log_cap = 0)
 {
-    if (mode != TL_MODE_REF_ORDER) return fail(c, TL_ERR_UNSUPPORTED, "batch 2-opt supports TL_MODE_REF_ORDER only");
+    if (mode != TL_MODE_REF_ORDER && mode != TL_MODE_BEST_SWEEP) return fail(c, TL_ERR_UNSUPPORTED, "batch 2-opt: unknown mode %d", mode);
     if (n < 3) return fail(c, TL_ERR_REF_PANICS, "two_opt: n=%u < 3 — the reference underflows `n_indices - 2` (two_opt.rs:17,29)", n);
     if (count == 0) return TL_OK;
+    if (mode == TL_MODE_BEST_SWEEP) return best_lds_enqueue(c, d_xy, d_dm, n, d_init, init_mode, seed, first, count, d_out_pos, d_out_cost, d_out_stats, s);
     TwoOptBatchArgs A{};
     A.xy = d_xy;
     A.dm = d_dm;
@@ -582,13 +638,16 @@ extern "C" int tl_two_opt_multistart_devices(tl_ctx *const *ctxs, int n_ctxs, co
     std::vector<Shard> shard((size_t)n_ctxs);
     for (int d = 0; d < n_ctxs; ++d) (void)tl_multistart_shard(first, count, n_ctxs, d, &shard[d].first, &shard[d].count);
     int rc;
-    if (batch_runs_hbm_form(c0, n)) {
+    const bool best_mode = mode == TL_MODE_BEST_SWEEP;
+    if (best_mode && n > 65535) return fail(c0, TL_ERR_UNSUPPORTED, kBestKeyLimit, n);
+    if (best_mode ? best_runs_loop(c0, n) : batch_runs_hbm_form(c0, n)) {
         // beyond the LDS-resident descent, or TL_FLAG_2OPT_FORCE_HBM on ctxs[0]: the restarts one after the other
         // through the HBM form, each shard on its own context — the same start permutations, so the same tours as a (hypothetical) batch
         // would give.  The shards, too, run one after the other (two_opt_ref_large polls its descent on the calling thread): kernel_ms is
         // the largest of the shards' summed device times — the slowest shard's, what devices side by side would wait for — and
         // total_ms is the sum of all of them.
-        if (mode != TL_MODE_REF_ORDER) return fail(c0, TL_ERR_UNSUPPORTED, "batch 2-opt supports TL_MODE_REF_ORDER only");
+        // TL_MODE_BEST_SWEEP beyond tl_two_opt_best_lds_max_n, or tl_two_opt_best_force_scan on ctxs[0]: the same loop over the chip-wide best-sweep descent.
+        if (mode != TL_MODE_REF_ORDER && !best_mode) return fail(c0, TL_ERR_UNSUPPORTED, "batch 2-opt: unknown mode %d", mode);
         std::vector<uint32_t> perm, pos(n), bestpos(n);
         uint64_t bestkey = ~0ull;
         tl_stats acc{};
@@ -596,12 +655,14 @@ extern "C" int tl_two_opt_multistart_devices(tl_ctx *const *ctxs, int n_ctxs, co
         for (int d = 0; d < n_ctxs; ++d) {
             if (!shard[d].count) continue;
             double shard_ms = 0;
-            rc = hbm_upload_xy(ctxs[d], xy, n);
+            rc = best_mode ? TL_OK : hbm_upload_xy(ctxs[d], xy, n);  // (two_opt_best_sweep uploads the instance itself)
             for (uint32_t r = shard[d].first; rc == TL_OK && r < shard[d].first + shard[d].count; ++r) {
                 restart_perm_host(n, seed, r, perm);
                 float cst = 0.f;
                 tl_stats st1{};
-                if ((rc = two_opt_ref_large(ctxs[d], nullptr, n, perm.data(), pos.data(), &cst, &st1))) break;
+                if ((rc = best_mode ? two_opt_best_sweep(ctxs[d], xy, n, nullptr, perm.data(), pos.data(), &cst, &st1)
+                                    : two_opt_ref_large(ctxs[d], nullptr, n, perm.data(), pos.data(), &cst, &st1)))
+                    break;
                 costs[r - first] = cst;
                 add_counters(acc, st1);
                 shard_ms += st1.kernel_ms;
@@ -638,6 +699,7 @@ extern "C" int tl_two_opt_multistart_devices(tl_ctx *const *ctxs, int n_ctxs, co
         ShardBest b;
         if ((rc = multistart_finish(ctxs[d], shard[d].first, shard[d].count, costs.data() + off, raw.data() + (size_t)off * TL_STATS_STRIDE, b)))
             return shard_fail(ctxs, d, rc);
+        if (best_mode) ctxs[d]->stats_valid = false;  // (no kernel-side counters in this mode: tl_two_opt_last_counters keeps refusing)
         if (b.key < best.key) {
             best = b;
             best_dev = d;
@@ -772,14 +834,79 @@ extern "C" int tl_two_opt_population(tl_ctx *c, const float *xy, uint32_t n, con
     return TL_OK;
 }
 
+// A population of explicit tours, each refined by its own BEST_SWEEP descent: tour r's result is tl_two_opt(..., TL_MODE_BEST_SWEEP, ...)'s
+// for row r alone.  One workgroup per tour (two_opt_best_lds.hip) wherever a descent fits the LDS; beyond it, or with
+// after tl_two_opt_best_force_scan, the tours one after the other through the chip-wide form (kernel_ms: the sum of the descents' device times).
+extern "C" int tl_two_opt_best_population(tl_ctx *c, const float *xy, uint32_t n, const uint32_t *init_pos, uint32_t count, uint32_t *out_pos,
+                                          float *out_costs, uint32_t *out_moves, tl_stats *stats)
+{
+    TL_ENTER(c);
+    if (!c || !xy) return fail(c, TL_ERR_BADARG, "tl_two_opt_best_population: NULL argument");
+    if (count == 0) return TL_OK;
+    if (!init_pos || !out_pos) return fail(c, TL_ERR_BADARG, "tl_two_opt_best_population: NULL argument");
+    if (n < 3) return fail(c, TL_ERR_REF_PANICS, "two_opt: n=%u < 3", n);
+    if (n > 65535) return fail(c, TL_ERR_UNSUPPORTED, kBestKeyLimit, n);
+    for (uint32_t r = 0; r < count; ++r)
+        if (!is_permutation(init_pos + (size_t)r * n, n))
+            return fail(c, TL_ERR_BADARG, "tl_two_opt_best_population: tour %u is not a permutation of 0..n-1", r);
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if (best_runs_loop(c, n)) {
+        tl_stats acc{};
+        for (uint32_t r = 0; r < count; ++r) {
+            float cst = 0.f;
+            tl_stats st1{};
+            rc = two_opt_best_sweep(c, xy, n, nullptr, init_pos + (size_t)r * n, out_pos + (size_t)r * n, &cst, &st1);
+            if (rc == TL_ERR_NO_CONVERGE) return fail(c, rc, "two_opt (BEST_SWEEP): sweep cap reached in tour %u", r);
+            if (rc) return rc;
+            if (out_costs) out_costs[r] = cst;
+            if (out_moves) out_moves[r] = (uint32_t)st1.moves;
+            add_counters(acc, st1);
+            acc.kernel_ms += st1.kernel_ms;
+        }
+        if (stats) {
+            *stats = acc;
+            stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return TL_OK;
+    }
+    const size_t words = (size_t)count * n;
+    if ((rc = ensure(c, c->init, words * 4)) || (rc = ensure(c, c->out_pos, words * 4)) || (rc = ensure(c, c->out_cost, (size_t)count * 4)) ||
+        (rc = ensure(c, c->out_stats, (size_t)count * TL_STATS_STRIDE * 8)))
+        return rc;
+    const float2 *dxy = nullptr;
+    if ((rc = upload_xy(c, xy, n, &dxy))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->init.p, init_pos, words * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = two_opt_enqueue(c, dxy, nullptr, n, (const uint32_t *)c->init.p, TL_INIT_ARRAY, 0, 0, count, TL_MODE_BEST_SWEEP, (uint32_t *)c->out_pos.p,
+                              (float *)c->out_cost.p, (uint64_t *)c->out_stats.p, c->stream)))
+        return rc;
+    std::vector<uint64_t> raw((size_t)count * TL_STATS_STRIDE);
+    std::vector<float> costs(count);
+    HIPCHK(c, hipMemcpyAsync(costs.data(), c->out_cost.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(raw.data(), c->out_stats.p, (size_t)count * TL_STATS_STRIDE * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t r = 0; r < count; ++r)
+        if (raw[TL_STATS_STRIDE * r + 3] != 0) return fail(c, TL_ERR_NO_CONVERGE, "two_opt (BEST_SWEEP): sweep cap reached in tour %u", r);
+    HIPCHK(c, hipMemcpyAsync(out_pos, c->out_pos.p, words * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t r = 0; r < count; ++r) {
+        if (out_costs) out_costs[r] = costs[r];
+        if (out_moves) out_moves[r] = (uint32_t)raw[TL_STATS_STRIDE * r + 1];
+    }
+    fill_stats(stats, n, raw.data(), count);
+    stamp_times(c, stats, t0);
+    return TL_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // 2-opt, TL_MODE_BEST_SWEEP (this build's own mode; specification: oracle tlo_two_opt_best)
 // ------------------------------------------------------------------------------------------------
 static int two_opt_best_sweep(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos,
                               uint32_t *out_pos, float *out_cost, tl_stats *stats)
 {
-    if (dm_packed || !xy) return fail(c, TL_ERR_UNSUPPORTED, "TL_MODE_BEST_SWEEP needs EUC_2D coordinates (dm_packed must be NULL)");
-    if (n > 65535) return fail(c, TL_ERR_UNSUPPORTED, "TL_MODE_BEST_SWEEP: n=%u > 65535 (packed (i,j) key)", n);
+    if (dm_packed || !xy) return fail(c, TL_ERR_UNSUPPORTED, kBestNeedsXy);
+    if (n > 65535) return fail(c, TL_ERR_UNSUPPORTED, kBestKeyLimit, n);
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(c, hipSetDevice(c->device));
     c->stats_valid = false;  // (this form keeps its counters in the workspace: nothing for tl_two_opt_last_counters)

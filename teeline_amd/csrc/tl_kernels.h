@@ -149,6 +149,24 @@ hipError_t launch_best_sweep_init(const BestSweepArgs &A, hipStream_t s);
 hipError_t launch_best_sweep_round(const BestSweepArgs &A, hipStream_t s);
 uint32_t best_sweep_scan_blocks(uint32_t n);
 
+// two_opt_best_lds.hip — BEST_SWEEP for a batch: one workgroup per descent, the whole state in its LDS
+struct BestLdsArgs {
+    const float2 *xy;      // n cities, city order
+    const uint32_t *init;  // [count][n] when init_mode == TL_INIT_ARRAY
+    uint32_t *out_pos;     // [count][n]
+    float *out_cost;       // [count]
+    uint64_t *out_stats;   // [count][TL_STATS_STRIDE] = sweeps, moves, reversed, status (0 ok, 1 sweep cap, 2 init position >= n), 0 ...
+    uint64_t seed;
+    uint32_t first;        // restart index of descent 0 (TL_INIT_SEEDED)
+    uint32_t n;
+    uint32_t max_sweeps;
+    uint32_t init_mode;    // TL_INIT_ARRAY or TL_INIT_SEEDED
+};
+size_t two_opt_best_lds_bytes(uint32_t n);            // LDS of one descent's workgroup
+uint32_t two_opt_best_lds_max_n(int lds_budget);      // largest n whose state fits (0: none)
+int two_opt_best_lds_threads(uint32_t n, uint32_t count, int cus, int lds_budget);
+hipError_t launch_two_opt_best_lds(const BestLdsArgs &A, uint32_t count, int threads, hipStream_t s);
+
 // two_opt_large.hip — REF_ORDER for tours beyond one CU's LDS
 struct LargeTwoOptState {
     unsigned long long key;  // (row << 32) | column of the lexicographically first improving candidate of the round; ~0 = none

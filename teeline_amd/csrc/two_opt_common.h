@@ -36,6 +36,27 @@ __device__ __forceinline__ void pt_put(const PtsFx &P, uint32_t k, PtsFx::Raw r)
     P.hi[k] = (uint8_t)r.hi;
 }
 
+// ---- the seeded start tour of a restart (oracle tlo_restart_perm), over the identity in perm:
+// Fisher-Yates `for i in (1..n).rev(): j = rng % (i+1); swap` from splitmix64(s), s = seed + restart:
+// the draws are counter-based, so compute them in parallel, then one lane applies the swaps.
+// draws: n 16-bit words of LDS that nothing else uses yet.  The caller's next barrier publishes the tour.
+__device__ __forceinline__ void seeded_start_perm(uint16_t *perm, uint16_t *draws, uint32_t n, uint64_t s, uint32_t tid, uint32_t nt)
+{
+    for (uint32_t i = 1 + tid; i < n; i += nt) {
+        const uint64_t kth = (uint64_t)(n - 1 - i);  // i = n-1 is draw 0
+        draws[i] = (uint16_t)(splitmix64_at(s, kth) % ((uint64_t)i + 1));
+    }
+    TL_SYNC();
+    if (tid == 0) {
+        for (uint32_t i = n - 1; i >= 1; --i) {
+            const uint32_t j = draws[i];
+            const uint16_t t = perm[i];
+            perm[i] = perm[j];
+            perm[j] = t;
+        }
+    }
+}
+
 // ---- whole-wave maximum of u32 keys in 6 DPP steps, result in lane 63 (no LDS, no readlane): row_shr 1, 2, 4, 8 leave each row's
 // maximum in its lane 15 (max is idempotent, so the overlapping windows do no harm), row_bcast15 / row_bcast31 carry it on to the
 // rows above.  Lanes without a DPP source read 0, the identity of an unsigned maximum.

@@ -846,23 +846,8 @@ __global__ __launch_bounds__(NT, 4) void k_two_opt_ref_lds(TwoOptBatchArgs A)
         for (uint32_t k = tid; k < n; k += NT) perm[k] = (uint16_t)k;  // two_opt.rs:18-20
     }
     if (A.init_mode == TL_INIT_SEEDED) {
-        // Fisher-Yates `for i in (1..n).rev(): j = rng % (i+1); swap` from splitmix64(seed + r):
-        // the draws are counter-based, so compute them in parallel, then one lane applies the swaps.
-        uint16_t *draws = reinterpret_cast<uint16_t *>(smem);  // the points are not live yet
-        const uint64_t s = A.seed + (uint64_t)(A.first + d);
-        for (uint32_t i = 1 + tid; i < n; i += NT) {
-            const uint64_t kth = (uint64_t)(n - 1 - i);  // i = n-1 is draw 0
-            draws[i] = (uint16_t)(splitmix64_at(s, kth) % ((uint64_t)i + 1));
-        }
-        TL_SYNC();
-        if (tid == 0) {
-            for (uint32_t i = n - 1; i >= 1; --i) {
-                const uint32_t j = draws[i];
-                const uint16_t t = perm[i];
-                perm[i] = perm[j];
-                perm[j] = t;
-            }
-        }
+        // (the draws go where the points will be: they are not live yet)
+        seeded_start_perm(perm, reinterpret_cast<uint16_t *>(smem), n, A.seed + (uint64_t)(A.first + d), (uint32_t)tid, (uint32_t)NT);
     }
     if (tid < 4) ctl->kr[tid] = make_uint2(kNoKey, 0u);
     if (tid < 6) ctl->cnt[tid] = 0ull;

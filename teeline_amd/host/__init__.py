@@ -73,6 +73,14 @@ class Context:
     def or_opt_lds_max_n(self):
         return int(self._lib.tl_or_opt_lds_max_n(self._h))
 
+    def two_opt_best_lds_max_n(self):
+        return int(self._lib.tl_two_opt_best_lds_max_n(self._h))
+
+    def two_opt_best_force_scan(self, on=True):
+        """tl_two_opt_best_force_scan: best-sweep multi-start / population calls of this context loop over the chip-wide descent at
+        every n (the cross-check of the two forms); on=False restores the default."""
+        self.check(self._lib.tl_two_opt_best_force_scan(self._h, 1 if on else 0))
+
     def three_opt_pop_max_n(self):
         return int(self._lib.tl_three_opt_pop_max_n(self._h))
 

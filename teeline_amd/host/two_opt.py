@@ -96,7 +96,11 @@ def replay_progress(problem, start_pos, move_log, sweeps, progress_tx):
 
 def multistart(problem, restarts, seed=0, first=0, *, ctx=None, mode=_capi.TL_MODE_REF_ORDER, return_costs=False):
     """Multi-start 2-opt (north-star config 4; no counterpart in the reference): restarts
-    [first, first+restarts) from seeded Fisher–Yates permutations, one descent per CU."""
+    [first, first+restarts) from seeded Fisher–Yates permutations, one descent per CU.
+
+    mode=TL_MODE_BEST_SWEEP: every restart is a whole best-sweep descent in one workgroup with its state in that CU's LDS (beyond
+    ctx.two_opt_best_lds_max_n(), or after ctx.two_opt_best_force_scan(), restart after restart through the chip-wide form:
+    the same results)."""
     from . import Solution, default_context
     ctx = ctx or default_context()
     n = len(problem)
@@ -115,7 +119,8 @@ def multistart(problem, restarts, seed=0, first=0, *, ctx=None, mode=_capi.TL_MO
 
 def multistart_devices(problem, restarts, contexts, seed=0, first=0, *, mode=_capi.TL_MODE_REF_ORDER, return_costs=False):
     """tl_two_opt_multistart_devices: the same multi-start job dealt over several contexts (one per GPU of the node) from
-    one process; the result does not depend on how many contexts share the restarts."""
+    one process; the result does not depend on how many contexts share the restarts.  mode as in multistart (the force-scan setting of
+    contexts[0] decides the form)."""
     from . import Solution
     n = len(problem)
     out = np.empty(n, dtype=np.uint32)
@@ -133,10 +138,18 @@ def multistart_devices(problem, restarts, contexts, seed=0, first=0, *, mode=_ca
     return (sol, costs) if return_costs else sol
 
 
-def solve_population(problem, init_tours, *, ctx=None):
+def solve_population(problem, init_tours, *, ctx=None, mode=_capi.TL_MODE_REF_ORDER):
     """Refine a population of tours (lists of city ids), each by its own two_opt::solve descent, all concurrently
-    (tl_two_opt_population).  Returns one Solution per tour; Solution k equals solve(problem, None, None, init_tours[k])."""
+    (tl_two_opt_population).  Returns one Solution per tour; Solution k equals solve(problem, None, None, init_tours[k]).
+
+    mode=TL_MODE_BEST_SWEEP: each tour by its own best-sweep descent (tl_two_opt_best_population, coordinates only); Solution k
+    equals solve(problem, None, None, init_tours[k], mode=TL_MODE_BEST_SWEEP), and its stats are the call's (sums over the
+    population) with `moves` replaced by that tour's own."""
     from . import Solution, default_context
+    if mode == _capi.TL_MODE_BEST_SWEEP:
+        return _solve_population_best(problem, init_tours, ctx)
+    if mode != _capi.TL_MODE_REF_ORDER:
+        raise _capi.TeelineGpuError(_capi.TL_ERR_BADARG, f"two_opt.solve_population: bad mode {mode}")
     ctx = ctx or default_context()
     n = len(problem)
     count = len(init_tours)
@@ -153,3 +166,27 @@ def solve_population(problem, init_tours, *, ctx=None):
                                             costs.ctypes.data_as(C.c_void_p), C.byref(st)))
     stats = st.as_dict()
     return [Solution(float(costs[k]), problem.ids[out[k]], problem, stats) for k in range(count)]
+
+
+def _solve_population_best(problem, init_tours, ctx):
+    from . import Solution, default_context
+    n = len(problem)
+    count = len(init_tours)
+    for k, tour in enumerate(init_tours):  # the library reads count x n u32 values: checked before any pointer is taken
+        if len(tour) != n:
+            raise _capi.TeelineGpuError(_capi.TL_ERR_BADARG, f"tour {k} has {len(tour)} cities, the problem {n}")
+    if problem.explicit_packed() is not None:
+        raise _capi.TeelineGpuError(_capi.TL_ERR_UNSUPPORTED, "TL_MODE_BEST_SWEEP needs EUC_2D coordinates")
+    ctx = ctx or default_context()
+    init = np.empty((count, n), dtype=np.uint32)
+    for k, tour in enumerate(init_tours):
+        init[k] = problem.positions_of(tour)
+    out = np.empty((count, n), dtype=np.uint32)
+    costs = np.empty(count, dtype=np.float32)
+    moves = np.zeros(count, dtype=np.uint32)
+    st = _capi.TlStats()
+    ctx.check(ctx.lib.tl_two_opt_best_population(ctx.handle, problem.xy.ctypes.data_as(C.c_void_p), n, init.ctypes.data_as(C.c_void_p), count,
+                                                 out.ctypes.data_as(C.c_void_p), costs.ctypes.data_as(C.c_void_p),
+                                                 moves.ctypes.data_as(C.c_void_p), C.byref(st)))
+    stats = st.as_dict()
+    return [Solution(float(costs[k]), problem.ids[out[k]], problem, dict(stats, moves=int(moves[k]))) for k in range(count)]

@@ -417,14 +417,33 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const HeuristicOp
     return detail::finish(problem, c.out, c.cost, c.st, progress_tx);
 }
 
-// A population of tours, each refined by its own descent, all concurrently (tl_two_opt_population);
-// element k equals solve(ctx, problem, {}, nullptr, &init_tours[k]).
-inline std::vector<Solution> solve_population(Context &ctx, const TspProblem &problem, const std::vector<std::vector<size_t>> &init_tours)
+// A population of tours, each refined by its own descent, all concurrently (tl_two_opt_population; mode TL_MODE_BEST_SWEEP:
+// tl_two_opt_best_population, coordinates only); element k equals solve(ctx, problem, {}, nullptr, &init_tours[k], mode).
+// moves (optional, best-sweep only): the moves each descent applied.
+inline std::vector<Solution> solve_population(Context &ctx, const TspProblem &problem, const std::vector<std::vector<size_t>> &init_tours,
+                                              int mode = TL_MODE_REF_ORDER, std::vector<uint32_t> *moves = nullptr)
 {
-    return detail::solve_population(problem, init_tours, nullptr,
-                                    [&](const detail::Call &c, const uint32_t *init, uint32_t count, uint32_t *out, float *costs, uint32_t *, tl_stats *st) {
-                                        ctx.check(tl_two_opt_population(ctx.get(), c.xy.data(), c.n, c.packed, init, count, out, costs, st));
+    return detail::solve_population(problem, init_tours, mode == TL_MODE_BEST_SWEEP ? moves : nullptr,
+                                    [&](const detail::Call &c, const uint32_t *init, uint32_t count, uint32_t *out, float *costs, uint32_t *mv, tl_stats *st) {
+                                        if (mode == TL_MODE_BEST_SWEEP) {
+                                            if (c.packed) throw std::runtime_error("TL_MODE_BEST_SWEEP needs EUC_2D coordinates");
+                                            ctx.check(tl_two_opt_best_population(ctx.get(), c.xy.data(), c.n, init, count, out, costs, mv, st));
+                                        } else {
+                                            ctx.check(tl_two_opt_population(ctx.get(), c.xy.data(), c.n, c.packed, init, count, out, costs, st));
+                                        }
                                     });
+}
+
+// Multi-start 2-opt (tl_two_opt_multistart; no counterpart in the reference): restarts [first, first + restarts) from seeded
+// Fisher-Yates permutations, all at once; the best tour, *best_restart (optional) the restart it came from.
+inline Solution multistart(Context &ctx, const TspProblem &problem, uint32_t restarts, uint64_t seed = 0, uint32_t first = 0, int mode = TL_MODE_REF_ORDER,
+                           uint32_t *best_restart = nullptr)
+{
+    detail::Call c(problem, nullptr);
+    uint32_t br = 0;
+    ctx.check(tl_two_opt_multistart(ctx.get(), c.xy.data(), c.n, seed, first, restarts, mode, c.out.data(), &c.cost, &br, nullptr, &c.st));
+    if (best_restart) *best_restart = br;
+    return detail::finish(problem, c.out, c.cost, c.st, nullptr);
 }
 }  // namespace two_opt
 
@@ -1507,6 +1526,7 @@ struct StageOptions {
     HeuristicOptions heuristic;
     LKOptions lk;
     int two_opt_mode = TL_MODE_REF_ORDER;
+    uint32_t two_opt_runs = 1;  // >= 2: a 2opt stage runs this many seeded restarts (seed) at once and keeps the best; its warm start is not used
     simulated_annealing::SAOptions sa;
     uint32_t sa_chains = 1;  // an sa stage runs this many chains and keeps the best
     uint32_t tabu_chains = 1;  // a tabu_search stage likewise
@@ -1534,6 +1554,7 @@ struct StageOutcome {  // :11-14
     Solution solution;
     uint64_t duration_ms = 0;
     double duration_us = 0.0;  // the same interval, finer (the CLI's --timing)
+    int64_t best_restart = -1;  // a multi-start 2opt stage: the restart its tour came from
 };
 
 // stage_warnings (:92-132), for the solvers this build knows
@@ -1576,9 +1597,13 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
         const std::vector<size_t> *init = have_seed ? &seed : nullptr;
         const auto t0 = std::chrono::steady_clock::now();
         Solution sol;
+        uint32_t best_restart = 0;
         switch (s) {
             case Solvers::NearestNeighbor: sol = nearest_neighbor::solve(ctx, problem, o.heuristic, o.progress, init); break;
-            case Solvers::TwoOpt: sol = two_opt::solve(ctx, problem, o.heuristic, o.progress, init, o.two_opt_mode); break;
+            case Solvers::TwoOpt:
+                sol = o.two_opt_runs >= 2 ? two_opt::multistart(ctx, problem, o.two_opt_runs, o.seed, 0, o.two_opt_mode, &best_restart)
+                                          : two_opt::solve(ctx, problem, o.heuristic, o.progress, init, o.two_opt_mode);
+                break;
             case Solvers::ThreeOpt: sol = three_opt::solve(ctx, problem, o.heuristic, o.progress, init); break;
             case Solvers::OrOpt: sol = or_opt::solve(ctx, problem, o.heuristic, o.progress, init); break;
             case Solvers::LinKernighan: sol = lin_kernighan::solve(ctx, problem, o.lk, o.progress, init, o.seed); break;
@@ -1615,7 +1640,8 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
             throw std::runtime_error(std::string("stage ") + solver_name(s) + " invalid tour");  // :70-71
         seed = sol.route();
         have_seed = true;
-        out.push_back(StageOutcome{s, std::move(sol), ms, std::chrono::duration<double, std::micro>(t1 - t0).count()});
+        out.push_back(StageOutcome{s, std::move(sol), ms, std::chrono::duration<double, std::micro>(t1 - t0).count(),
+                                   s == Solvers::TwoOpt && o.two_opt_runs >= 2 ? (int64_t)best_restart : -1});
     }
     return out;
 }

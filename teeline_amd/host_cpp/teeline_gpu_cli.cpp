@@ -56,6 +56,8 @@
 //               with --optimal-tour the comparison goes to stderr in text mode and into the JSON object in JSON mode
 //   own flags (no counterpart in the reference): --seed S (LK kicks and the shuffle stage; the reference draws both from an
 //   unseeded thread RNG), --best-sweep (TL_MODE_BEST_SWEEP), --device N, --stats,
+//   `solve 2opt --runs K [--seed S] [--best-sweep]` with K >= 2: K seeded restarts at once (tl_two_opt_multistart), the best printed,
+//   --stats then also reports best_restart; without --runs, or with K = 1, the output is what it was,
 //   --exact-walk (TL_FLAG_BHK_EXACT_WALK: bhk reads its route back by exact equality instead of the reference's tolerance walk, whose
 //   result is now and then no tour — the stage then fails with "invalid tour", as in the reference),
 //   --timing (one JSON line on stderr: milliseconds of main() by phase — read input, create context, every stage's wall and kernel
@@ -79,6 +81,7 @@ struct Args {
     std::string cmd, solver, file, steps, optimal_tour, distance_type, output_format = "text";
     bool no_seed = false, best = false, exact_walk = false, stats = false, short_list = false, progress_digest = false, timing = false, full_exit = false;
     int device = 0, repeat = 1;
+    uint32_t runs = 1;  // --runs as given: `solve 2opt` reads it here
     pipeline::StageOptions opt;
     std::vector<double> fourier_lambdas, fourier_lrs;  // --lambda / --lr comma lists: their product is a fourier_curve batch
     // `bound` (the Held-Karp lower bound) and --lower-bound on solve / pipeline
@@ -100,6 +103,7 @@ struct Args {
                  "                         [--cooling-rate C] [--min-temperature LO] [--max-temperature HI] [--chains K] [--tabu-chains K]\n"
                  "                         [--mutation-probability P] [--n-elite N] [--ga-runs K]\n"
                  "                         [--alpha A] [--beta B] [--evaporation-rate R] [--num-ants N] [--runs K]\n"
+                 "                         (solve 2opt --runs K: K seeded restarts of --seed at once, the best printed)\n"
                  "                         [--max-nodes N] [--time-limit-ms T]\n"
                  "       teeline-gpu pipeline --steps=nn,2opt,... | --steps=greedy_edge,2opt,... | --steps=savings,2opt,... | --steps=christofides,lk,... [-i FILE] [options as above]\n"
                  "       teeline-gpu bound -i FILE [--upper U | --tour FILE] [--root R] [--iterations T] [--lambda L,L,...] [--patience P,P,...] [--output-format text|json]\n"
@@ -174,7 +178,7 @@ Args parse(int argc, char **argv)
         else if (s == "--beta") a.opt.aco.beta = std::stof(val());
         else if (s == "--evaporation-rate" || s == "--evaporation_rate") a.opt.aco.evaporation_rate = std::stof(val());
         else if (s == "--num-ants" || s == "--num_ants") a.opt.aco.num_ants = parse_usize(s, val());
-        else if (s == "--runs") a.opt.aco_runs = a.opt.pso_runs = a.opt.cs_runs = a.opt.fpa_runs = a.opt.gsa_runs = a.opt.som_runs = a.opt.hill_chains = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
+        else if (s == "--runs") a.runs = a.opt.aco_runs = a.opt.pso_runs = a.opt.cs_runs = a.opt.fpa_runs = a.opt.gsa_runs = a.opt.som_runs = a.opt.hill_chains = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--chains") a.opt.sa_chains = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
         else if (s == "--platoo_epochs" || s == "--platoo-epochs") a.opt.heuristic.platoo_epochs = a.opt.lk.heuristic.platoo_epochs = parse_usize(s, val());
         else if (s == "--n_nearest" || s == "--n-nearest") a.opt.heuristic.n_nearest = a.opt.lk.heuristic.n_nearest = a.opt.bnb.n_nearest = parse_usize(s, val());  // (branch_and_bound: only an explicit K restricts it)
@@ -350,7 +354,10 @@ int run(int argc, char **argv)
                 }
                 // auto_expand_with_nn (mod.rs:129-139): deterministic local searches are seeded with a nearest-neighbour stage
                 const bool expand = s == Solvers::TwoOpt || s == Solvers::ThreeOpt || s == Solvers::LinKernighan || s == Solvers::OrOpt || s == Solvers::TabuSearch || s == Solvers::BranchAndBound;
-                if (!a.no_seed && expand) stages = {Solvers::NearestNeighbor, s};
+                if (s == Solvers::TwoOpt && a.runs >= 2) {  // seeded restarts: no warm start to build
+                    a.opt.two_opt_runs = a.runs;
+                    stages = {s};
+                } else if (!a.no_seed && expand) stages = {Solvers::NearestNeighbor, s};
                 else if (!a.no_seed && (s == Solvers::SimulatedAnnealing || s == Solvers::GeneticAlgorithm || s == Solvers::AntColony || s == Solvers::ParticleSwarm || s == Solvers::CuckooSearch || s == Solvers::FlowerPollination || s == Solvers::GravitationalSearch || s == Solvers::HillClimb)) stages = {Solvers::RandomShuffle, s};  // mod.rs:144-157
                 else stages = {s};
             }
@@ -503,10 +510,13 @@ int run(int argc, char **argv)
                          ms_before_main, ms_read, ms_create, ms_problem, runs_json.c_str(), ms_since(t_out), ms_since(t_main), problem.cities.size());
         }
         if (a.stats)
-            for (const auto &o : outcomes)
-                std::fprintf(stderr, "stage %s: cost=%.5f sweeps=%llu candidates=%llu moves=%llu kernel_ms=%.3f wall_ms=%llu\n", solver_name(o.solver),
+            for (const auto &o : outcomes) {
+                std::fprintf(stderr, "stage %s: cost=%.5f sweeps=%llu candidates=%llu moves=%llu kernel_ms=%.3f wall_ms=%llu", solver_name(o.solver),
                              o.solution.total, (unsigned long long)o.solution.stats.sweeps, (unsigned long long)o.solution.stats.candidates,
                              (unsigned long long)o.solution.stats.moves, o.solution.stats.kernel_ms, (unsigned long long)o.duration_ms);
+                if (o.best_restart >= 0) std::fprintf(stderr, " best_restart=%lld", (long long)o.best_restart);
+                std::fprintf(stderr, "\n");
+            }
         return 0;
     } catch (const ReferencePanic &e) {
         std::fprintf(stderr, "thread 'main' panicked: %s\n", e.what());
