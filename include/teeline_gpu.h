@@ -318,6 +318,42 @@ typedef void (*tl_lk_progress_fn)(void *user, const uint32_t *best_pos, uint32_t
 int tl_lk_live(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, const tl_lk_opts *opts,
                uint64_t seed, uint32_t *out_pos, float *out_cost, tl_stats *stats, tl_lk_progress_fn progress, void *user);
 
+/* ---- Lin–Kernighan for seeded runs (additive entries, ABI v5) ---------------------------------------------------
+ * LK's result depends on its kick stream; the usual way to use it is several runs with different seeds, keeping the best.
+ * THE RUN SEED: run r of seed S is the search tl_lk performs with seed tl_lk_run_seed(S, r) — run 0: S itself; run r >= 1: output
+ * 2^63 + r of the splitmix64 stream of S (the kicks draw outputs below 2^35 of their stream, so run 1 of seed 1 is not run 0 of seed
+ * 2, as it would be with S + r).  Nothing else of LK changes: candidate lists, first lk_pass, accept / plateau rule, the cap of
+ * 64 n + 4096 moves per pass.  tl_lk_run_seed is host-only.
+ * tl_lk_population runs the runs first_run .. first_run + count - 1; run r of any call equals first_run = r, count = 1, and run 0
+ * equals tl_lk(seed): tour, cost bits and counters.  init_count: 0 (init_pos NULL) — the nearest-neighbour seed tl_lk would build,
+ * computed once; 1 — one start tour for all runs; count — row i starts run first_run + i; anything else TL_ERR_BADARG.  A row that is
+ * not a permutation: TL_ERR_BADARG, the message names the row; nothing is launched or written.  dm_packed as in tl_lk (the NN seed
+ * and the reported totals).  out_pos: count x n positions.  out_costs (optional, count floats): what tl_lk reports.  out_counters
+ * (optional, count x 4): the run's sweeps, candidates, moves, reversed as tl_lk's tl_stats counts them.  *best_index (optional): the
+ * row of minimum tl_pack_cost_key(cost, i) — equal costs go to the lowest run.  stats (optional): sums over the runs.
+ * count == 0: TL_OK, nothing written.  n < 4: every run returns its start tour untouched.  Options as tl_lk checks them (n_nearest
+ * 1..64, max_depth 1..16).  A run whose lk_pass hits the cap: TL_ERR_NO_CONVERGE, the message names the run.
+ * TWO FORMS, the same results.  Form 1: one workgroup per run with the whole ILS of that run in its CU's LDS (csrc/lk_ils.h,
+ * k_lk_ils_pop<NT>), all runs at once (256 threads up to n = 200, two such workgroups per CU where two LDS images fit; 1024 threads beyond, one per CU: the kernel's 110 registers allow 16 waves on a CU); possible where the LDS form of tl_lk fits
+ * (tl_lk_population_max_n: the largest such n for these options; 0 for a NULL context or where none fits).  Form 0: the runs one after
+ * the other, each in whatever form tl_lk takes (stats->kernel_ms: the sum of the runs' device times).
+ * tl_lk_population_plan (host-only, no context): the rule the entry follows for `count` runs of n cities on a device with `cus`
+ * compute units and lds_bytes of LDS per workgroup — force_form -1: the plan's choice (form 1 wherever it fits from the measured
+ * crossover count on: 64 runs where epochs and plateau are both >= 64, the speculative epochs of a single tl_lk filling the chip, else 2), 0 / 1: forced (1 where it does not fit still gives 0).  Outputs, each optional: *form; *threads (256 up to
+ * n = 200, else 1024; 0 in form 0); *per_cu (workgroups that share a CU: 2 where *threads is 256 and two LDS images fit, else 1; 0 in form 0).  TL_ERR_BADARG for cus < 1,
+ * lds_bytes < 0, a force_form outside -1..1 and options out of range.
+ * tl_lk_population_setting: a setting of the context, not a tl_create flag (all 31 assigned flag bits are taken; bit 31 stays the one
+ * no flag has) — the force_form of this context's later populations, and slice_scans, the scans a run advances per launch of form 1
+ * (0: the default of 8192; small values let tests reach the slice boundaries).  The cross-check knob of the two forms. */
+uint64_t tl_lk_run_seed(uint64_t seed, uint32_t run);
+uint32_t tl_lk_population_max_n(const tl_ctx *ctx, const tl_lk_opts *opts);
+int tl_lk_population_plan(uint32_t n, const tl_lk_opts *opts, uint32_t count, int cus, int lds_bytes, int force_form, int *form,
+                          int *threads, uint32_t *per_cu);
+int tl_lk_population_setting(tl_ctx *ctx, int force_form, uint32_t slice_scans);
+int tl_lk_population(tl_ctx *ctx, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
+                     uint32_t first_run, uint32_t count, const tl_lk_opts *opts, uint64_t seed, uint32_t *out_pos, float *out_costs,
+                     uint64_t *out_counters, uint32_t *best_index, tl_stats *stats);
+
 /* ---- LK candidate lists: replaces lin_kernighan::build_candidates (lin_kernighan.rs:12-27) -- */
 /* out: n x min(k, n-1) u32 — the k-NN buffer of the reference's kd-tree query per city (kdtree.rs:193-212, mod.rs:1839-1889):
  * ascending f32 distance, equal distances in the tree's visiting order.  The tree is the reference's wherever its median

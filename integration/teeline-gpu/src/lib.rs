@@ -238,6 +238,14 @@ unsafe extern "C" {
                                out_pos: *mut u32, out_costs: *mut f32, out_moves: *mut u32, stats: *mut Stats) -> c_int;
     fn tl_lk(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, opts: *const LkOpts, seed: u64,
              out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats) -> c_int;
+    fn tl_lk_run_seed(seed: u64, run: u32) -> u64;
+    fn tl_lk_population_max_n(ctx: *const TlCtx, opts: *const LkOpts) -> u32;
+    fn tl_lk_population_plan(n: u32, opts: *const LkOpts, count: u32, cus: c_int, lds_bytes: c_int, force_form: c_int, form: *mut c_int,
+                             threads: *mut c_int, per_cu: *mut u32) -> c_int;
+    fn tl_lk_population_setting(ctx: *mut TlCtx, force_form: c_int, slice_scans: u32) -> c_int;
+    fn tl_lk_population(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, init_count: u32, first_run: u32,
+                        count: u32, opts: *const LkOpts, seed: u64, out_pos: *mut u32, out_costs: *mut f32, out_counters: *mut u64,
+                        best_index: *mut u32, stats: *mut Stats) -> c_int;
     fn tl_sim_anneal_lds_max_n(ctx: *const TlCtx) -> u32;
     fn tl_sim_anneal(ctx: *mut TlCtx, xy: *const f32, n: u32, dm_packed: *const f32, init_pos: *const u32, opts: *const SaOpts, seed: u64,
                      out_pos: *mut u32, out_cost: *mut f32, stats: *mut Stats) -> c_int;
@@ -1274,6 +1282,63 @@ impl Context {
         Ok((0..count)
             .map(|k| Tour { pos: pos[k * n as usize..(k + 1) * n as usize].to_vec(), cost: costs[k], stats: Stats { moves: moves[k] as u64, ..stats } })
             .collect())
+    }
+
+    /// The seed of run `run` of a Lin-Kernighan population seeded `seed` (`tl_lk_run_seed`): run 0 the seed itself, run r >= 1 output
+    /// 2^63 + r of the seed's splitmix64 stream.
+    pub fn lk_run_seed(seed: u64, run: u32) -> u64 {
+        // SAFETY: a pure function of its arguments.
+        unsafe { tl_lk_run_seed(seed, run) }
+    }
+
+    /// Largest n whose seeded LK runs take one workgroup each with these options (`tl_lk_population_max_n`).
+    pub fn lk_population_max_n(&self, opts: LkOpts) -> u32 {
+        // SAFETY: a plain query of a live context.
+        unsafe { tl_lk_population_max_n(self.raw, &opts) }
+    }
+
+    /// Which form this context's later `lin_kernighan_population` calls take (-1: the plan's choice, 0: the loop over `tl_lk`, 1: one
+    /// workgroup per run wherever it fits) and the scans a run advances per launch of form 1 (0: the default): the cross-check knob.
+    pub fn lk_population_setting(&self, force_form: i32, slice_scans: u32) -> Result<(), Error> {
+        // SAFETY: a setting of a live context.
+        self.check(unsafe { tl_lk_population_setting(self.raw, force_form as c_int, slice_scans) })
+    }
+
+    /// Seeded runs `first_run .. first_run + count` of `lin_kernighan` at once (`tl_lk_population`): run r is the search of seed
+    /// `lk_run_seed(seed, r)`.  `init_pos`: None (the NN seed), one tour of n positions for all runs, or `count` of them back to back.
+    /// One `Tour` per run, its `stats` the call's with the run's own sweeps / candidates / moves / reversed; and the index of the
+    /// cheapest (equal costs: the lowest run).
+    pub fn lin_kernighan_population(&self, xy: &[f32], dm_packed: Option<&[f32]>, init_pos: Option<&[u32]>, first_run: u32, count: u32,
+                                    opts: LkOpts, seed: u64) -> Result<(Vec<Tour>, u32), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, None);
+        if n == 0 || count == 0 {
+            return Ok((Vec::new(), 0));
+        }
+        let init_count = init_pos.map_or(0, |p| {
+            assert!(p.len() % n as usize == 0, "init_pos holds whole tours of n positions");
+            (p.len() / n as usize) as u32
+        });
+        let mut pos = vec![0u32; count as usize * n as usize];
+        let mut costs = vec![0f32; count as usize];
+        let mut counters = vec![0u64; count as usize * 4];
+        let mut best = 0u32;
+        let mut stats = Stats::default();
+        // SAFETY: as in lin_kernighan; every output buffer holds count (x n, x 4) entries.
+        let rc = unsafe {
+            tl_lk_population(self.raw, xy.as_ptr(), n, dm_packed.map_or(std::ptr::null(), |d| d.as_ptr()),
+                             init_pos.map_or(std::ptr::null(), |p| p.as_ptr()), init_count, first_run, count, &opts, seed, pos.as_mut_ptr(),
+                             costs.as_mut_ptr(), counters.as_mut_ptr(), &mut best, &mut stats)
+        };
+        self.check(rc)?;
+        let tours = (0..count as usize)
+            .map(|k| Tour {
+                pos: pos[k * n as usize..(k + 1) * n as usize].to_vec(),
+                cost: costs[k],
+                stats: Stats { sweeps: counters[4 * k], candidates: counters[4 * k + 1], moves: counters[4 * k + 2], reversed: counters[4 * k + 3], ..stats },
+            })
+            .collect();
+        Ok((tours, best))
     }
 
     /// Largest n of the per-workgroup form of `three_opt_population` (either input form).

@@ -58,6 +58,7 @@ SYMBOLS = [
     "tl_greedy_edge", "tl_savings_hub", "tl_savings", "tl_christofides", "tl_bellman_karp",
     "tl_or_opt_population", "tl_or_opt_lds_max_n",
     "tl_two_opt_best_population", "tl_two_opt_best_lds_max_n", "tl_two_opt_best_plan", "tl_two_opt_best_force_scan",
+    "tl_lk_run_seed", "tl_lk_population_max_n", "tl_lk_population_plan", "tl_lk_population_setting", "tl_lk_population",
     "tl_three_opt_population", "tl_three_opt_pop_max_n", "tl_three_opt_population_plan", "tl_three_opt_population_work_limit",
     "tl_sim_anneal", "tl_sim_anneal_trace", "tl_sim_anneal_trace_chain", "tl_sim_anneal_population", "tl_sim_anneal_lds_max_n", "tl_sim_anneal_plan",
     "tl_sa_draw", "tl_sa_schedule_epochs", "tl_sa_selftest_accept",
@@ -256,6 +257,13 @@ def load():
     L.tl_or_opt_lds_max_n.argtypes = [vp]
     L.tl_or_opt_lds_max_n.restype = u32
     L.tl_or_opt_population.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, C.POINTER(TlStats)]
+    L.tl_lk_run_seed.argtypes = [u64, u32]
+    L.tl_lk_run_seed.restype = u64
+    L.tl_lk_population_max_n.argtypes = [vp, C.POINTER(TlLkOpts)]
+    L.tl_lk_population_max_n.restype = u32
+    L.tl_lk_population_plan.argtypes = [u32, C.POINTER(TlLkOpts), u32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(u32)]
+    L.tl_lk_population_setting.argtypes = [vp, i32, u32]
+    L.tl_lk_population.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, C.POINTER(TlLkOpts), u64, vp, vp, vp, C.POINTER(u32), C.POINTER(TlStats)]
     L.tl_two_opt_best_lds_max_n.argtypes = [vp]
     L.tl_two_opt_best_lds_max_n.restype = u32
     L.tl_two_opt_best_plan.argtypes = [u32, u32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]

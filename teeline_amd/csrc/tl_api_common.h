@@ -53,6 +53,8 @@ struct tl_ctx {
     std::string err;
     DevBuf xy, dm, init, out_pos, out_cost, out_stats, misc, work, dmfull, kd, fx, nl, dmx;  // dmx: matrix-form 2-opt, the descents' per-city records of their late sweeps
     bool two_opt_best_force_scan = false;  // tl_two_opt_best_force_scan: best-sweep batches loop over the chip-wide descent at every n
+    int lk_pop_force_form = -1;          // tl_lk_population_setting: -1 the plan's choice, 0 the loop over tl_lk, 1 one workgroup per run
+    uint32_t lk_pop_slice_scans = 0;     // ... and the scans per launch of that form (0: kLkIlsSlice)
     uint64_t three_opt_pop_work = 0;  // tl_three_opt_population: cap on the per-tour matrices' workspace (0: the default)
     uint32_t dm_n = 0;
     int dm_layout = -1;

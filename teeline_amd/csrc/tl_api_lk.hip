@@ -514,3 +514,235 @@ extern "C" int tl_lk_live(tl_ctx *c, const float *xy, uint32_t n, const float *d
     return lk_run(c, xy, n, dm_packed, init_pos, opts, seed, out_pos, out_cost, stats, nullptr, nullptr, 0, nullptr, progress, user);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Lin-Kernighan for seeded runs: run r of seed S is tl_lk with seed tl_lk_run_seed(S, r)
+// ------------------------------------------------------------------------------------------------
+// The plan's crossover: the smallest count from which one workgroup per run beats the loop over tl_lk.  Measured on one MI355X
+// (scripts/timing_lk_population.py, profiles/lk_population_timing.jsonl; NOTEBOOK.md, "Lin-Kernighan for seeded runs"), counts 1, 2, 4, 8,
+// 16, 64, 256, 512.  With a long plateau (tl_lk's own test for "the speculative epochs fill the chip": epochs and plateau >= 64) a single
+// tl_lk is 10-15 times faster than its one-workgroup form, and the loop wins up to 16 runs — berlin52 34.8 against 41.5 ms, att532 554
+// against 687 ms with the CLI's options — and loses at 64 (139 against 58 ms, 2 217 against 820 ms): 64, the smallest count measured at
+// which form 1 is faster.  With a short plateau there is little to speculate on: n = 1 002 with the library defaults, 2 runs 51.0 against
+// 40.1 ms: 2 (smaller n with a short plateau was not measured and takes the same constant).
+static uint32_t lk_pop_min_count(const tl_lk_opts &o) { return (o.epochs >= 64u && o.platoo_epochs >= 64u) ? 64u : 2u; }
+
+static uint64_t splitmix64_at_host(uint64_t seed, uint64_t k)  // tl_device.h splitmix64_at
+{
+    uint64_t z = seed + (k + 1) * 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+// run 0: the seed itself (tl_lk as it is); run r >= 1: output 2^63 + r of the seed's splitmix64 stream — the kicks draw below 2^35
+extern "C" uint64_t tl_lk_run_seed(uint64_t seed, uint32_t run) { return run == 0u ? seed : splitmix64_at_host(seed, (1ull << 63) + run); }
+
+// the options as tl_lk reads them; 0, or the code tl_lk gives (what: filled with the reason)
+static int lk_pop_opts(const tl_lk_opts *opts, tl_lk_opts *o, const char **what)
+{
+    *o = tl_lk_opts{100, 10, 5, 5};
+    if (opts) *o = *opts;
+    *what = nullptr;
+    if (o->n_nearest == 0) return *what = "n_nearest must be >= 1", TL_ERR_BADARG;
+    if (o->max_depth == 0) return *what = "max_depth must be >= 1", TL_ERR_BADARG;
+    if (o->max_depth > tl_lk_deep::lk_max_depth()) return *what = "max_depth beyond the largest chain this build holds (16)", TL_ERR_UNSUPPORTED;
+    if (o->n_nearest > 64) return *what = "n_nearest > 64 (the k-nearest buffer of a query lives in registers)", TL_ERR_UNSUPPORTED;
+    return TL_OK;
+}
+
+// records per level queue of the one-workgroup form for these options on lds_bytes of LDS, its LDS image; 0: the form does not apply
+static uint32_t lk_pop_qcap(uint32_t n, const tl_lk_opts &o, size_t lds_bytes, size_t *image)
+{
+    if (n < 4) return 0u;
+    const uint32_t k = o.n_nearest > n - 1 ? n - 1 : o.n_nearest;
+    const bool deep = o.max_depth > lk_max_depth();
+    const uint32_t q = deep ? tl_lk_deep::lk_ils_qcap(n, k, o.max_depth, lds_bytes) : lk_ils_qcap(n, k, o.max_depth, lds_bytes);
+    if (q && image) *image = deep ? tl_lk_deep::lk_ils_lds_bytes(n, k, o.max_depth, q) : lk_ils_lds_bytes(n, k, o.max_depth, q);
+    return q;
+}
+
+extern "C" uint32_t tl_lk_population_max_n(const tl_ctx *c, const tl_lk_opts *opts)
+{
+    tl_lk_opts o;
+    const char *what;
+    if (!c || c->lds_bytes <= 0 || lk_pop_opts(opts, &o, &what)) return 0u;
+    for (uint32_t n = 65535u; n >= 4u; --n)
+        if (lk_pop_qcap(n, o, (size_t)c->lds_bytes, nullptr)) return n;
+    return 0u;
+}
+
+extern "C" int tl_lk_population_plan(uint32_t n, const tl_lk_opts *opts, uint32_t count, int cus, int lds_bytes, int force_form, int *form,
+                                     int *threads, uint32_t *per_cu)
+{
+    tl_lk_opts o;
+    const char *what;
+    if (cus < 1 || lds_bytes < 0 || force_form < -1 || force_form > 1 || lk_pop_opts(opts, &o, &what)) return TL_ERR_BADARG;
+    size_t image = 0;
+    const bool fits = lk_pop_qcap(n, o, (size_t)lds_bytes, &image) != 0u;
+    const bool one_each = fits && (force_form == 1 || (force_form < 0 && count >= lk_pop_min_count(o)));
+    if (form) *form = one_each ? 1 : 0;
+    if (threads) *threads = one_each ? (int)lk_ils_threads(n) : 0;
+    // Two workgroups share a CU where two LDS images fit AND the registers allow it: k_lk_ils_pop takes 110 VGPRs (128 in the deep build;
+    // scripts/kernel_regs.sh), i.e. 4 waves per SIMD, 16 per CU — ONE workgroup of 1024 threads, while the 4 waves of a 256-thread one
+    // leave room for a second (the dispatcher places the workgroups; this is what the launch can expect, not something it enforces).
+    if (per_cu) *per_cu = one_each ? ((lk_ils_threads(n) == 256u && 2 * image <= (size_t)lds_bytes) ? 2u : 1u) : 0u;
+    return TL_OK;
+}
+
+extern "C" int tl_lk_population_setting(tl_ctx *c, int force_form, uint32_t slice_scans)
+{
+    TL_ENTER(c);
+    if (!c) return fail(c, TL_ERR_BADARG, "tl_lk_population_setting: NULL context");
+    if (force_form < -1 || force_form > 1) return fail(c, TL_ERR_BADARG, "tl_lk_population_setting: force_form=%d is none of -1, 0, 1", force_form);
+    c->lk_pop_force_form = force_form;
+    c->lk_pop_slice_scans = slice_scans;
+    return TL_OK;
+}
+
+extern "C" int tl_lk_population(tl_ctx *c, const float *xy, uint32_t n, const float *dm_packed, const uint32_t *init_pos, uint32_t init_count,
+                                uint32_t first_run, uint32_t count, const tl_lk_opts *opts, uint64_t seed, uint32_t *out_pos, float *out_costs,
+                                uint64_t *out_counters, uint32_t *best_index, tl_stats *stats)
+{
+    TL_ENTER(c);
+    if (!c || !xy) return fail(c, TL_ERR_BADARG, "tl_lk_population: NULL argument");
+    if (count == 0) return TL_OK;
+    if (!out_pos) return fail(c, TL_ERR_BADARG, "tl_lk_population: NULL argument");
+    if (n == 0) return fail(c, TL_ERR_BADARG, "tl_lk_population: n == 0");
+    if ((uint64_t)first_run + count > 0x100000000ull) return fail(c, TL_ERR_BADARG, "tl_lk_population: first_run + count exceeds 2^32");
+    tl_lk_opts o;
+    const char *what;
+    if (int orc = lk_pop_opts(opts, &o, &what)) return fail(c, orc, "tl_lk_population: %s", what);
+    if ((init_count != 0 && init_count != 1 && init_count != count) || (init_count != 0) != (init_pos != nullptr))
+        return fail(c, TL_ERR_BADARG, "tl_lk_population: init_count=%u is none of 0 (init_pos NULL), 1 and count=%u", init_count, count);
+    for (uint32_t i = 0; i < init_count; ++i)
+        if (!is_permutation(init_pos + (size_t)i * n, n))
+            return fail(c, TL_ERR_BADARG, "tl_lk_population: start tour %u is not a permutation of 0..n-1", i);
+    const auto t0 = std::chrono::steady_clock::now();
+    int form = 0, rc;
+    if ((rc = tl_lk_population_plan(n, &o, count, c->cus > 0 ? c->cus : 1, c->lds_bytes, c->lk_pop_force_form, &form, nullptr, nullptr)))
+        return fail(c, rc, "tl_lk_population: no plan for these options");
+    std::vector<float> costs(count);
+    std::vector<uint64_t> cnts((size_t)count * 4, 0ull);
+    auto start_of = [&](uint32_t i) { return init_count == 0 ? nullptr : init_pos + (size_t)(init_count == 1 ? 0 : i) * n; };
+    auto finish = [&](double kernel_ms, bool own_events) {
+        uint64_t bk = ~0ull;
+        tl_stats acc{};
+        for (uint32_t i = 0; i < count; ++i) {
+            const uint64_t key = tl_pack_cost_key(costs[i], i);
+            if (key < bk) bk = key;
+            acc.sweeps += cnts[(size_t)i * 4];
+            acc.candidates += cnts[(size_t)i * 4 + 1];
+            acc.moves += cnts[(size_t)i * 4 + 2];
+            acc.reversed += cnts[(size_t)i * 4 + 3];
+        }
+        if (out_costs) memcpy(out_costs, costs.data(), (size_t)count * 4);
+        if (out_counters) memcpy(out_counters, cnts.data(), (size_t)count * 32);
+        if (best_index) *best_index = (uint32_t)(bk & 0xFFFFFFFFull);
+        if (stats) {
+            *stats = acc;
+            if (own_events) stamp_times(c, stats, t0);
+            else {
+                stats->kernel_ms = kernel_ms;
+                stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            }
+        }
+        return TL_OK;
+    };
+    if (form == 0) {
+        // the runs one after the other, each in whatever form tl_lk takes (n < 4: the start tour untouched, lin_kernighan.rs:45-59)
+        std::vector<uint32_t> pos((size_t)count * n);
+        double kms = 0;
+        for (uint32_t i = 0; i < count; ++i) {
+            tl_stats st{};
+            rc = lk_run(c, xy, n, dm_packed, start_of(i), &o, tl_lk_run_seed(seed, first_run + i), pos.data() + (size_t)i * n, &costs[i], &st, nullptr, nullptr, 0, nullptr);
+            if (rc != TL_OK) {
+                const std::string why = c->err;
+                return fail(c, rc, "tl_lk_population: run %u: %s", first_run + i, why.c_str());
+            }
+            cnts[(size_t)i * 4] = st.sweeps;
+            cnts[(size_t)i * 4 + 1] = st.candidates;
+            cnts[(size_t)i * 4 + 2] = st.moves;
+            cnts[(size_t)i * 4 + 3] = st.reversed;
+            kms += st.kernel_ms;
+        }
+        memcpy(out_pos, pos.data(), pos.size() * 4);
+        return finish(kms, false);
+    }
+    // ---- one workgroup per run (k_lk_ils_pop<NT>): every check and every allocation before the first enqueue
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool deep = o.max_depth > lk_max_depth();
+    const uint32_t k = o.n_nearest > n - 1 ? n - 1 : o.n_nearest;
+    const uint32_t qcap = lk_pop_qcap(n, o, (size_t)c->lds_bytes, nullptr);
+    const size_t rows = up256((size_t)count * n * 4), ck = up256((size_t)n * k * 4);
+    const size_t o_cand = 0, o_dc = ck, o_tour = o_dc + ck, o_ids = o_tour + rows, o_best = o_ids + rows, o_state = o_best + rows,
+                 o_seeds = o_state + up256((size_t)count * sizeof(LkState)), total = o_seeds + up256((size_t)count * 8);
+    if (!init_pos && dm_packed && (size_t)n + 1024 > (size_t)c->lds_bytes)
+        return fail(c, TL_ERR_UNSUPPORTED, "nearest_neighbor: n=%u exceeds the LDS-resident visited flags", n);
+    if ((rc = ensure(c, c->xy, (size_t)n * 8)) || (rc = ensure(c, c->work, total)) || (rc = ensure(c, c->out_cost, (size_t)count * 4))) return rc;
+    std::vector<uint64_t> seeds(count);
+    for (uint32_t i = 0; i < count; ++i) seeds[i] = tl_lk_run_seed(seed, first_run + i);
+    std::vector<LkState> hs(count);
+    unsigned char *w = (unsigned char *)c->work.p;
+    HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    const float *ddm = nullptr;
+    if (dm_packed && (rc = upload_dm(c, dm_packed, n, &ddm))) return rc;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    c->ev_valid = false;
+    if (init_pos) {
+        HIPCHK(c, hipMemcpyAsync(w + o_tour, init_pos, (size_t)init_count * n * 4, hipMemcpyHostToDevice, c->stream));
+    } else if (ddm) {
+        HIPCHK(c, launch_nn_seed_dm(ddm, n, (uint32_t *)(w + o_tour), c->lds_bytes, c->stream));
+    } else if ((rc = nn_seed_dev(c, (const float2 *)c->xy.p, n, 3, (uint32_t *)(w + o_tour)))) {
+        return rc;
+    }
+    if ((rc = build_candidates_dev(c, xy, (const float2 *)c->xy.p, n, k, (uint32_t *)(w + o_cand)))) return rc;
+    HIPCHK(c, hipMemsetAsync(w + o_state, 0, (size_t)count * sizeof(LkState), c->stream));
+    HIPCHK(c, hipMemcpyAsync(w + o_seeds, seeds.data(), (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
+    LkArgs G{};
+    G.xy = (const float2 *)c->xy.p;
+    G.cand = (const uint32_t *)(w + o_cand);
+    G.ils_dcand = (float *)(w + o_dc);
+    G.tour = (uint32_t *)(w + o_tour);
+    G.city_ids = (uint32_t *)(w + o_ids);
+    G.best = (uint32_t *)(w + o_best);
+    G.state = (LkState *)(w + o_state);
+    G.counters = (uint64_t *)(w + o_seeds);  // (the population launch reads the runs' seeds here)
+    G.n = n;
+    G.k = k;
+    G.max_depth = o.max_depth;
+    G.epochs = o.epochs;
+    G.platoo_epochs = o.platoo_epochs;
+    G.lds_budget = (uint32_t)c->lds_bytes;
+    G.ils_qcap = qcap;
+    G.ils_slice = c->lk_pop_slice_scans ? c->lk_pop_slice_scans : kLkIlsSlice;
+    G.ils_mode = 0u;
+    HIPCHK(c, deep ? tl_lk_deep::launch_lk_pop_prepare(G, count, init_count != count, c->stream) : launch_lk_pop_prepare(G, count, init_count != count, c->stream));
+    // a launch is a slice: every unfinished run advances by at most ils_slice scans and stores its state; the host reads the `count`
+    // states back and stops when every run has finished (1) or been found cycling (2)
+    for (;;) {
+        HIPCHK(c, deep ? tl_lk_deep::launch_lk_ils_pop(G, count, c->stream) : launch_lk_ils_pop(G, count, c->stream));
+        HIPCHK(c, hipMemcpyAsync(hs.data(), G.state, (size_t)count * sizeof(LkState), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        bool all = true;
+        for (uint32_t i = 0; i < count && all; ++i) all = hs[i].finished != 0u;
+        if (all) break;
+    }
+    for (uint32_t i = 0; i < count; ++i)
+        if (hs[i].finished == 2u)
+            return fail(c, TL_ERR_NO_CONVERGE, "tl_lk_population: run %u: an lk_pass does not terminate (the reference's loop cycles on this input: chains of rounded f32 gain that lead back to the same tour)", first_run + i);
+    // lin_kernighan.rs:99 Solution::new -> each run's total through problem.distances.tour_length (closing edge first)
+    for (uint32_t i = 0; i < count; ++i)
+        HIPCHK(c, launch_tour_length(ddm ? nullptr : G.xy, ddm, n, G.best + (size_t)i * n, (float *)c->out_cost.p + i, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    c->ev_valid = true;
+    HIPCHK(c, hipMemcpyAsync(out_pos, G.best, (size_t)count * n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(costs.data(), c->out_cost.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < count; ++i) {
+        cnts[(size_t)i * 4] = hs[i].scans;
+        cnts[(size_t)i * 4 + 1] = hs[i].searches;
+        cnts[(size_t)i * 4 + 2] = hs[i].moves;
+        cnts[(size_t)i * 4 + 3] = hs[i].exchanged;
+    }
+    return finish(0, true);
+}

@@ -750,6 +750,8 @@ struct LkArgs {
     uint32_t *ils_ep_tour;   // [ils_P][n] the tour each epoch ends on
     float *ils_ep_dist;      // [ils_P] its tour_distance
     uint64_t *ils_ep_cnt;    // [ils_P][4] scans, searches, moves, exchanged edges of the epoch
+    // the population launch (k_lk_ils_pop<NT>): state, tour, best and city_ids are arrays of `count` rows and `counters` holds the runs'
+    // seeds, run b's in counters[b] (no field of its own: a longer LkArgs moves the hidden kernel arguments of the chip-wide kernels)
 };
 // form: 0 = default (16 lanes per city up to n = 32 K, 4 beyond), 4 = four lanes per city, 1 = one lane per city
 hipError_t launch_knn(const float2 *xy, uint32_t n, uint32_t k, uint32_t *cand, hipStream_t s, int form = 0);
@@ -764,6 +766,9 @@ uint32_t lk_ils_qcap(uint32_t n, uint32_t k, uint32_t max_depth, size_t lds_budg
 size_t lk_ils_lds_bytes(uint32_t n, uint32_t k, uint32_t max_depth, uint32_t qcap);   // LDS of one k_lk_ils workgroup
 hipError_t launch_lk_ils(const LkArgs &G, hipStream_t s);                             // mode 0 / 1: one slice of G.ils_slice scans; mode 2: ils_P epochs
 hipError_t launch_lk_ils_commit(const LkArgs &G, hipStream_t s);                      // the verdict over a batch of epochs
+uint32_t lk_ils_threads(uint32_t n);                                                   // its width by n: 256 up to TL_ILS_SMALL_N, else 1024
+hipError_t launch_lk_pop_prepare(const LkArgs &G, uint32_t count, bool share_start, hipStream_t s);  // a population's ils_dcand, and its shared start tour into every row
+hipError_t launch_lk_ils_pop(const LkArgs &G, uint32_t count, hipStream_t s);         // one slice of G.ils_slice scans of every unfinished run, a workgroup per run
 size_t lk_chain_slot_words();
 size_t lk_sub_slot_words();
 uint32_t lk_max_depth();  // the build's compile-time recursion bound (6)
@@ -779,6 +784,9 @@ uint32_t lk_ils_qcap(uint32_t n, uint32_t k, uint32_t max_depth, size_t lds_budg
 size_t lk_ils_lds_bytes(uint32_t n, uint32_t k, uint32_t max_depth, uint32_t qcap);
 hipError_t launch_lk_ils(const tl::LkArgs &G, hipStream_t s);
 hipError_t launch_lk_ils_commit(const tl::LkArgs &G, hipStream_t s);
+uint32_t lk_ils_threads(uint32_t n);
+hipError_t launch_lk_pop_prepare(const tl::LkArgs &G, uint32_t count, bool share_start, hipStream_t s);
+hipError_t launch_lk_ils_pop(const tl::LkArgs &G, uint32_t count, hipStream_t s);
 size_t lk_chain_slot_words();
 size_t lk_sub_slot_words();
 uint32_t lk_max_depth();

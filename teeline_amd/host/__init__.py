@@ -81,6 +81,17 @@ class Context:
         every n (the cross-check of the two forms); on=False restores the default."""
         self.check(self._lib.tl_two_opt_best_force_scan(self._h, 1 if on else 0))
 
+    def lk_population_setting(self, force_form=-1, slice_scans=0):
+        """tl_lk_population_setting: which form this context's later lin_kernighan.solve_population calls take (-1: the plan's choice,
+        0: the loop over tl_lk, 1: one workgroup per run wherever it fits) and the scans a run advances per launch of form 1 (0: the
+        default) — the cross-check of the two forms."""
+        self.check(self._lib.tl_lk_population_setting(self._h, int(force_form), int(slice_scans)))
+
+    def lk_population_max_n(self, opts=None):
+        """tl_lk_population_max_n: the largest n whose runs take one workgroup each with these LKOptions (None: the library defaults)."""
+        o = None if opts is None else C.byref(_capi.TlLkOpts(opts.heuristic.epochs, opts.heuristic.platoo_epochs, opts.heuristic.n_nearest, opts.max_depth))
+        return int(self._lib.tl_lk_population_max_n(self._h, o))
+
     def three_opt_pop_max_n(self):
         return int(self._lib.tl_three_opt_pop_max_n(self._h))
 

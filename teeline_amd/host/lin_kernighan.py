@@ -58,3 +58,66 @@ def build_candidates(problem, k, *, ctx=None):
     ctx.check(ctx.lib.tl_build_candidates(ctx.handle, problem.xy.ctypes.data_as(C.c_void_p), n, int(k),
                                           out.ctypes.data_as(C.c_void_p)))
     return out[:, :kk]
+
+
+def _lk_opts(opts):
+    from .. import _capi
+    return _capi.TlLkOpts(opts.heuristic.epochs, opts.heuristic.platoo_epochs, opts.heuristic.n_nearest, opts.max_depth)
+
+
+def run_seed(seed, run):
+    """tl_lk_run_seed: the seed of run `run` of a population seeded `seed` — run 0 the seed itself, run r >= 1 output 2^63 + r of the
+    seed's splitmix64 stream (the kicks of a search draw below 2^35 of theirs)."""
+    from .. import _capi
+    return int(_capi.load().tl_lk_run_seed(int(seed) & (2**64 - 1), int(run)))
+
+
+def population_plan(n, opts=None, runs=2, *, cus=256, lds_bytes=163840, force_form=-1):
+    """tl_lk_population_plan (host-only): {"form": 1 one workgroup per run / 0 the loop over tl_lk, "threads", "per_cu"} for `runs` runs
+    of n cities on a device with `cus` compute units and `lds_bytes` of LDS per workgroup."""
+    from . import TeelineGpuError
+    from .. import _capi
+    f, t, p = C.c_int(), C.c_int(), C.c_uint32()
+    rc = _capi.load().tl_lk_population_plan(int(n), None if opts is None else C.byref(_lk_opts(opts)), int(runs), int(cus), int(lds_bytes),
+                                            int(force_form), C.byref(f), C.byref(t), C.byref(p))
+    if rc:
+        raise TeelineGpuError(rc, "tl_lk_population_plan: cus < 1, lds_bytes < 0, force_form outside -1..1 or options out of range")
+    return {"form": f.value, "threads": t.value, "per_cu": p.value}
+
+
+def solve_population(problem, opts=None, init_tours=None, *, seed, runs, first_run=0, ctx=None):
+    """Seeded runs first_run .. first_run + runs - 1 of lin_kernighan::solve at once (tl_lk_population): run r is solve(...,
+    seed=run_seed(seed, r)), run 0 the plain seed's.  init_tours: None (the NN seed solve would build), one tour of city ids for all
+    runs, or `runs` of them.  Returns (solutions, best): one Solution per run with that run's own counters in its stats (the call's
+    times), and the index of the cheapest (equal totals: the lowest run)."""
+    from . import LKOptions, Solution, TeelineGpuError, default_context
+    from .. import _capi
+    runs = int(runs)
+    if runs < 1:
+        raise TeelineGpuError(_capi.TL_ERR_BADARG, f"lin_kernighan.solve_population: runs={runs} < 1")
+    if init_tours is not None and len(init_tours) not in (1, runs):
+        raise TeelineGpuError(_capi.TL_ERR_BADARG, f"lin_kernighan.solve_population: {len(init_tours)} start tours for {runs} runs (one, or one per run)")
+    n = len(problem)
+    for k, tour in enumerate(init_tours or ()):  # the library reads rows of n u32 values: checked before any pointer is taken
+        if len(tour) != n:
+            raise TeelineGpuError(_capi.TL_ERR_BADARG, f"tour {k} has {len(tour)} cities, the problem {n}")
+    opts = opts or LKOptions()
+    opts.validate()
+    ctx = ctx or default_context()
+    init = None if init_tours is None else np.ascontiguousarray([problem.positions_of(t) for t in init_tours], dtype=np.uint32)
+    o = _lk_opts(opts)
+    out = np.empty((runs, n), dtype=np.uint32)
+    costs = np.empty(runs, dtype=np.float32)
+    cnt = np.zeros((runs, 4), dtype=np.uint64)
+    best = C.c_uint32()
+    st = _capi.TlStats()
+    packed = problem.explicit_packed()
+    ctx.check(ctx.lib.tl_lk_population(ctx.handle, problem.xy.ctypes.data_as(C.c_void_p), n,
+                                       None if packed is None else packed.ctypes.data_as(C.c_void_p),
+                                       None if init is None else init.ctypes.data_as(C.c_void_p), 0 if init is None else len(init),
+                                       int(first_run), runs, C.byref(o), int(seed) & (2**64 - 1), out.ctypes.data_as(C.c_void_p),
+                                       costs.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p), C.byref(best), C.byref(st)))
+    stats = st.as_dict()
+    sols = [Solution(float(costs[r]), problem.ids[out[r]], problem,
+                     dict(stats, sweeps=int(cnt[r, 0]), candidates=int(cnt[r, 1]), moves=int(cnt[r, 2]), reversed=int(cnt[r, 3]))) for r in range(runs)]
+    return sols, int(best.value)

@@ -706,6 +706,46 @@ inline Solution solve(Context &ctx, const TspProblem &problem, const LKOptions &
     if (live.err) std::rethrow_exception(live.err);
     return detail::finish(problem, out, cost, st, nullptr);
 }
+
+inline uint64_t run_seed(uint64_t seed, uint32_t run) { return tl_lk_run_seed(seed, run); }
+
+// Seeded runs first_run .. first_run + runs - 1 at once (tl_lk_population): run r is solve(..., seed = run_seed(seed, r)), run 0 the plain
+// seed's.  init_tours: none (the NN seed solve would build), one start for all runs, or one per run.  One Solution per run, each with the
+// run's own counters in its stats (the times are the call's); *best (optional): the cheapest, equal totals going to the lowest run.
+inline std::vector<Solution> solve_population(Context &ctx, const TspProblem &problem, const LKOptions &opts, const std::vector<std::vector<size_t>> *init_tours,
+                                              uint64_t seed, uint32_t runs, uint32_t first_run = 0, uint32_t *best = nullptr)
+{
+    if (opts.heuristic.n_nearest == 0) throw std::runtime_error("n_nearest must be >= 1");
+    if (opts.max_depth == 0) throw std::runtime_error("max_depth must be >= 1");
+    if (runs == 0) throw std::runtime_error("lin_kernighan::solve_population: runs == 0");
+    const size_t given = init_tours ? init_tours->size() : 0;
+    if (init_tours && given != 1 && given != runs) throw std::runtime_error("lin_kernighan::solve_population: one start tour, or one per run");
+    const auto xy = problem.xy();
+    const uint32_t n = (uint32_t)problem.cities.size();
+    std::vector<uint32_t> init, out((size_t)runs * n);
+    for (size_t k = 0; k < given; ++k) {
+        const std::vector<uint32_t> row = problem.positions_of((*init_tours)[k]);
+        init.insert(init.end(), row.begin(), row.end());
+    }
+    tl_lk_opts o{(uint32_t)opts.heuristic.epochs, (uint32_t)opts.heuristic.platoo_epochs, (uint32_t)opts.heuristic.n_nearest, (uint32_t)opts.max_depth};
+    std::vector<float> costs(runs);
+    std::vector<uint64_t> cnt((size_t)runs * 4);
+    uint32_t bi = 0;
+    tl_stats st{};
+    ctx.check(tl_lk_population(ctx.get(), xy.data(), n, problem.explicit_packed(), given ? init.data() : nullptr, (uint32_t)given, first_run, runs, &o, seed,
+                               out.data(), costs.data(), cnt.data(), &bi, &st));
+    std::vector<Solution> sols;
+    for (uint32_t r = 0; r < runs; ++r) {
+        tl_stats sr = st;
+        sr.sweeps = cnt[(size_t)r * 4];
+        sr.candidates = cnt[(size_t)r * 4 + 1];
+        sr.moves = cnt[(size_t)r * 4 + 2];
+        sr.reversed = cnt[(size_t)r * 4 + 3];
+        sols.push_back(detail::finish(problem, std::vector<uint32_t>(out.begin() + (size_t)r * n, out.begin() + (size_t)(r + 1) * n), costs[r], sr, nullptr));
+    }
+    if (best) *best = bi;
+    return sols;
+}
 }  // namespace lin_kernighan
 
 namespace tsplib {  // tsplib.rs:142-255
@@ -1527,6 +1567,7 @@ struct StageOptions {
     LKOptions lk;
     int two_opt_mode = TL_MODE_REF_ORDER;
     uint32_t two_opt_runs = 1;  // >= 2: a 2opt stage runs this many seeded restarts (seed) at once and keeps the best; its warm start is not used
+    uint32_t lk_runs = 1;  // >= 2: an lk stage that is the LAST stage runs this many seeded runs (seed) at once from its warm start and keeps the best
     simulated_annealing::SAOptions sa;
     uint32_t sa_chains = 1;  // an sa stage runs this many chains and keeps the best
     uint32_t tabu_chains = 1;  // a tabu_search stage likewise
@@ -1555,6 +1596,7 @@ struct StageOutcome {  // :11-14
     uint64_t duration_ms = 0;
     double duration_us = 0.0;  // the same interval, finer (the CLI's --timing)
     int64_t best_restart = -1;  // a multi-start 2opt stage: the restart its tour came from
+    int64_t best_run = -1;      // an lk stage of several seeded runs: the run its tour came from
 };
 
 // stage_warnings (:92-132), for the solvers this build knows
@@ -1589,7 +1631,9 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
     std::vector<StageOutcome> out;
     std::vector<size_t> seed;
     bool have_seed = false;
+    size_t stage_index = 0;
     for (Solvers s : stages) {
+        const bool last_stage = ++stage_index == stages.size();
         if (have_seed && !validate_tour(seed, problem.cities)) {
             std::fprintf(stderr, "warning: pipeline: invalid seed; using default seeding\n");
             have_seed = false;
@@ -1597,7 +1641,8 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
         const std::vector<size_t> *init = have_seed ? &seed : nullptr;
         const auto t0 = std::chrono::steady_clock::now();
         Solution sol;
-        uint32_t best_restart = 0;
+        uint32_t best_restart = 0, best_run = 0;
+        const bool lk_population = s == Solvers::LinKernighan && last_stage && o.lk_runs >= 2;
         switch (s) {
             case Solvers::NearestNeighbor: sol = nearest_neighbor::solve(ctx, problem, o.heuristic, o.progress, init); break;
             case Solvers::TwoOpt:
@@ -1606,7 +1651,15 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
                 break;
             case Solvers::ThreeOpt: sol = three_opt::solve(ctx, problem, o.heuristic, o.progress, init); break;
             case Solvers::OrOpt: sol = or_opt::solve(ctx, problem, o.heuristic, o.progress, init); break;
-            case Solvers::LinKernighan: sol = lin_kernighan::solve(ctx, problem, o.lk, o.progress, init, o.seed); break;
+            case Solvers::LinKernighan:
+                if (lk_population) {
+                    std::vector<std::vector<size_t>> start;
+                    if (init) start.push_back(*init);
+                    sol = lin_kernighan::solve_population(ctx, problem, o.lk, init ? &start : nullptr, o.seed, o.lk_runs, 0, &best_run)[best_run];
+                } else {
+                    sol = lin_kernighan::solve(ctx, problem, o.lk, o.progress, init, o.seed);
+                }
+                break;
             case Solvers::RandomShuffle: sol = random_shuffle::solve(ctx, problem, o.seed); break;
             case Solvers::GreedyEdge: sol = greedy_edge::solve(ctx, problem, o.heuristic, o.progress, init); break;
             case Solvers::Savings: sol = savings::solve(ctx, problem, o.heuristic, o.progress, init); break;
@@ -1641,7 +1694,7 @@ inline std::vector<StageOutcome> run_pipeline_stages(Context &ctx, const TspProb
         seed = sol.route();
         have_seed = true;
         out.push_back(StageOutcome{s, std::move(sol), ms, std::chrono::duration<double, std::micro>(t1 - t0).count(),
-                                   s == Solvers::TwoOpt && o.two_opt_runs >= 2 ? (int64_t)best_restart : -1});
+                                   s == Solvers::TwoOpt && o.two_opt_runs >= 2 ? (int64_t)best_restart : -1, lk_population ? (int64_t)best_run : -1});
     }
     return out;
 }
@@ -1748,9 +1801,12 @@ inline std::string format_lower_bound(float solver_cost, const one_tree_bound::B
 
 // lb (--lower-bound): adds "bound" and "gap_pct" (f64); beside an optimal comparison, whose "gap_pct" keeps its key, the bound's gap
 // is "bound_gap_pct"
-inline std::string format_solution_json(const Solution &tour, bool is_optimized, const OptimalComparison *opt, const one_tree_bound::Bound *lb = nullptr)
+// best_run >= 0 (an lk stage of `runs` seeded runs): adds "best_run" and "runs"
+inline std::string format_solution_json(const Solution &tour, bool is_optimized, const OptimalComparison *opt, const one_tree_bound::Bound *lb = nullptr,
+                                        int64_t best_run = -1, uint32_t runs = 0)
 {
     std::string s = "{";
+    if (best_run >= 0) s += "\"best_run\":" + std::to_string(best_run) + ",";
     if (lb) s += "\"bound\":" + json_f64(lb->bound) + ",";
     if (lb && opt) s += "\"bound_gap_pct\":" + json_f64(lb->gap_pct((double)tour.total)) + ",";
     s += "\"cost\":" + json_f32(tour.total);
@@ -1761,7 +1817,9 @@ inline std::string format_solution_json(const Solution &tour, bool is_optimized,
         if (k) s += ',';
         s += std::to_string(tour.route()[k]);
     }
-    s += "]}\n";
+    s += "]";
+    if (best_run >= 0) s += ",\"runs\":" + std::to_string(runs);
+    s += "}\n";
     return s;
 }
 }  // namespace cli

@@ -56,6 +56,9 @@
 //               with --optimal-tour the comparison goes to stderr in text mode and into the JSON object in JSON mode
 //   own flags (no counterpart in the reference): --seed S (LK kicks and the shuffle stage; the reference draws both from an
 //   unseeded thread RNG), --best-sweep (TL_MODE_BEST_SWEEP), --device N, --stats,
+//   `solve lk --runs K [--seed S]` with K >= 2 (and `pipeline --steps ...,lk --runs K`): K seeded runs of the last lk stage at once
+//   (tl_lk_population: run r is the search of seed tl_lk_run_seed(S, r), all from the stage's warm start), the best printed; --stats then
+//   also reports best_run, --output-format json gains "best_run" and "runs"; without --runs, or with K = 1, the output is what it was,
 //   `solve 2opt --runs K [--seed S] [--best-sweep]` with K >= 2: K seeded restarts at once (tl_two_opt_multistart), the best printed,
 //   --stats then also reports best_restart; without --runs, or with K = 1, the output is what it was,
 //   --exact-walk (TL_FLAG_BHK_EXACT_WALK: bhk reads its route back by exact equality instead of the reference's tolerance walk, whose
@@ -104,6 +107,7 @@ struct Args {
                  "                         [--mutation-probability P] [--n-elite N] [--ga-runs K]\n"
                  "                         [--alpha A] [--beta B] [--evaporation-rate R] [--num-ants N] [--runs K]\n"
                  "                         (solve 2opt --runs K: K seeded restarts of --seed at once, the best printed)\n"
+                 "                         (solve lk --runs K: K seeded runs of --seed at once from the same start, the best printed)\n"
                  "                         [--max-nodes N] [--time-limit-ms T]\n"
                  "       teeline-gpu pipeline --steps=nn,2opt,... | --steps=greedy_edge,2opt,... | --steps=savings,2opt,... | --steps=christofides,lk,... [-i FILE] [options as above]\n"
                  "       teeline-gpu bound -i FILE [--upper U | --tour FILE] [--root R] [--iterations T] [--lambda L,L,...] [--patience P,P,...] [--output-format text|json]\n"
@@ -368,6 +372,7 @@ int run(int argc, char **argv)
             }
             stages = parse_steps(a.steps);
         }
+        if (a.cmd != "bound" && a.runs >= 2 && !stages.empty() && stages.back() == Solvers::LinKernighan) a.opt.lk_runs = a.runs;  // seeded runs of the last lk stage
         for (const auto &w : pipeline::stage_warnings(stages)) std::fprintf(stderr, "warning: %s\n", w.c_str());
 
         tsplib::TspLibData data;
@@ -501,7 +506,7 @@ int run(int argc, char **argv)
         const bool have_cmp = have_opt && cli::compute_optimal_comparison(ctx, tour.total, problem, ot, cmp);
         one_tree_bound::Bound lb;
         if (a.lower_bound) lb = one_tree_bound::bound(ctx, problem, (double)tour.total);  // the solved tour is the upper bound
-        if (json_mode) std::fputs(cli::format_solution_json(tour, false, have_cmp ? &cmp : nullptr, a.lower_bound ? &lb : nullptr).c_str(), stdout);
+        if (json_mode) std::fputs(cli::format_solution_json(tour, false, have_cmp ? &cmp : nullptr, a.lower_bound ? &lb : nullptr, outcomes.back().best_run, a.opt.lk_runs).c_str(), stdout);
         else if (have_cmp) std::fputs(cli::format_optimal_comparison(tour.total, cmp).c_str(), stderr);
         if (a.lower_bound && !json_mode) std::fputs(cli::format_lower_bound(tour.total, lb).c_str(), stderr);
         if (a.timing) {
@@ -515,6 +520,7 @@ int run(int argc, char **argv)
                              o.solution.total, (unsigned long long)o.solution.stats.sweeps, (unsigned long long)o.solution.stats.candidates,
                              (unsigned long long)o.solution.stats.moves, o.solution.stats.kernel_ms, (unsigned long long)o.duration_ms);
                 if (o.best_restart >= 0) std::fprintf(stderr, " best_restart=%lld", (long long)o.best_restart);
+                if (o.best_run >= 0) std::fprintf(stderr, " best_run=%lld", (long long)o.best_run);
                 std::fprintf(stderr, "\n");
             }
         return 0;
