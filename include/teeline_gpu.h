@@ -1361,6 +1361,45 @@ int tl_one_tree_bound_plan(uint32_t n, int lds_bytes, int *threads, uint32_t *it
 uint32_t tl_one_tree_bound_max_n(int lds_bytes);
 uint64_t tl_one_tree_bound_work_bytes(uint32_t n, uint32_t jobs, uint32_t log_cap);
 
+/* ---- alpha-nearness candidate lists under given penalties, and Lin-Kernighan on supplied lists ----- */
+/* This project's own specification (csrc/alpha_spec.h, tests/_alpha_oracle.py): Helsgaun's alpha-nearness over the
+ * two arrays tl_one_tree_bound hands back.  The 1-tree under pi (n doubles, NULL: all zero) with special position `root` is exactly
+ * the one described above, w(i, j) = (double)d(i, j) + (pi_i + pi_j); the entry rebuilds it from pi, and for the out_pi of a
+ * tl_one_tree_bound call the parents and root neighbours written here equal that call's out_parent and root_nb.
+ *   i != j, both != root: beta(i, j) = the largest w on the tree path between i and j; alpha(i, j) = w(i, j) - beta(i, j).
+ *   the root r with its neighbours a (chosen first) and b: alpha(r, a) = alpha(r, b) = 0, else alpha(r, j) = w(r, j) - w(r, b);
+ *   alpha(j, r) = alpha(r, j).
+ * beta is a maximum of doubles and therefore exact, alpha ONE defined subtraction per pair: device, host and numpy agree bit for
+ * bit.  alpha >= +0.0 always.  Row i of out_cand (n x k', k' = min(k, n - 1)) holds the positions j != i smallest by
+ * (alpha(i, j), w(i, j), j) — the doubles compared as numbers, the position last — in that order; out_alpha (optional, n x k')
+ * their values; out_parent (optional, n) and out_root_nb (optional, 2) the tree.
+ * TL_ERR_BADARG: root >= n (n >= 1), k == 0, threads neither 0 nor whole waves up to 1024.  TL_ERR_UNSUPPORTED: k > 64,
+ * n > tl_alpha_candidates_max_n (both before anything of size n is read); a coordinate or matrix entry tl_one_tree_bound refuses, a
+ * penalty that is not finite or beyond 2^1020.  n <= 2 is answered on the host (n == 2: each position's candidate is the other, alpha 0).
+ * threads: the workgroup of a source city, 0: the plan's; a launch parameter, the same result.  stats: sweeps = the tree's levels
+ * (a source's sweep takes one barrier fewer), candidates = alpha values formed, kernel_ms = the 1-tree's launch plus the rows' kernel.
+ * tl_alpha_candidates_host: the sequential O(n^2) restatement on the CPU (no context, no device), the same contract, n <= 65 535.
+ * tl_alpha_candidates_plan: the threads of a source's workgroup and the LDS of its row (16 n bytes); tl_alpha_candidates_max_n: the
+ * largest n whose 1-tree state (24 n bytes) and row fit lds_bytes.
+ *
+ * tl_lk_candidates: a setting of the context, like tl_lk_population_setting (the flag bits are used up).  The call copies n x k
+ * positions; every later tl_lk, tl_lk_trace, tl_lk_live and tl_lk_population on this context searches these lists instead of the
+ * kd-tree's.  cand == NULL or k == 0 clears them, and every LK entry does again exactly what it does without the setting.
+ * TL_ERR_BADARG, the message naming the row: a row that holds its own position, a repeat, or a position >= n; also k > 64 and
+ * k > n - 1.  While lists are set: an LK call with another n returns TL_ERR_BADARG naming the setting; opts->n_nearest is ignored —
+ * the list width is k wherever LK sizes by it (key bits, queue capacity, tl_lk_population_max_n; tl_lk_population_plan takes no
+ * context: pass n_nearest = k); the nearest-neighbour seed of init_pos == NULL is untouched.
+ * ALPHA CHOOSES THE SET, DISTANCE ORDERS IT: the kernels search a row in ascending f32 Euclidean distance, so at each LK call the
+ * stored rows are put into ascending dist(xy_i, xy_j) order — stably: equal distances keep the supplied order — before anything
+ * reads them.  The results equal the reference's lin_kernighan on the rows so ordered. */
+int tl_alpha_candidates(tl_ctx *ctx, const float *xy, const float *dm_packed, uint32_t n, const double *pi, uint32_t root, uint32_t k,
+                        uint32_t threads, uint32_t *out_cand, double *out_alpha, uint32_t *out_parent, uint32_t *out_root_nb, tl_stats *stats);
+int tl_alpha_candidates_host(const float *xy, const float *dm_packed, uint32_t n, const double *pi, uint32_t root, uint32_t k, uint32_t *out_cand,
+                             double *out_alpha, uint32_t *out_parent, uint32_t *out_root_nb);
+int tl_alpha_candidates_plan(uint32_t n, uint32_t k, int lds_bytes, int *threads, uint32_t *lds_used);
+uint32_t tl_alpha_candidates_max_n(int lds_bytes);
+int tl_lk_candidates(tl_ctx *ctx, const uint32_t *cand, uint32_t n, uint32_t k);
+
 /* ---- device-resident batch entry (bench / pipelines that keep data in HBM) ------------------- */
 /* All d_* are DEVICE pointers on the context's device.  d_init: count x n u32 (NULL: seeded restarts
  * first..first+count as above; seed ignored otherwise).  d_out_pos: count x n u32, d_out_cost: count f32,

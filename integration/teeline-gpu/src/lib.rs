@@ -375,6 +375,13 @@ unsafe extern "C" {
     fn tl_one_tree_bound_plan(n: u32, lds_bytes: c_int, threads: *mut c_int, iters_per_launch: *mut u32) -> i32;
     fn tl_one_tree_bound_max_n(lds_bytes: c_int) -> u32;
     fn tl_one_tree_bound_work_bytes(n: u32, jobs: u32, log_cap: u32) -> u64;
+    fn tl_alpha_candidates(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, pi: *const f64, root: u32, k: u32, threads: u32,
+                           out_cand: *mut u32, out_alpha: *mut f64, out_parent: *mut u32, out_root_nb: *mut u32, stats: *mut Stats) -> i32;
+    fn tl_alpha_candidates_host(xy: *const f32, dm_packed: *const f32, n: u32, pi: *const f64, root: u32, k: u32, out_cand: *mut u32,
+                                out_alpha: *mut f64, out_parent: *mut u32, out_root_nb: *mut u32) -> i32;
+    fn tl_alpha_candidates_plan(n: u32, k: u32, lds_bytes: c_int, threads: *mut c_int, lds_used: *mut u32) -> i32;
+    fn tl_alpha_candidates_max_n(lds_bytes: c_int) -> u32;
+    fn tl_lk_candidates(ctx: *mut TlCtx, cand: *const u32, n: u32, k: u32) -> i32;
     fn tl_nearest_neighbor(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, n_nearest: u32,
                            out_pos: *mut u32, out_cost: *mut f32) -> c_int;
     fn tl_greedy_edge(ctx: *mut TlCtx, xy: *const f32, dm_packed: *const f32, n: u32, out_pos: *mut u32, out_cost: *mut f32,
@@ -1101,6 +1108,78 @@ impl Context {
         pi.truncate(n as usize);
         tour.truncate(n as usize);
         Ok(OneTreeBound { result: res, pi, tour: if res.is_tour != 0 { Some(tour) } else { None } })
+    }
+
+    /// Alpha-nearness candidate lists (this project's own specification) under the penalties `pi` (None: zero),
+    /// usually a `OneTreeBound`'s: n rows of min(k, n - 1) POSITIONS in (alpha, w, position) order, and their alphas.  (Written
+    /// against the header; not compiled here: no Rust toolchain on the build machine, see scripts/check_rust.sh.)
+    pub fn alpha_candidates(&self, xy: &[f32], dm_packed: Option<&[f32]>, pi: Option<&[f64]>, root: u32, k: u32) -> Result<(Vec<u32>, Vec<f64>), Error> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, None);
+        assert!(pi.map_or(true, |p| p.len() == n as usize), "alpha_candidates: pi must hold n penalties");
+        let kk = (k.min(n.saturating_sub(1)).min(64)) as usize;
+        let mut rows = vec![0u32; (n as usize * kk).max(1)];
+        let mut alpha = vec![0f64; (n as usize * kk).max(1)];
+        let mut st = Stats::default();
+        // SAFETY: the slices hold n cities and n penalties; the outputs hold n x min(k, n - 1) entries; the tree's outputs are null.
+        let rc = unsafe {
+            tl_alpha_candidates(self.raw, xy.as_ptr(), opt_ptr(dm_packed), n, pi.map_or(ptr::null(), |p| p.as_ptr()), root, k, 0, rows.as_mut_ptr(),
+                                alpha.as_mut_ptr(), ptr::null_mut(), ptr::null_mut(), &mut st)
+        };
+        self.check(rc)?;
+        rows.truncate(n as usize * kk);
+        alpha.truncate(n as usize * kk);
+        Ok((rows, alpha))
+    }
+
+    /// The sequential restatement on the CPU (no context, no device), the same contract: the library's return code on refusal.
+    pub fn alpha_candidates_host(xy: &[f32], dm_packed: Option<&[f32]>, pi: Option<&[f64]>, root: u32, k: u32) -> Result<(Vec<u32>, Vec<f64>), i32> {
+        let n = Self::n_of(xy);
+        Self::check_inputs(n, dm_packed, None);
+        assert!(pi.map_or(true, |p| p.len() == n as usize), "alpha_candidates_host: pi must hold n penalties");
+        let kk = (k.min(n.saturating_sub(1)).min(64)) as usize;
+        let mut rows = vec![0u32; (n as usize * kk).max(1)];
+        let mut alpha = vec![0f64; (n as usize * kk).max(1)];
+        // SAFETY: as alpha_candidates.
+        let rc = unsafe {
+            tl_alpha_candidates_host(xy.as_ptr(), opt_ptr(dm_packed), n, pi.map_or(ptr::null(), |p| p.as_ptr()), root, k, rows.as_mut_ptr(), alpha.as_mut_ptr(),
+                                     ptr::null_mut(), ptr::null_mut())
+        };
+        if rc != 0 {
+            return Err(rc);
+        }
+        rows.truncate(n as usize * kk);
+        alpha.truncate(n as usize * kk);
+        Ok((rows, alpha))
+    }
+
+    /// The largest n of `alpha_candidates` on `lds_bytes` of LDS.
+    pub fn alpha_candidates_max_n(lds_bytes: i32) -> u32 {
+        // SAFETY: a host-only query.
+        unsafe { tl_alpha_candidates_max_n(lds_bytes) }
+    }
+
+    /// (threads of a source city's workgroup, LDS bytes of its row) for n cities and lists of width k; None where the pair is refused.
+    pub fn alpha_candidates_plan(n: u32, k: u32, lds_bytes: i32) -> Option<(i32, u32)> {
+        let (mut t, mut used) = (0 as c_int, 0u32);
+        // SAFETY: a host-only query with two live outputs.
+        let rc = unsafe { tl_alpha_candidates_plan(n, k, lds_bytes, &mut t, &mut used) };
+        if rc == 0 { Some((t, used)) } else { None }
+    }
+
+    /// tl_lk_candidates: every later Lin-Kernighan call of this context searches `rows` (n x k POSITIONS, e.g. `alpha_candidates`')
+    /// instead of the kd-tree's lists; None clears them.  Alpha chooses the set, distance orders it: the library puts every row into
+    /// ascending Euclidean distance, stably, before a search reads it.
+    pub fn lk_candidates(&self, rows: Option<(&[u32], u32, u32)>) -> Result<(), Error> {
+        let rc = match rows {
+            None => unsafe { tl_lk_candidates(self.raw, ptr::null(), 0, 0) }, // SAFETY: NULL clears
+            Some((r, n, k)) => {
+                assert!(r.len() == n as usize * k as usize, "lk_candidates: rows must hold n x k positions");
+                // SAFETY: the slice holds n x k entries; the library copies them.
+                unsafe { tl_lk_candidates(self.raw, r.as_ptr(), n, k) }
+            }
+        };
+        self.check(rc)
     }
 
     /// The largest n whose state fits `lds_bytes` of LDS, and (threads, iterations of a launch) for n, None where n is refused.

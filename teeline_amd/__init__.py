@@ -13,13 +13,13 @@ from ._capi import (TL_BHK_MAX_N, TL_FLAG_3OPT_POP_FORCE_SCAN, TL_FLAG_3OPT_POP_
                     TL_FLAG_LK_CHIP_WIDE, TL_FLAG_LK_CLASSIC_VIEW, TL_FLAG_LK_ILS_LDS, TL_FLAG_LK_NO_GRAPH, TL_FLAG_LK_NO_SPECULATION, TL_FLAG_LK_NO_SUBCHAINS, TL_FLAG_LK_ONE_WORKGROUP, TL_FLAG_LK_SCAN_PERSIST, TL_FLAG_LK_SEPARATE_PICK, TL_FLAG_LK_SEPARATE_STEP, TL_FLAG_LK_SMALL, TL_FLAG_LK_SPLIT2, TL_FLAG_MULTISTART_RCCL, TL_FLAG_NONE, TL_FLAG_NO_PRUNE, TL_FLAG_OR_OPT_FORCE_SCAN, TL_FLAG_SA_NO_SPECULATION, TL_FLAG_TABU_FULL_COMPARE,
                     TL_MODE_BEST_SWEEP, TL_MODE_REF_ORDER, ReferencePanics, TeelineGpuError)
 from .host import (Context, HeuristicOptions, KDPoint, LKOptions, SAOptions, Solution, TspProblem, default_context,
-                   ant_colony, bellman_karp, branch_and_bound, christofides, cuckoo_search, distance_matrix, flower_pollination, fourier_curve, genetic_algorithm, gravitational_search, greedy_edge, hill_climb, kohonen_som, lin_kernighan, multistart, nearest_neighbor, one_tree_bound, opt_tour, or_opt, particle_swarm, pipeline, savings, simulated_annealing, synth, tabu_search, three_opt, tsplib,
+                   alpha_candidates, ant_colony, bellman_karp, branch_and_bound, christofides, cuckoo_search, distance_matrix, flower_pollination, fourier_curve, genetic_algorithm, gravitational_search, greedy_edge, hill_climb, kohonen_som, lin_kernighan, multistart, nearest_neighbor, one_tree_bound, opt_tour, or_opt, particle_swarm, pipeline, savings, simulated_annealing, synth, tabu_search, three_opt, tsplib,
                    two_opt,
                    validate_tour)
 
 __all__ = [
     "Context", "HeuristicOptions", "KDPoint", "LKOptions", "SAOptions", "Solution", "TspProblem", "default_context",
-    "distance_matrix", "greedy_edge", "savings", "christofides", "bellman_karp", "branch_and_bound", "lin_kernighan", "simulated_annealing", "tabu_search", "genetic_algorithm", "ant_colony", "particle_swarm", "cuckoo_search", "flower_pollination", "gravitational_search", "kohonen_som", "hill_climb", "fourier_curve", "one_tree_bound", "three_opt", "tsplib", "two_opt", "validate_tour",
+    "distance_matrix", "greedy_edge", "savings", "christofides", "bellman_karp", "branch_and_bound", "lin_kernighan", "simulated_annealing", "tabu_search", "genetic_algorithm", "ant_colony", "particle_swarm", "cuckoo_search", "flower_pollination", "gravitational_search", "kohonen_som", "hill_climb", "fourier_curve", "one_tree_bound", "alpha_candidates", "three_opt", "tsplib", "two_opt", "validate_tour",
     "TL_MODE_REF_ORDER", "TL_MODE_BEST_SWEEP", "TL_FLAG_NONE", "TL_FLAG_NO_PRUNE", "TL_FLAG_BHK_EXACT_WALK", "TL_BHK_MAX_N",
     "TeelineGpuError", "ReferencePanics",
 ]

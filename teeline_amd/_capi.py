@@ -85,6 +85,7 @@ SYMBOLS = [
     "tl_branch_and_bound", "tl_branch_and_bound_host", "tl_branch_and_bound_plan",
     "tl_one_tree_bound", "tl_one_tree_bound_batch", "tl_one_tree_bound_host", "tl_one_tree_bound_plan", "tl_one_tree_bound_max_n",
     "tl_one_tree_bound_work_bytes",
+    "tl_alpha_candidates", "tl_alpha_candidates_host", "tl_alpha_candidates_plan", "tl_alpha_candidates_max_n", "tl_lk_candidates",
 ]
 
 
@@ -429,5 +430,11 @@ def load():
     L.tl_one_tree_bound_max_n.restype = u32
     L.tl_one_tree_bound_work_bytes.argtypes = [u32, u32, u32]
     L.tl_one_tree_bound_work_bytes.restype = u64
+    L.tl_alpha_candidates.argtypes = [vp, vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp, C.POINTER(TlStats)]
+    L.tl_alpha_candidates_host.argtypes = [vp, vp, u32, vp, u32, u32, vp, vp, vp, vp]
+    L.tl_alpha_candidates_plan.argtypes = [u32, u32, i32, C.POINTER(i32), C.POINTER(u32)]
+    L.tl_alpha_candidates_max_n.argtypes = [i32]
+    L.tl_alpha_candidates_max_n.restype = u32
+    L.tl_lk_candidates.argtypes = [vp, vp, u32, u32]
     _lib = L
     return L

@@ -13,8 +13,8 @@ CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libteeline_gpu.so")
 
-SOURCES = ["tl_api.hip", "tl_api_two_opt.hip", "tl_api_scans.hip", "tl_api_lk.hip", "tl_api_greedy.hip", "tl_api_bhk.hip", "tl_api_sa.hip", "tl_api_tabu.hip", "tl_api_ga.hip", "tl_api_aco.hip", "tl_api_pso.hip", "tl_api_cs.hip", "tl_api_fpa.hip", "tl_api_gsa.hip", "tl_api_som.hip", "tl_api_hill.hip", "tl_api_fourier.hip", "tl_api_bnb.hip", "tl_api_onetree.hip", "two_opt_ref.hip", "two_opt_nl.hip", "two_opt_dm.hip", "dm_build.hip", "three_opt.hip", "three_opt_pop.hip", "lk.hip", "lk_deep.hip", "nn_knn.hip", "two_opt_best.hip", "two_opt_best_lds.hip", "or_opt.hip", "or_opt_lds.hip", "two_opt_large.hip", "kdtree.hip", "greedy_edge.hip", "christofides.hip", "bellman_karp.hip", "sim_anneal.hip", "tabu_search.hip", "genetic.hip", "ant_colony.hip", "particle_swarm.hip", "cuckoo_search.hip", "flower_pollination.hip", "gravitational_search.hip", "kohonen_som.hip", "hill_climb.hip", "fourier_curve.hip", "branch_and_bound.hip", "one_tree_bound.hip"]
-HEADERS = ["tl_device.h", "tl_kernels.h", "two_opt_common.h", "two_opt_best_scan.h", "or_opt_scan.h", "three_opt_scan.h", "chain_tour.h", "swarm_tour.h", "lk_chain.h", "lk_one_workgroup.h", "lk_scan.h", "lk_scan_persist.h", "lk_ils.h", "lk_ils_body.h", "sa_spec.h", "tabu_spec.h", "ga_spec.h", "aco_spec.h", "pso_spec.h", "cs_spec.h", "levy_spec.h", "fpa_spec.h", "gsa_spec.h", "som_spec.h", "hill_spec.h", "fourier_spec.h", "one_tree_spec.h", "swap_seq.h", "tl_api_common.h", "tl_api_chains.h", "tl_api_swarm.h", os.path.join(ROOT, "include", "teeline_gpu.h")]
+SOURCES = ["tl_api.hip", "tl_api_two_opt.hip", "tl_api_scans.hip", "tl_api_lk.hip", "tl_api_greedy.hip", "tl_api_bhk.hip", "tl_api_sa.hip", "tl_api_tabu.hip", "tl_api_ga.hip", "tl_api_aco.hip", "tl_api_pso.hip", "tl_api_cs.hip", "tl_api_fpa.hip", "tl_api_gsa.hip", "tl_api_som.hip", "tl_api_hill.hip", "tl_api_fourier.hip", "tl_api_bnb.hip", "tl_api_onetree.hip", "tl_api_alpha.hip", "two_opt_ref.hip", "two_opt_nl.hip", "two_opt_dm.hip", "dm_build.hip", "three_opt.hip", "three_opt_pop.hip", "lk.hip", "lk_deep.hip", "nn_knn.hip", "two_opt_best.hip", "two_opt_best_lds.hip", "or_opt.hip", "or_opt_lds.hip", "two_opt_large.hip", "kdtree.hip", "greedy_edge.hip", "christofides.hip", "bellman_karp.hip", "sim_anneal.hip", "tabu_search.hip", "genetic.hip", "ant_colony.hip", "particle_swarm.hip", "cuckoo_search.hip", "flower_pollination.hip", "gravitational_search.hip", "kohonen_som.hip", "hill_climb.hip", "fourier_curve.hip", "branch_and_bound.hip", "one_tree_bound.hip", "alpha_candidates.hip"]
+HEADERS = ["tl_device.h", "tl_kernels.h", "two_opt_common.h", "two_opt_best_scan.h", "or_opt_scan.h", "three_opt_scan.h", "chain_tour.h", "swarm_tour.h", "lk_chain.h", "lk_one_workgroup.h", "lk_scan.h", "lk_scan_persist.h", "lk_ils.h", "lk_ils_body.h", "sa_spec.h", "tabu_spec.h", "ga_spec.h", "aco_spec.h", "pso_spec.h", "cs_spec.h", "levy_spec.h", "fpa_spec.h", "gsa_spec.h", "som_spec.h", "hill_spec.h", "fourier_spec.h", "one_tree_spec.h", "alpha_spec.h", "swap_seq.h", "tl_api_common.h", "tl_api_chains.h", "tl_api_swarm.h", os.path.join(ROOT, "include", "teeline_gpu.h")]
 
 # -ffp-contract=off: the reference never fuses mul+add (src/tsp/kdtree.rs:291-295); bit-exact parity
 # depends on it.  Correctly rounded sqrt/div is hipcc's default and is spelled out here on purpose.

@@ -8,6 +8,9 @@
 
 namespace tlapi {
 
+// tl_api_onetree.hip: nullptr where every distance of the instance is finite and >= +0.0, else what is wrong (also tl_api_alpha.hip's rule)
+const char *one_tree_bad_input(const float *xy, const float *dm_packed, uint32_t n);
+
 // The first checks of a call over `count` chains (noun "chain") or runs ("run") numbered from `first`.  count == 0 passes: the
 // caller returns TL_OK at once.  init_count: 0 (city order), 1 (one start tour) or count.
 inline int check_chain_call(tl_ctx *c, const char *who, const float *xy, const float *dm_packed, uint32_t count, const uint32_t *out_pos,

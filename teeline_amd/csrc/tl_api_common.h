@@ -55,6 +55,10 @@ struct tl_ctx {
     bool two_opt_best_force_scan = false;  // tl_two_opt_best_force_scan: best-sweep batches loop over the chip-wide descent at every n
     int lk_pop_force_form = -1;          // tl_lk_population_setting: -1 the plan's choice, 0 the loop over tl_lk, 1 one workgroup per run
     uint32_t lk_pop_slice_scans = 0;     // ... and the scans per launch of that form (0: kLkIlsSlice)
+    // tl_lk_candidates: lk_cand_n x lk_cand_k positions every LK entry searches instead of the kd-tree's lists (empty: none set), and
+    // the copy the call in progress has put into ascending distance
+    std::vector<uint32_t> lk_cand, lk_cand_sorted;
+    uint32_t lk_cand_n = 0, lk_cand_k = 0;
     uint64_t three_opt_pop_work = 0;  // tl_three_opt_population: cap on the per-tour matrices' workspace (0: the default)
     uint32_t dm_n = 0;
     int dm_layout = -1;

@@ -25,8 +25,8 @@ static const char *one_tree_invalid(const tl_one_tree_opts &o, uint32_t n)
     return nullptr;
 }
 
-// nullptr: every distance of the instance is finite and >= +0.0
-static const char *one_tree_bad_input(const float *xy, const float *dm_packed, uint32_t n)
+// nullptr: every distance of the instance is finite and >= +0.0 (tl_api_alpha.hip holds its input to the same rules)
+const char *tlapi::one_tree_bad_input(const float *xy, const float *dm_packed, uint32_t n)
 {
     if (dm_packed) {
         const size_t m = (size_t)n * (n - 1) / 2;

@@ -691,6 +691,25 @@ uint32_t one_tree_max_n(int lds_bytes);    // the largest n whose state fits
 int one_tree_threads(uint32_t n);          // n in whole waves, 64 .. 1024
 hipError_t launch_one_tree_ascent(const OneTreeArgs &A, uint32_t jobs, int threads, hipStream_t s);  // one workgroup per job
 
+// alpha_candidates.hip — alpha-nearness under given penalties, one workgroup per source city, its beta / alpha row in LDS
+struct AlphaNode;  // alpha_spec.h
+struct AlphaArgs {
+    const float2 *xy;           // coordinate form
+    const float *dm_full;       // matrix form: the expanded n x n matrix (then xy is not read)
+    const double *pi;           // [n]
+    const AlphaNode *by_pos;    // [n] the 1-tree's positions: parent, w(v, parent)
+    const AlphaNode *by_level;  // [n - 1] the same in level order from Prim's start
+    const uint32_t *level_at;   // [levels + 1] where a level begins in by_level
+    uint32_t *out_cand;         // [n][kk]
+    double *out_alpha;          // [n][kk] or nullptr
+    uint32_t n, kk, levels;
+    uint32_t root, nb0, nb1;    // the special position and its two neighbours in the order chosen
+};
+size_t alpha_rows_lds_bytes(uint32_t n);    // w and beta / alpha of a row: 16 n bytes
+uint32_t alpha_rows_max_n(int lds_bytes);   // the largest n whose row fits
+int alpha_rows_threads(uint32_t n);         // n in whole waves, 64 .. 256
+hipError_t launch_alpha_rows(const AlphaArgs &A, int threads, hipStream_t s);  // one workgroup per source
+
 // lk.hip
 struct LkState {          // device-side state machine of the multi-CU LK variant
     uint32_t key;            // min pair index with a valid chain in the current scan (0xFFFFFFFF: none)

@@ -87,6 +87,24 @@ class Context:
         default) — the cross-check of the two forms."""
         self.check(self._lib.tl_lk_population_setting(self._h, int(force_form), int(slice_scans)))
 
+    def lk_candidates(self, rows=None):
+        """tl_lk_candidates: every later lin_kernighan.solve / solve_population on this context searches these lists (n x k POSITIONS,
+        e.g. alpha_candidates.candidates(...).rows) instead of the kd-tree's; None clears them.  Alpha chooses the set, distance orders
+        it: the library puts every row into ascending Euclidean distance (stably) before a search reads it."""
+        if rows is None:
+            self.check(self._lib.tl_lk_candidates(self._h, None, 0, 0))
+            self._lk_rows = None
+            return
+        rows = np.array(rows, dtype=np.uint32, order="C")  # (a copy: lk_candidates_set hands it back)
+        if rows.ndim != 2:
+            raise TeelineGpuError(_capi.TL_ERR_BADARG, f"lk_candidates: rows has shape {rows.shape}, not (n, k)")
+        self.check(self._lib.tl_lk_candidates(self._h, rows.ctypes.data_as(C.c_void_p), rows.shape[0], rows.shape[1]))
+        self._lk_rows = rows
+
+    def lk_candidates_set(self):
+        """The rows last set through lk_candidates on this context (a refused setting leaves the earlier ones), or None."""
+        return getattr(self, "_lk_rows", None)
+
     def lk_population_max_n(self, opts=None):
         """tl_lk_population_max_n: the largest n whose runs take one workgroup each with these LKOptions (None: the library defaults)."""
         o = None if opts is None else C.byref(_capi.TlLkOpts(opts.heuristic.epochs, opts.heuristic.platoo_epochs, opts.heuristic.n_nearest, opts.max_depth))
@@ -237,5 +255,5 @@ def validate_tour(tour_ids, problem):
     return ids == sorted(int(v) for v in problem.ids)
 
 
-from . import ant_colony, bellman_karp, branch_and_bound, christofides, cuckoo_search, flower_pollination, fourier_curve, genetic_algorithm, gravitational_search, greedy_edge, hill_climb, kohonen_som, lin_kernighan, multistart, nearest_neighbor, one_tree_bound, opt_tour, or_opt, particle_swarm, pipeline, savings, simulated_annealing, synth, tabu_search, three_opt, tsplib, two_opt  # noqa: E402,F401
+from . import alpha_candidates, ant_colony, bellman_karp, branch_and_bound, christofides, cuckoo_search, flower_pollination, fourier_curve, genetic_algorithm, gravitational_search, greedy_edge, hill_climb, kohonen_som, lin_kernighan, multistart, nearest_neighbor, one_tree_bound, opt_tour, or_opt, particle_swarm, pipeline, savings, simulated_annealing, synth, tabu_search, three_opt, tsplib, two_opt  # noqa: E402,F401
 from .simulated_annealing import SAOptions  # noqa: E402,F401

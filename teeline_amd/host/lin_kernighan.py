@@ -4,8 +4,28 @@ import ctypes as C
 import numpy as np
 
 
-def solve(problem, opts=None, progress_tx=None, init_tour=None, *, ctx=None, seed=1):
-    """progress_tx: optional callable(kind, payload) — the reference's mpsc::Sender<ProgressMessage>.  The reference sends
+class _Lists:
+    """`candidates=` of a solve: the context searches these rows for the length of the call, then has again the lists it was found
+    with (those set through Context.lk_candidates, or none)."""
+
+    def __init__(self, ctx, rows):
+        self.ctx, self.rows, self.before = ctx, rows, None
+
+    def __enter__(self):
+        if self.rows is not None:
+            self.before = self.ctx.lk_candidates_set()
+            self.ctx.lk_candidates(self.rows)
+
+    def __exit__(self, *exc):
+        if self.rows is not None:
+            self.ctx.lk_candidates(self.before)
+        return False
+
+
+def solve(problem, opts=None, progress_tx=None, init_tour=None, *, ctx=None, seed=1, candidates=None):
+    """candidates: n x k POSITIONS (e.g. alpha_candidates.candidates(problem, k, pi).rows) searched instead of the kd-tree's lists
+    (tl_lk_candidates for the length of this call; opts.heuristic.n_nearest is then ignored, the width is k).
+    progress_tx: optional callable(kind, payload) — the reference's mpsc::Sender<ProgressMessage>.  The reference sends
     PathUpdate(best_tour, best_dist) after the first lk_pass and after every epoch that improves on it, and no Done
     (lin_kernighan.rs:71,90; nothing when n < 4, :57-59).  With a channel the solve goes through tl_lk_live: the device-side state
     machine files exactly those tours and distances and the host hands them on while the search runs (tl_lk_trace lists the same
@@ -29,7 +49,8 @@ def solve(problem, opts=None, progress_tx=None, init_tour=None, *, ctx=None, see
             None if init_pos is None else init_pos.ctypes.data_as(C.c_void_p), C.byref(o), int(seed),
             out.ctypes.data_as(C.c_void_p), C.byref(cost), C.byref(st))
     if progress_tx is None or n < 4:
-        ctx.check(ctx.lib.tl_lk(*args))
+        with _Lists(ctx, candidates):
+            ctx.check(ctx.lib.tl_lk(*args))
     else:
         # with a channel: tl_lk_live calls back WHILE the device-side search runs (between two polls of its state machine), once
         # per best tour the ILS settles on, in order — the messages arrive as the reference's would, not after the solve
@@ -42,7 +63,8 @@ def solve(problem, opts=None, progress_tx=None, init_tour=None, *, ctx=None, see
                 err.append(exc)
 
         cb = _capi.LK_PROGRESS_FN(on_best)
-        ctx.check(ctx.lib.tl_lk_live(*args, cb, None))
+        with _Lists(ctx, candidates):
+            ctx.check(ctx.lib.tl_lk_live(*args, cb, None))
         if err:
             raise err[0]
     return Solution(cost.value, problem.ids[out], problem, st.as_dict())
@@ -85,8 +107,9 @@ def population_plan(n, opts=None, runs=2, *, cus=256, lds_bytes=163840, force_fo
     return {"form": f.value, "threads": t.value, "per_cu": p.value}
 
 
-def solve_population(problem, opts=None, init_tours=None, *, seed, runs, first_run=0, ctx=None):
-    """Seeded runs first_run .. first_run + runs - 1 of lin_kernighan::solve at once (tl_lk_population): run r is solve(...,
+def solve_population(problem, opts=None, init_tours=None, *, seed, runs, first_run=0, ctx=None, candidates=None):
+    """candidates: as in solve — the lists every run searches.
+    Seeded runs first_run .. first_run + runs - 1 of lin_kernighan::solve at once (tl_lk_population): run r is solve(...,
     seed=run_seed(seed, r)), run 0 the plain seed's.  init_tours: None (the NN seed solve would build), one tour of city ids for all
     runs, or `runs` of them.  Returns (solutions, best): one Solution per run with that run's own counters in its stats (the call's
     times), and the index of the cheapest (equal totals: the lowest run)."""
@@ -112,11 +135,12 @@ def solve_population(problem, opts=None, init_tours=None, *, seed, runs, first_r
     best = C.c_uint32()
     st = _capi.TlStats()
     packed = problem.explicit_packed()
-    ctx.check(ctx.lib.tl_lk_population(ctx.handle, problem.xy.ctypes.data_as(C.c_void_p), n,
-                                       None if packed is None else packed.ctypes.data_as(C.c_void_p),
-                                       None if init is None else init.ctypes.data_as(C.c_void_p), 0 if init is None else len(init),
-                                       int(first_run), runs, C.byref(o), int(seed) & (2**64 - 1), out.ctypes.data_as(C.c_void_p),
-                                       costs.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p), C.byref(best), C.byref(st)))
+    with _Lists(ctx, candidates):
+        ctx.check(ctx.lib.tl_lk_population(ctx.handle, problem.xy.ctypes.data_as(C.c_void_p), n,
+                                           None if packed is None else packed.ctypes.data_as(C.c_void_p),
+                                           None if init is None else init.ctypes.data_as(C.c_void_p), 0 if init is None else len(init),
+                                           int(first_run), runs, C.byref(o), int(seed) & (2**64 - 1), out.ctypes.data_as(C.c_void_p),
+                                           costs.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p), C.byref(best), C.byref(st)))
     stats = st.as_dict()
     sols = [Solution(float(costs[r]), problem.ids[out[r]], problem,
                      dict(stats, sweeps=int(cnt[r, 0]), candidates=int(cnt[r, 1]), moves=int(cnt[r, 2]), reversed=int(cnt[r, 3]))) for r in range(runs)]

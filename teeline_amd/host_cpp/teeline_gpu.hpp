@@ -1478,6 +1478,39 @@ inline Bound bound(Context &ctx, const TspProblem &problem, double upper, const 
 }
 }  // namespace one_tree_bound
 
+namespace alpha_candidates {  // alpha-nearness candidate lists of DESIGN.md §4.32 (this project's own specification) and LK on supplied lists
+struct Lists {
+    uint32_t n = 0, k = 0;            // k: min(asked, n - 1)
+    std::vector<uint32_t> rows;       // n x k POSITIONS in (alpha, w, position) order
+    std::vector<double> alpha;        // their values
+    std::vector<uint32_t> parent;     // the 1-tree they come from
+    uint32_t root_nb[2] = {TL_ONE_TREE_NONE, TL_ONE_TREE_NONE};
+    tl_stats stats{};
+};
+// pi: n penalties (usually a one_tree_bound::Bound's) or empty for zero
+inline Lists candidates(Context &ctx, const TspProblem &problem, uint32_t k, const std::vector<double> &pi = {}, uint32_t root = 0)
+{
+    const auto xy = problem.xy();
+    Lists L;
+    L.n = (uint32_t)problem.cities.size();
+    if (!pi.empty() && pi.size() != L.n) throw std::runtime_error("alpha_candidates: pi must hold one penalty per city");
+    L.k = std::min(k, L.n ? L.n - 1u : 0u);
+    L.rows.resize(std::max<size_t>((size_t)L.n * std::min(L.k, 64u), 1u));
+    L.alpha.resize(L.rows.size());
+    L.parent.resize(std::max(L.n, 1u));
+    ctx.check(tl_alpha_candidates(ctx.get(), xy.data(), problem.explicit_packed(), L.n, pi.empty() ? nullptr : pi.data(), root, k, 0u, L.rows.data(), L.alpha.data(),
+                                  L.parent.data(), L.root_nb, &L.stats));
+    L.rows.resize((size_t)L.n * L.k);
+    L.alpha.resize((size_t)L.n * L.k);
+    L.parent.resize(L.n);
+    return L;
+}
+// Every later lin_kernighan call of this context searches these lists (alpha chooses the set, distance orders it: the library puts
+// every row into ascending Euclidean distance, stably, before a search reads it); clear() restores the kd-tree's.
+inline void set_lk_lists(Context &ctx, const Lists &L) { ctx.check(tl_lk_candidates(ctx.get(), L.rows.data(), L.n, L.k)); }
+inline void clear_lk_lists(Context &ctx) { ctx.check(tl_lk_candidates(ctx.get(), nullptr, 0u, 0u)); }
+}  // namespace alpha_candidates
+
 // Solvers (mod.rs:47-72) this build accelerates, by the reference's names and aliases (FromStr, mod.rs:559-590)
 enum class Solvers { NearestNeighbor, TwoOpt, ThreeOpt, OrOpt, LinKernighan, RandomShuffle, GreedyEdge, Savings, Christofides, BellmanKarp, SimulatedAnnealing, TabuSearch, GeneticAlgorithm, AntColony, ParticleSwarm, CuckooSearch, FlowerPollination, GravitationalSearch, KohonenSom, HillClimb, FourierCurve, BranchAndBound };
 

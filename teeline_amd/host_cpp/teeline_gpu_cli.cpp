@@ -4,6 +4,9 @@
 //   teeline-gpu bound -i FILE [--upper U | --tour FILE] [--root R] [--iterations T] [--lambda L,L,..] [--patience P,P,..]
 //               [--output-format text|json]: the Held-Karp lower bound, the lists a grid of jobs; prints the best
 //               bound, its job, the upper bound used and the gap in percent, `proved=1` where the 1-tree is a tour
+//   teeline-gpu candidates --alpha -k K -i FILE [--ascent-iterations I] [--root R]: the alpha-nearness lists, a line per city
+//   solve lk / pipeline with an lk step --candidates alpha[:K] [--ascent-iterations I]: the ascent as `bound` runs it, the lists under its best
+//   penalties (I = 0: zero penalties), and every lk step searches them (tl_lk_candidates); --stats names the lists' kind and width
 //   solve / pipeline --lower-bound: the bound with the solved tour as upper; `bound` and `gap_pct` on stderr (text) or in the JSON object
 //   teeline-gpu solve <solver|preset> [-i FILE] [--no-seed] [--output-format text|json] [--optimal-tour FILE]
 //                                     [--distance-type euc_2d|geo] [--epochs E] [--platoo_epochs P] [--n_nearest K] [--max-depth D]
@@ -93,6 +96,10 @@ struct Args {
     std::string tour_file;
     one_tree_bound::BoundOptions bound_opt;
     std::vector<double> bound_patiences;  // --patience P,P,..: with --lambda L,L,.. a grid of jobs, lambda the outer index
+    // alpha-nearness candidate lists: `solve lk --candidates alpha[:K]` / pipelines with an lk step, and `candidates --alpha -k K`
+    bool cand_alpha = false;
+    uint32_t cand_k = 5;
+    size_t ascent_iterations = 1000;     // --ascent-iterations I; 0: zero penalties, no ascent
 };
 
 [[noreturn]] void usage_exit(const char *why)
@@ -111,6 +118,9 @@ struct Args {
                  "                         [--max-nodes N] [--time-limit-ms T]\n"
                  "       teeline-gpu pipeline --steps=nn,2opt,... | --steps=greedy_edge,2opt,... | --steps=savings,2opt,... | --steps=christofides,lk,... [-i FILE] [options as above]\n"
                  "       teeline-gpu bound -i FILE [--upper U | --tour FILE] [--root R] [--iterations T] [--lambda L,L,...] [--patience P,P,...] [--output-format text|json]\n"
+                 "       teeline-gpu candidates --alpha -k K -i FILE [--ascent-iterations I] [--root R]   (a line per city: its id, then its K candidates' ids)\n"
+                 "       solve lk and pipelines with an lk step take --candidates alpha[:K] [--ascent-iterations I]: the ascent as `bound` runs it (upper from nn,2opt;\n"
+                 "       I = 0: zero penalties), alpha-nearness lists of width K (5) under its best penalties, and every lk step searches them (--stats: lists=alpha:K)\n"
                  "       solve and pipeline also take --lower-bound: the Held-Karp bound with the solved tour as upper, `bound` and `gap_pct` on stderr or in the JSON object\n"
                  "       teeline-gpu solvers [--short]\n");
     std::exit(2);  // clap's usage-error exit code
@@ -147,7 +157,7 @@ Args parse(int argc, char **argv)
         if (argc < 3 || argv[2][0] == '-') usage_exit("solve: SOLVER_NAME is required");
         a.solver = argv[2];
         i = 3;
-    } else if (a.cmd != "pipeline" && a.cmd != "solvers" && a.cmd != "bound") {
+    } else if (a.cmd != "pipeline" && a.cmd != "solvers" && a.cmd != "bound" && a.cmd != "candidates") {
         usage_exit("unknown sub-command");
     }
     for (; i < argc; ++i) {
@@ -178,7 +188,7 @@ Args parse(int argc, char **argv)
         else if (s == "--mutation-probability" || s == "--mutation_probability") a.opt.ga.mutation_probability = a.opt.cs_mutation_probability = a.opt.fpa_mutation_probability = std::stof(val());
         else if (s == "--n-elite" || s == "--n_elite") a.opt.ga.n_elite = parse_usize(s, val());
         else if (s == "--ga-runs" || s == "--ga_runs") a.opt.ga_runs = (uint32_t)std::max<size_t>(1, parse_usize(s, val()));
-        else if (s == "--alpha") a.opt.aco.alpha = std::stof(val());
+        else if (s == "--alpha" && a.cmd != "candidates") a.opt.aco.alpha = std::stof(val());
         else if (s == "--beta") a.opt.aco.beta = std::stof(val());
         else if (s == "--evaporation-rate" || s == "--evaporation_rate") a.opt.aco.evaporation_rate = std::stof(val());
         else if (s == "--num-ants" || s == "--num_ants") a.opt.aco.num_ants = parse_usize(s, val());
@@ -226,6 +236,16 @@ Args parse(int argc, char **argv)
                 at = comma + 1;
             }
         }
+        else if (s == "--candidates") {  // alpha[:K]
+            const std::string v = val();
+            const size_t colon = v.find(':');
+            if (v.substr(0, colon) != "alpha") usage_exit("--candidates: alpha[:K]");
+            a.cand_alpha = true;
+            if (colon != std::string::npos) a.cand_k = (uint32_t)std::min<size_t>(parse_usize(s, v.substr(colon + 1)), 0xFFFFFFFFu);
+        }
+        else if (s == "--alpha" && a.cmd == "candidates") a.cand_alpha = true;
+        else if (s == "-k" && a.cmd == "candidates") a.cand_k = (uint32_t)std::min<size_t>(parse_usize(s, val()), 0xFFFFFFFFu);
+        else if (s == "--ascent-iterations" || s == "--ascent_iterations") a.ascent_iterations = parse_usize(s, val());
         else if (s == "--progress-digest") a.progress_digest = true;
         else if (s == "--timing") a.timing = true;
         else if (s == "--full-exit") a.full_exit = true;
@@ -235,6 +255,12 @@ Args parse(int argc, char **argv)
     if (a.output_format != "text" && a.output_format != "json") usage_exit("--output-format: text or json");
     if (!a.fourier_lambdas.empty()) a.opt.fourier.lambda = a.fourier_lambdas[0];
     if (!a.fourier_lrs.empty()) a.opt.fourier.lr = a.fourier_lrs[0];
+    if (a.cand_alpha && a.cand_k == 0) usage_exit("the candidate lists' K must be >= 1");
+    if (a.cmd == "candidates") {
+        if (!a.cand_alpha) usage_exit("candidates: --alpha is required (the kd-tree's lists have no command of their own)");
+        if (a.file.empty()) usage_exit("candidates: -i FILE is required");
+        return a;
+    }
     if (a.cmd == "bound") {
         if (a.file.empty()) usage_exit("bound: -i FILE is required");
         if (a.upper != 0.0 && !a.tour_file.empty()) usage_exit("bound: --upper or --tour, not both");
@@ -341,7 +367,7 @@ int run(int argc, char **argv)
         }
         std::vector<Solvers> stages;
         const bool json_mode = a.cmd == "solve" && a.output_format == "json";  // `pipeline` always prints text (main.rs:425,430)
-        if (a.cmd == "bound") {
+        if (a.cmd == "bound" || a.cmd == "candidates") {
             stages = {Solvers::NearestNeighbor, Solvers::TwoOpt};  // where neither --upper nor --tour gives the upper bound
         } else if (a.cmd == "solve") {
             std::string name = a.solver;
@@ -372,7 +398,7 @@ int run(int argc, char **argv)
             }
             stages = parse_steps(a.steps);
         }
-        if (a.cmd != "bound" && a.runs >= 2 && !stages.empty() && stages.back() == Solvers::LinKernighan) a.opt.lk_runs = a.runs;  // seeded runs of the last lk stage
+        if (a.cmd != "bound" && a.cmd != "candidates" && a.runs >= 2 && !stages.empty() && stages.back() == Solvers::LinKernighan) a.opt.lk_runs = a.runs;  // seeded runs of the last lk stage
         for (const auto &w : pipeline::stage_warnings(stages)) std::fprintf(stderr, "warning: %s\n", w.c_str());
 
         tsplib::TspLibData data;
@@ -477,6 +503,36 @@ int run(int argc, char **argv)
                             upper, upper_from.c_str(), b.gap_pct(upper), b.is_tour ? " proved=1" : "");
             return 0;
         }
+        // alpha-nearness lists: the ascent as `bound` runs it (upper from nn,2opt), its best penalties, the lists under them
+        auto alpha_lists = [&]() {
+            std::vector<double> pi;
+            if (a.ascent_iterations > 0) {
+                const double upper = (double)pipeline::run_pipeline_stages(ctx, problem, {Solvers::NearestNeighbor, Solvers::TwoOpt}, a.opt).back().solution.total;
+                one_tree_bound::BoundOptions bo = a.bound_opt;
+                bo.iterations = a.ascent_iterations;
+                pi = one_tree_bound::bound(ctx, problem, upper, bo).pi;
+            }
+            return alpha_candidates::candidates(ctx, problem, a.cand_k, pi, (uint32_t)std::min<size_t>(a.bound_opt.root, 0xFFFFFFFFu));
+        };
+        if (a.cmd == "candidates") {
+            const alpha_candidates::Lists L = alpha_lists();
+            for (uint32_t i = 0; i < L.n; ++i) {
+                std::printf("%zu:", problem.cities[i].id);
+                for (uint32_t q = 0; q < L.k; ++q) std::printf(" %zu", problem.cities[L.rows[(size_t)i * L.k + q]].id);
+                std::printf("\n");
+            }
+            return 0;
+        }
+        const bool has_lk = std::find(stages.begin(), stages.end(), Solvers::LinKernighan) != stages.end();
+        uint32_t lists_k = 0;  // != 0: every lk step searches alpha lists of this width
+        if (a.cand_alpha && !has_lk) std::fprintf(stderr, "warning: --candidates: no lk step searches them\n");
+        if (a.cand_alpha && has_lk) {
+            const alpha_candidates::Lists L = alpha_lists();
+            if (L.k >= 1u) {
+                alpha_candidates::set_lk_lists(ctx, L);
+                lists_k = L.k;
+            }
+        }
         if (a.progress_digest) a.opt.progress = &on_progress;
         std::string runs_json;
         std::vector<pipeline::StageOutcome> outcomes;
@@ -493,6 +549,7 @@ int run(int argc, char **argv)
             }
             runs_json += "]}";
         }
+        if (lists_k) alpha_candidates::clear_lk_lists(ctx);
         const auto t_out = clk::now();
         if (a.progress_digest) {
             std::fprintf(stderr, "progress: path_updates=%llu city_changes=%llu done=%llu digest=%016llx", (unsigned long long)dg.n[0],
@@ -521,6 +578,11 @@ int run(int argc, char **argv)
                              (unsigned long long)o.solution.stats.moves, o.solution.stats.kernel_ms, (unsigned long long)o.duration_ms);
                 if (o.best_restart >= 0) std::fprintf(stderr, " best_restart=%lld", (long long)o.best_restart);
                 if (o.best_run >= 0) std::fprintf(stderr, " best_run=%lld", (long long)o.best_run);
+                if (o.solver == Solvers::LinKernighan) {  // the lists the step searched: their kind and width
+                    const size_t n1 = problem.cities.empty() ? 0 : problem.cities.size() - 1;
+                    if (lists_k) std::fprintf(stderr, " lists=alpha:%u", lists_k);
+                    else std::fprintf(stderr, " lists=kdtree:%zu", std::min(a.opt.lk.heuristic.n_nearest, n1));
+                }
                 std::fprintf(stderr, "\n");
             }
         return 0;
